@@ -83,7 +83,13 @@ def parse():
     ap.add_argument("--replicate", choices=["rebuild", "broadcast"], default="broadcast",
                     help="N>1, how every rank gets the trie: rank 0 builds it and one RCCL broadcast replicates the image (default), "
                          "or each rank builds it from the same seeded input (no collective outside the bitmap gather)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the presence answers of the last step to DIR/*.npy (float32/float64, a fixed "
+                         "sample of the queries plus per-block counts of the whole bitmap), so that two builds can be compared")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(args):
@@ -202,6 +208,40 @@ def pmc_for(workload_key, nq, kmer_bytes, allow_live, opts=(), stored_key=None):
     return {"error": f"{err}; profiles/{PMC_FALLBACK} is for other sources"}, False
 
 
+DUMP_SAMPLE = 1 << 21  # queries whose answers --dump-outputs writes one by one (float32 answer + float64 index: 24 MiB)
+DUMP_BLOCKS = 1 << 21  # at most this many per-block counts of present answers over the whole bitmap (float32: 8 MiB)
+
+
+def dump_outputs(dirpath, bits, nq, world):
+    """--dump-outputs: what the timed path returned in its last step -- the presence bitmap of all `world` shards (`bits`: uint8
+    device tensor, `world` shards of ((nq + 63) // 64) * 8 bytes each, nq answers per shard) -- as .npy files in `dirpath`:
+      presence.npy              float32 0/1 answers of a fixed sample of the queries (all of them when there are at most DUMP_SAMPLE);
+      presence_index.npy        float64 position of each of those queries in the batch (rank r's shard at r * nq);
+      presence_block_count.npy  float32 number of present answers in each block of consecutive queries (blocks of a multiple of 64 queries,
+                                at most DUMP_BLOCKS of them), so that every answer of the batch counts somewhere.
+    The sample is drawn by a fixed seed from the batch size alone: the same arguments give the same files for the same answers."""
+    import torch
+    from bloomfiltertrie_amd import workloads as W
+    os.makedirs(dirpath, exist_ok=True)
+    shards = bits.view(world, -1)
+    ans = torch.cat([W.bits_to_bool(shards[r], nq) for r in range(world)])
+    n = ans.numel()
+    if n <= DUMP_SAMPLE:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(20240).integers(0, n, DUMP_SAMPLE, dtype=np.int64))
+    sample = ans[torch.from_numpy(idx).to(ans.device)].float().cpu().numpy()
+    blk = 64 * max(1, -(-n // (64 * DUMP_BLOCKS)))
+    padded = torch.zeros(-(-n // blk) * blk, dtype=torch.int32, device=ans.device)
+    padded[:n] = ans.to(torch.int32)
+    counts = padded.view(-1, blk).sum(1).float().cpu().numpy()
+    files = {"presence": sample.astype(np.float32), "presence_index": idx.astype(np.float64), "presence_block_count": counts.astype(np.float32)}
+    for name, a in files.items():
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+    return {"dir": dirpath, "files": sorted(n_ + ".npy" for n_ in files), "queries": int(n), "sampled": int(len(idx)), "block_queries": int(blk),
+            "bytes": int(sum(a.nbytes for a in files.values()))}
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 def main():
     args = parse()
@@ -304,6 +344,10 @@ def main():
         ok_br = bool((bb[:nb8] == np.asarray(hbb)[:nb8]).all() and (bcounts == np.asarray(hcounts)).all())
         dist_extra = {"color_rows": ok_rows, "branching": ok_br, "queries": int(len(sample))}
 
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, gathered if use_dist else dbits, nq, world)
+
     if rank != 0:
         if use_dist:
             dist.destroy_process_group()
@@ -335,6 +379,7 @@ def main():
         },
         "parity_ok": parity_ok,
         "dist_extra_paths": dist_extra,
+        "dumped_outputs": dumped,
         "answers_checked_per_gpu": nq,
         "present_fraction": round(n_present / nq, 4),
         "build": {"insert_build_s_incl_torch": round(t_insert, 3), "M_pairs_per_s_incl_torch_packing": round(n_pairs_in / max(t_insert, 1e-9) / 1e6, 1),

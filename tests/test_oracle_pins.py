@@ -1,5 +1,6 @@
 """Pin the oracle against every known answer available for the path:
- - the reference's own xxhash.c / popcnt.c / log2.c compiled into oracle/_ref (when present),
+ - the reference's own xxhash.c / popcnt.c / log2.c: their answers stored in tests/golden/ref_prims.npz, and the sources
+   compiled into oracle/_ref (when present),
  - the published XXH64 test vector,
  - README.md:172 codec vector,
  - reference-run observations recorded in SURVEY.md / BASELINE.md (tests/golden/survey_pins.json).
@@ -14,6 +15,7 @@ import pytest
 from bloomfiltertrie_amd import synth as S
 
 PINS = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "survey_pins.json")))
+REF_PRIMS = os.path.join(os.path.dirname(__file__), "golden", "ref_prims.npz")
 
 
 def test_xxh64_published_vectors(oracle_mod):
@@ -36,10 +38,31 @@ def test_xxh64_published_vectors(oracle_mod):
 
 
 def test_primitives_against_reference_sources(oracle_mod):
+    """The oracle's primitives against the answers of the reference's own sources: the vectors stored in
+    tests/golden/ref_prims.npz (tests/golden/make_ref_prims.py) always, and the compiled sources in oracle/_ref where built."""
     O = oracle_mod
+    G = np.load(REF_PRIMS)
+    assert (G["xxh_seeds"] == np.array([0, 1, PINS["default_seeds"]["r1"], PINS["default_seeds"]["r2"], 2 ** 63 + 5], dtype=np.uint64)).all()
+    data, pos = G["xxh_data"], 0
+    for i, seed in enumerate(G["xxh_seeds"]):
+        for j, ln in enumerate(G["xxh_lengths"]):
+            d = data[pos:pos + ln].tobytes()
+            pos += int(ln)
+            assert O.xxh64(d, int(seed)) == int(G["xxh64"][i, j]), (int(seed), int(ln))
+    assert pos == len(data)
+    for i, nb in zip(G["nb_ids"], G["nb_bytes"]):
+        assert O.nb_bytes_id(int(i)) == int(nb), int(i)
+    for b in range(256):
+        assert G["rev"][b] == ((b & 3) << 6 | (b & 0xC) << 2 | (b & 0x30) >> 2 | (b & 0xC0) >> 6)
+        assert G["popcount8"][b] == bin(b).count("1")
     ref = O.ref_prims()
     if ref is None:
-        pytest.skip("oracle/_ref not built (no /root/reference on this box)")
+        return
+    pos = 0
+    for i, seed in enumerate(G["xxh_seeds"]):  # the stored vectors are the compiled sources' answers
+        for j, ln in enumerate(G["xxh_lengths"]):
+            assert ref.BFT_HASH_XXH64(data[pos:pos + ln].tobytes(), int(ln), int(seed)) == int(G["xxh64"][i, j])
+            pos += int(ln)
     rng = np.random.default_rng(7)
     for seed in (0, 1, PINS["default_seeds"]["r1"], PINS["default_seeds"]["r2"], 2 ** 63 + 5):
         for ln in (0, 1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 31, 32, 33, 63, 64, 65, 100, 257):
