@@ -306,6 +306,54 @@ class BFT:
         return out[:n.value].tobytes()
 
 
+    def _prefix_batch(self, prefixes, lengths):
+        """ASCII prefixes (lengths = their lengths) or packed rows [n, nb] with lengths (one per row, or one for all) -> (packed, lengths)."""
+        if lengths is None:
+            prefixes = list(prefixes)
+            lens = np.array([len(p) for p in prefixes], dtype=np.int64)
+            if ((lens < 1) | (lens > self.k)).any():
+                raise ValueError(f"prefix length outside [1, {self.k}] (reference prefix_matching exits, src/bft.c:1106-1107)")
+            packed, valid = ascii_to_packed([(p if isinstance(p, str) else p.decode()) + "A" * (self.k - len(p)) for p in prefixes], self.k)
+            if not valid.all():
+                raise ValueError("prefix with a character outside ACGTU (reference prefix_matching exits, src/bft.c:1125-1126)")
+            return packed, lens.astype(np.uint8)
+        packed = self._chk(prefixes)
+        lens = np.broadcast_to(np.asarray(lengths, dtype=np.int64), (len(packed),))
+        if ((lens < 1) | (lens > self.k)).any():
+            raise ValueError(f"prefix length outside [1, {self.k}]")
+        return packed, np.ascontiguousarray(lens, dtype=np.uint8)
+
+    def query_prefixes(self, prefixes, lengths=None):
+        """prefix_matching (include/bft.h:135, src/bft.c:1087-1147) for a batch: the stored k-mers that start with each prefix.
+        Returns (offsets [n + 1] uint64, kmers [m, nb] uint8, rows [m] uint32, colour sets [m] uint32); prefix i's matches are entries
+        offsets[i]:offsets[i + 1], in ascending row order (the order of extract())."""
+        packed, lens = self._prefix_batch(prefixes, lengths)
+        n = len(packed)
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        cap = max(1024, 4 * n)
+        while True:
+            kmers = np.zeros((cap, self.nb), dtype=np.uint8)
+            rows = np.zeros(cap, dtype=np.uint32)
+            sets = np.zeros(cap, dtype=np.uint32)
+            need = C.c_uint64()
+            rc = self._lib.bft_gpu_query_prefixes(self._h, packed.ctypes.data, lens.ctypes.data, n, offsets.ctypes.data, kmers.ctypes.data,
+                                                  rows.ctypes.data, sets.ctypes.data, cap, C.byref(need))
+            if rc == -6:  # BFT_GPU_E_NOSPACE
+                cap = int(need.value)
+                continue
+            _lib.check(rc)
+            m = int(need.value)
+            return offsets, kmers[:m], rows[:m], sets[:m]
+
+    def query_prefixes_dev(self, d_prefixes_ptr, d_lengths_ptr, n, d_offsets_ptr, d_kmers_ptr, d_rows_ptr, d_colorsets_ptr, cap, d_needed_ptr=0,
+                           stream=None):
+        """Device-resident prefix matching (bft_gpu_query_prefixes_dev): offsets (n + 1 uint64) always, the first `cap` matches into the
+        outputs that are not 0, the number of matches at d_needed_ptr; no synchronisation.  A length outside [1, k] matches nothing."""
+        _lib.check(self._lib.bft_gpu_query_prefixes_dev(self._h, C.c_void_p(d_prefixes_ptr), C.c_void_p(d_lengths_ptr), n, C.c_void_p(d_offsets_ptr),
+                                                        C.c_void_p(d_kmers_ptr or 0), C.c_void_p(d_rows_ptr or 0), C.c_void_p(d_colorsets_ptr or 0),
+                                                        cap, C.c_void_p(d_needed_ptr or 0), C.c_void_p(stream or 0)))
+
+
 class BFTGroup:
     """One built index replicated on several GPUs of this process; host batches are sharded over them (bft_gpu_group_*)."""
 

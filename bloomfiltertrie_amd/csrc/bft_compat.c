@@ -521,6 +521,60 @@ void iterate_over_kmers(BFT* bft, BFT_func_ptr f, ...) {
     va_end(args);
 }
 
+/* ---------------------------------------------------------------- pattern matching */
+
+/* src/bft.c:1087-1147.  The matches are one batch query (bft_gpu_query_prefixes): counted first, then fetched, and f is called on them in
+ * ascending row order -- the reference calls it in the DFS order of its containers. */
+bool prefix_matching(BFT* bft, char* prefix, BFT_func_ptr f, ...) {
+    NOT_NULL(bft, "prefix_matching()");
+    NOT_NULL(prefix, "prefix_matching()");
+    const int k = bft->k, nb = bytes_of(k);
+    const size_t len = strlen(prefix);
+    if (len > (size_t)k) DIE("prefix_matching(): Prefix length is larger than k-mer length.\n");
+    if (len == 0) DIE("prefix_matching(): Prefix length is 0.\n");
+    NOT_NULL(f, "prefix_matching()");
+    uint8_t* packed = calloc((size_t)nb, 1);
+    NOT_NULL(packed, "prefix_matching()");
+    if (!parseKmerCount(prefix, (int)len, packed, 0)) DIE("prefix_matching(): Non-ACGT char. encountered in prefix.\n");
+    const uint8_t length = (uint8_t)len;
+    uint64_t offsets[2] = {0, 0}, n = 0;
+    ck(bft_gpu_query_prefixes(bft->gpu, packed, &length, 1, offsets, NULL, NULL, NULL, 0, &n), "prefix_matching()");
+    if (n == 0) {
+        free(packed);
+        return false;
+    }
+    uint8_t* kmers = malloc((size_t)n * (size_t)nb);
+    uint32_t* rows = malloc((size_t)n * sizeof(uint32_t));
+    uint32_t* sets = malloc((size_t)n * sizeof(uint32_t));
+    if (kmers == NULL || rows == NULL || sets == NULL) DIE("prefix_matching(): out of memory\n");
+    ck(bft_gpu_query_prefixes(bft->gpu, packed, &length, 1, offsets, kmers, rows, sets, n, &n), "prefix_matching()");
+    BFT_kmer* km = create_empty_kmer();
+    km->kmer = malloc((size_t)k + 1);
+    km->kmer_comp = malloc((size_t)nb);
+    km->res = new_res(bft, 1, 0, 0);
+    if (km->kmer == NULL || km->kmer_comp == NULL) DIE("prefix_matching(): out of memory\n");
+    va_list args;
+    va_start(args, f);
+    for (uint64_t i = 0; i < n; i++) {
+        memcpy(km->kmer_comp, kmers + i * (size_t)nb, (size_t)nb);
+        unpack_kmer(km->kmer_comp, k, km->kmer);
+        km->res->row = rows[i];
+        km->res->colorset = sets[i];
+        va_list copy; /* a fresh copy per call, as v_iterate_over_kmers */
+        va_copy(copy, args);
+        const size_t go_on = f(km, bft, copy);
+        va_end(copy);
+        if (go_on == 0) break;
+    }
+    va_end(args);
+    free_BFT_kmer(km, 1);
+    free(kmers);
+    free(rows);
+    free(sets);
+    free(packed);
+    return true;
+}
+
 size_t write_kmer_ascii_to_disk(BFT_kmer* bft_kmer, BFT* bft, va_list args) { /* src/bft.c:299-308 */
     FILE* file = va_arg(args, FILE*);
     bft_kmer->kmer[bft->k] = '\n';

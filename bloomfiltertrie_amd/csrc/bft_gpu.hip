@@ -31,6 +31,7 @@
 #include "bft_image.h"
 #include "bft_index.h"
 #include "bft_kh.h"
+#include "bft_prefix.h"
 #include "bft_scan.h"
 #include "bft_sort.h"
 #include "bft_walk.h"
@@ -387,6 +388,11 @@ struct bft_gpu {
     hipStream_t qc_stream = nullptr;
     hipEvent_t qc_ev = nullptr;  // where the last use of the scratch ends (the stream it ran on is the caller's: it may be gone by the next call)
     bool qc_used = false;  // bound on the blocks of k-mer positions the sequence kernel deals out (claim_counters)
+    DevBuf pm_buf, pm_tmp;         // scratch of the prefix queries (BftPmScratch, bft_prefix.h) and their scans' temporary (grown, never shrunk)
+    uint64_t pm_n = 0;             // prefixes pm_buf has room for
+    hipStream_t pm_stream = nullptr;
+    hipEvent_t pm_ev = nullptr;    // where the last use of that scratch ends
+    bool pm_used = false;
     bool inject_build_failure = false;  // test hook: the next bft_gpu_build fails right before its commit point (one shot)
     bool opt_build_stages = false;      // "build_stages": the next builds record GPU time and bytes per stage (bft_gpu_build_stages)
     struct Stage { std::string name; double ms, bytes; };
@@ -537,6 +543,7 @@ extern "C" void bft_gpu_free(bft_gpu* h) {
     for (auto& e : h->ext) (void)hipEventDestroy(e.ev);
     h->ext.clear();
     if (h->qc_ev) { (void)hipEventDestroy(h->qc_ev); h->qc_ev = nullptr; }
+    if (h->pm_ev) { (void)hipEventDestroy(h->pm_ev); h->pm_ev = nullptr; }
     const hipStream_t s = h->stream;
     if (s) (void)hipStreamSynchronize(s);
     if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); h->stream2 = nullptr; }
@@ -3304,6 +3311,152 @@ extern "C" int bft_gpu_query_rows(bft_gpu* h, const uint8_t* kmers, uint64_t n, 
         }
         HIPCK(hipStreamSynchronize(h->stream));
     }
+    return BFT_GPU_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// prefix matching (prefix_matching, include/bft.h:135, src/bft.c:1087-1147): the kernels of bft_prefix.hip over the sorted table
+// ------------------------------------------------------------------------------------------------
+static bool stream_capturing(hipStream_t s) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return st != hipStreamCaptureStatusNone;
+}
+template <class F>
+static int timed_launch(bft_gpu* h, hipStream_t s, F&& launch) {
+    hipEvent_t e0, e1;
+    CK(timing_begin(h, s, &e0, &e1));
+    CK(launch());
+    return timing_end(h, s, e0, e1);
+}
+static uint64_t pm_bytes(uint64_t m) {
+    auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
+    return 2 * al(m * 4) + 2 * al(m * 8) + al((m + 1) * 8) + al(BFT_PM_CHUNKS * 8ull) + al((BFT_PM_CHUNKS + 1) * 8ull);
+}
+// The handle's scratch for a batch of n prefixes on stream s.  It belongs to the handle, not to a stream: a call on another stream first waits for
+// the last use (an event of the handle's own); nothing is allocated or waited for while s is being captured.
+static int pm_scratch(bft_gpu* h, uint64_t n, hipStream_t s, bool capturing, BftPmScratch* p) {
+    if (h->pm_used && h->pm_stream != s) {
+        if (capturing) return fail(BFT_GPU_E_ARG, "prefix query recorded into a graph: the handle's prefix scratch is in use on another stream");
+        HIPCK(h->pm_ev ? hipEventSynchronize(h->pm_ev) : hipDeviceSynchronize());
+        h->pm_used = false;
+    }
+    const size_t tb = bft_scan::scratch_bytes(std::max<uint64_t>(n, BFT_PM_CHUNKS) + 1);
+    if (h->pm_n < n || h->pm_tmp.bytes < tb) {
+        if (capturing) return fail(BFT_GPU_E_ARG, "prefix query recorded into a graph: make one direct call of this size first (nothing may allocate in a capture)");
+        if (h->pm_used) HIPCK(hipStreamSynchronize(s));
+        if (h->pm_n < n) {
+            const uint64_t m = n + n / 2;
+            CK(h->pm_buf.alloc(pm_bytes(m)));
+            h->pm_n = m;
+        }
+        if (h->pm_tmp.bytes < tb) CK(h->pm_tmp.alloc(tb + tb / 2));
+    }
+    const uint64_t m = h->pm_n;
+    auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
+    uint8_t* q = h->pm_buf.as<uint8_t>();
+    p->a = (uint32_t*)q; q += al(m * 4);
+    p->filt = (uint32_t*)q; q += al(m * 4);
+    p->cand = (uint64_t*)q; q += al(m * 8);
+    p->kept = (uint64_t*)q; q += al(m * 8);
+    p->coff = (uint64_t*)q; q += al((m + 1) * 8);
+    p->chunk = (uint64_t*)q; q += al(BFT_PM_CHUNKS * 8ull);
+    p->chunk_off = (uint64_t*)q;
+    h->pm_used = true;
+    h->pm_stream = s;
+    return 0;
+}
+static void pm_release(bft_gpu* h, hipStream_t s) {
+    if (!h->pm_ev && hipEventCreateWithFlags(&h->pm_ev, hipEventDisableTiming) != hipSuccess) { h->pm_ev = nullptr; (void)hipGetLastError(); }
+    if (h->pm_ev && hipEventRecord(h->pm_ev, s) != hipSuccess) (void)hipGetLastError();
+}
+// intervals, candidate offsets, matches per prefix -> d_offsets (n + 1; d_offsets[n] = total, also written to d_needed when it is not NULL) and
+// the chunk offsets the emit reads; every launch is timed ("timing")
+static int pm_count(bft_gpu* h, const uint8_t* d_pref, const uint8_t* d_len, uint64_t n, uint64_t* d_offsets, uint64_t* d_needed, hipStream_t s,
+                    const BftPmScratch& p) {
+    const uint64_t* tk = h->d_tk.as<uint64_t>();
+    CK(timed_launch(h, s, [&] { return bft_pm_bounds(h->W, d_pref, d_len, n, h->k, h->B, tk, h->n_kmers, p, s); }));
+    CK(timed_launch(h, s, [&] { return bft_scan::exclusive_sum_ptr<uint64_t>(p.cand, p.coff, n, s, h->pm_tmp, nullptr, true); }));
+    CK(timed_launch(h, s, [&] { return bft_pm_count(h->W, n, tk, p, s); }));
+    CK(timed_launch(h, s, [&] { return bft_scan::exclusive_sum_ptr<uint64_t>(p.kept, d_offsets, n, s, h->pm_tmp, (unsigned long long*)d_needed, true); }));
+    CK(timed_launch(h, s, [&] { return bft_scan::exclusive_sum_ptr<uint64_t>(p.chunk, p.chunk_off, BFT_PM_CHUNKS, s, h->pm_tmp, nullptr, true); }));
+    return 0;
+}
+static int pm_emit(bft_gpu* h, uint64_t n, const BftPmScratch& p, uint64_t cap, uint8_t* d_kmers, uint32_t* d_rows, uint32_t* d_cs, hipStream_t s) {
+    if (cap == 0 || (!d_kmers && !d_rows && !d_cs)) return 0;
+    return timed_launch(h, s, [&] { return bft_pm_emit(h->W, n, h->k, h->B, h->d_tk.as<uint64_t>(), h->d_tcol.as<uint32_t>(), p, cap, d_kmers, d_rows, d_cs, s); });
+}
+
+extern "C" int bft_gpu_query_prefixes_dev(bft_gpu* h, const void* d_prefixes, const void* d_lengths, uint64_t n, void* d_offsets, void* d_kmers_out,
+                                          void* d_rows_out, void* d_colorsets_out, uint64_t cap, void* d_needed, void* hip_stream) {
+    if (!h || !d_offsets || ((!d_prefixes || !d_lengths) && n)) return fail(BFT_GPU_E_ARG, "NULL argument");
+    ENTER(h);
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
+    const bool capturing = stream_capturing(s);
+    CK(ensure_built(h, false));
+    if (h->table_dropped) {  // ("compact_table": the rows come from the sorted table; bringing it back synchronises)
+        if (capturing) return fail(BFT_GPU_E_ARG, "prefix query recorded into a graph: the sorted table is not resident (compact_table); make one direct call first");
+        CK(ensure_table(h));
+    }
+    if (n == 0) {
+        CK(bft_zero_async(d_offsets, 8, s));  // (kernels, not memsets, wherever a caller may be capturing: bft_dev.h)
+        if (d_needed) CK(bft_zero_async(d_needed, 8, s));
+        return note_foreign_stream(h, s);
+    }
+    BftPmScratch p;
+    CK(pm_scratch(h, n, s, capturing, &p));
+    CK(pm_count(h, (const uint8_t*)d_prefixes, (const uint8_t*)d_lengths, n, (uint64_t*)d_offsets, (uint64_t*)d_needed, s, p));
+    CK(pm_emit(h, n, p, cap, (uint8_t*)d_kmers_out, (uint32_t*)d_rows_out, (uint32_t*)d_colorsets_out, s));
+    pm_release(h, s);
+    return note_foreign_stream(h, s);
+}
+
+// The host-buffer form: lengths are checked first, the matches counted on the device, and the outputs filled only when cap holds them all.
+extern "C" int bft_gpu_query_prefixes(bft_gpu* h, const uint8_t* prefixes, const uint8_t* lengths, uint64_t n, uint64_t* offsets, uint8_t* kmers_out,
+                                      uint32_t* rows_out, uint32_t* colorsets_out, uint64_t cap, uint64_t* needed) {
+    if (!h || !offsets || ((!prefixes || !lengths) && n)) return fail(BFT_GPU_E_ARG, "NULL argument");
+    for (uint64_t i = 0; i < n; i++)
+        if (lengths[i] < 1 || lengths[i] > h->k) return fail(BFT_GPU_E_ARG, "prefix length outside [1, k]");
+    ENTER(h);
+    CK(ensure_built(h));
+    if (n == 0) {
+        offsets[0] = 0;
+        if (needed) *needed = 0;
+        return BFT_GPU_OK;
+    }
+    const hipStream_t s = h->stream;
+    DevBuf dp, dl, doff, dneed;
+    CK(dp.alloc(n * h->B));
+    CK(dl.alloc(n));
+    CK(doff.alloc((n + 1) * 8));
+    CK(dneed.alloc(8));
+    HIPCK(hipMemcpyAsync(dp.p, prefixes, n * h->B, hipMemcpyHostToDevice, s));
+    HIPCK(hipMemcpyAsync(dl.p, lengths, n, hipMemcpyHostToDevice, s));
+    BftPmScratch p;
+    CK(pm_scratch(h, n, s, false, &p));
+    CK(pm_count(h, dp.as<uint8_t>(), dl.as<uint8_t>(), n, doff.as<uint64_t>(), dneed.as<uint64_t>(), s, p));
+    uint64_t total = 0;
+    HIPCK(hipMemcpyAsync(&total, dneed.p, 8, hipMemcpyDeviceToHost, s));
+    HIPCK(hipStreamSynchronize(s));
+    if (needed) *needed = total;
+    const bool want = kmers_out || rows_out || colorsets_out;
+    if (want && total > cap) {
+        pm_release(h, s);
+        return fail(BFT_GPU_E_NOSPACE, "prefix match buffers too small");
+    }
+    if (want && total) {
+        DevBuf dk, dr, dc;
+        if (kmers_out) CK(dk.alloc(total * h->B));
+        if (rows_out) CK(dr.alloc(total * 4));
+        if (colorsets_out) CK(dc.alloc(total * 4));
+        CK(pm_emit(h, n, p, total, dk.as<uint8_t>(), dr.as<uint32_t>(), dc.as<uint32_t>(), s));
+        if (kmers_out) HIPCK(hipMemcpyAsync(kmers_out, dk.p, total * h->B, hipMemcpyDeviceToHost, s));
+        if (rows_out) HIPCK(hipMemcpyAsync(rows_out, dr.p, total * 4, hipMemcpyDeviceToHost, s));
+        if (colorsets_out) HIPCK(hipMemcpyAsync(colorsets_out, dc.p, total * 4, hipMemcpyDeviceToHost, s));
+    }
+    HIPCK(hipMemcpyAsync(offsets, doff.p, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIPCK(hipStreamSynchronize(s));
+    pm_release(h, s);
     return BFT_GPU_OK;
 }
 

@@ -491,6 +491,29 @@ extern "C" void bft_hosttest_flatten(void* hv, uint32_t flat_min) {
     t->im.ccx = t->idx.ccx.data(); t->im.f18 = t->idx.f18.data(); t->im.fent = t->idx.fent.data();
 }
 
+// the range rule of prefix matching (bft_prefix_range, shared with the k_pm_* kernels) for n packed prefixes of lens[i] nucleotides:
+// lo / hi (W words each, most significant first), the filter's bit offset (-1: none) and value; returns how many lengths were in [1, k]
+extern "C" uint64_t bft_hosttest_prefix_range(const uint8_t* prefixes, const uint8_t* lens, uint64_t n, int k, uint64_t* lo, uint64_t* hi, int32_t* fsh,
+                                              uint32_t* fval) {
+    const int W = bft_words_for_k(k), B = bft_bytes_for_k(k);
+    uint64_t ok = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        uint64_t x[BFT_MAX_W] = {0};
+        for (int b = 0; b < B; b++) x[b >> 3] |= (uint64_t)prefixes[i * B + b] << (8 * (b & 7));
+        int sh = -1;
+        bool r;
+        switch (W) {
+        case 1: r = bft_prefix_range<1>(x, k, lens[i], lo + i * W, hi + i * W, &sh, fval + i); break;
+        case 2: r = bft_prefix_range<2>(x, k, lens[i], lo + i * W, hi + i * W, &sh, fval + i); break;
+        case 3: r = bft_prefix_range<3>(x, k, lens[i], lo + i * W, hi + i * W, &sh, fval + i); break;
+        default: r = bft_prefix_range<4>(x, k, lens[i], lo + i * W, hi + i * W, &sh, fval + i); break;
+        }
+        fsh[i] = sh;
+        ok += r ? 1 : 0;
+    }
+    return ok;
+}
+
 extern "C" void bft_hosttest_hashmod(int r1, int r2, uint32_t* out) { bft_make_hashmod(r1, r2, out); }
 extern "C" void bft_hosttest_free(void* hv) { delete (HostTrie*)hv; }
 

@@ -208,6 +208,61 @@ BFT_HD uint32_t bft_rows_lower_bound(const uint64_t* rows, uint32_t n, const uin
     }
     return lo;
 }
+// upper bound: the first of n sorted rows greater than t, in [0, n]
+template <int W>
+BFT_HD uint32_t bft_rows_upper_bound(const uint64_t* rows, uint32_t n, const uint64_t* t) {
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        uint32_t mid = (lo + hi) >> 1;
+        uint64_t r[W];
+        bft_load_row<W>(rows + (size_t)mid * W, r);
+        if (bft_cmp<W>(r, t) <= 0) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// Prefix matching (prefix_matching, reference src/bft.c:1087-1147) as a range of the sorted T-form table.  A prefix of len nucleotides
+// (1 <= len <= k) in the packed layout x (nucleotides from len on are ignored, whatever they hold) matches the rows t with lo <= t <= hi
+// whose 2-bit field `fval` sits at bit `fsh` of the T-form (counted from its least significant bit), or every row of [lo, hi] when
+// fsh < 0.  With f = len / 9 whole blocks and m = len - 9 f:
+//   m = 0           the top 18 f bits are the prefix: one interval;
+//   m > 0, f < L    block f (n2..n9,n1) holds n2..nm in its top 2 (m - 1) bits and n1 in its low 2 bits: the interval over the top
+//                   18 f + 2 (m - 1) bits, filtered on those 2 low bits (m = 1 keeps about a quarter of it);
+//   m > 0, f = L    the prefix reaches into the R = k % 9 remaining nucleotides (first one most significant): one interval over the
+//                   top 18 L + 2 m bits.
+// Returns false, and no row matches, when len is outside [1, k].  lo / hi: W words, word 0 most significant, like the table's rows.
+template <int W>
+BFT_HD bool bft_prefix_range(const uint64_t* x, int k, int len, uint64_t* lo, uint64_t* hi, int* fsh, uint32_t* fval) {
+    *fsh = -1;
+    *fval = 0;
+    if (len < 1 || len > k) return false;
+    uint64_t xm[W], t[W];
+#pragma unroll
+    for (int w = 0; w < W; w++) {  // nucleotide j at bits 2j: keep the first len of them
+        const int keep = 2 * len - 64 * w;
+        xm[w] = keep >= 64 ? x[w] : keep <= 0 ? 0ull : x[w] & ((1ull << keep) - 1ull);
+    }
+    bft_tform_from_x<W>(xm, k, t);
+    const int L = k / 9, f = len / 9, m = len - 9 * f;
+    int fixed;
+    if (m == 0) fixed = 18 * f;
+    else if (f < L) {
+        fixed = 18 * f + 2 * (m - 1);
+        *fsh = 2 * (k - 9 * L) + 18 * (L - 1 - f);
+        *fval = bft_get18_le<W>(xm, 18 * f) & 3u;  // nucleotide 9 f: the block's n1
+    } else
+        fixed = 18 * L + 2 * m;
+    const int free_bits = 2 * k - fixed;
+#pragma unroll
+    for (int w = 0; w < W; w++) {  // word w holds bits [64 (W - 1 - w), 64 (W - w)) of the T-form
+        const int nb = free_bits - 64 * (W - 1 - w);
+        const uint64_t mask = nb >= 64 ? ~0ull : nb <= 0 ? 0ull : (1ull << nb) - 1ull;
+        lo[w] = t[w] & ~mask;
+        hi[w] = lo[w] | mask;
+    }
+    return true;
+}
 
 // Exact search of t among the n sorted rows of a suffix group, starting from an interpolated guess g
 // (suffix values are close to uniform inside a group, so the guess is a few rows off): probe, gallop

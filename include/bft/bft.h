@@ -17,7 +17,7 @@
  *     bft_gpu.h on bft_device_index(bft) -- that is the point of the GPU path;
  *   - insertions are collected on the GPU and the containers are rebuilt in bulk by the first query after them;
  *   - there is no CPU fallback: without a usable GPU every function reports the error and exits.
- * Not provided (outside the path): marking / flags, annotation set operations, prefix_matching,
+ * Not provided (outside the path): marking / flags, annotation set operations, prefix_matching_custom,
  * create_cdbg_from_bft_kmers, add_id_genomes, colour compression (write_BFT ignores compress_annotations and writes
  * uncompressed annotations, which the reference loads).
  */
@@ -155,6 +155,13 @@ BFT_kmer* get_successors(BFT_kmer* bft_kmer, BFT* bft);
  * the index's (ascending in its internal key), not the reference's container order. ---- */
 void iterate_over_kmers(BFT* bft, BFT_func_ptr f, ...);
 void v_iterate_over_kmers(BFT* bft, BFT_func_ptr f, va_list args);
+
+/* ---- pattern matching (include/bft.h:135, src/bft.c:1087-1147).  f is called on every stored k-mer whose first strlen(prefix)
+ * nucleotides are the prefix (1 <= strlen(prefix) <= k, ACGTU in either case; anything else prints a message and exits), with kmer, kmer_comp
+ * and res (row and colour set: get_annotation works on it) filled; returning 0 stops the iteration.  Returns true iff at least one k-mer
+ * matched.  The same set of k-mers as the reference; the order is the index's (ascending in its internal key), as for iterate_over_kmers,
+ * not the reference's container order. ---- */
+bool prefix_matching(BFT* bft, char* prefix, BFT_func_ptr f, ...);
 
 /* ---- disk (include/bft.h:175-176, src/bft.c:1090-1110, src/write_to_disk.c) ---- */
 void write_BFT(BFT* bft, char* filename, bool compress_annotations);

@@ -261,6 +261,29 @@ int bft_gpu_colorset(bft_gpu* h, uint32_t colorset, uint32_t* ids, uint32_t cap,
 int bft_gpu_query_rows(bft_gpu* h, const uint8_t* kmers, uint64_t nb_kmers, uint8_t* present_bits, uint32_t* rows,
                        uint32_t* colorsets);
 
+/* prefix_matching(bft, prefix, f, ...) (include/bft.h:135, src/bft.c:1087-1147; the reference's walk: src/presenceNode.c:1923-2448) for a
+ * batch: prefix i is the first lengths[i] nucleotides (1 <= lengths[i] <= k) of the packed k-mer prefixes[i] (B = CEIL(2k/8) bytes, the layout
+ * of every batch here; nucleotides from lengths[i] on are ignored, whatever they hold).  Its matches -- the stored k-mers whose first
+ * lengths[i] nucleotides are the prefix's -- are entries offsets[i] .. offsets[i + 1] of the outputs, in ascending row order (the order of
+ * bft_gpu_extract; the reference calls f in the DFS order of its containers instead): the packed k-mer (kmers_out, B bytes each), its row
+ * in the stored k-mer table (rows_out, what bft_gpu_query_rows reports) and its colour-set id (colorsets_out, argument of bft_gpu_colorset /
+ * bft_gpu_colorset_annot); any output may be NULL.  offsets: nb_prefixes + 1 entries; *needed (may be NULL) = offsets[nb_prefixes], the
+ * number of matches.  When an output is given and cap (entries) is below the number of matches, nothing is written -- offsets neither --,
+ * *needed is set and BFT_GPU_E_NOSPACE is returned; with every output NULL the call only counts.  A length outside [1, k] is BFT_GPU_E_ARG,
+ * before any GPU work.  The matches are a range of the sorted k-mer table: under "compact_table" the table comes back first (as for
+ * bft_gpu_query_rows and bft_gpu_extract) and stays until the next build.  Host buffers. */
+int bft_gpu_query_prefixes(bft_gpu* h, const uint8_t* prefixes, const uint8_t* lengths, uint64_t nb_prefixes, uint64_t* offsets, uint8_t* kmers_out,
+                           uint32_t* rows_out, uint32_t* colorsets_out, uint64_t cap, uint64_t* needed);
+/* The same on a RESIDENT batch, without synchronisation (runs on hip_stream; NULL = the handle's stream), the capacity rule of
+ * bft_gpu_query_colors_dev: d_offsets (nb_prefixes + 1 uint64) is always written in full, the outputs (device, any may be NULL) receive the
+ * first cap matches only (never an entry beyond cap), *d_needed (device, may be NULL) the number of matches -- pass NULL outputs and cap 0
+ * first to learn the size.  A length outside [1, k] gives that prefix no match (checking it would cost a host synchronisation).  Scratch
+ * (~40 bytes per prefix) belongs to the handle: calls on different streams are serialised by the library.  Recorded into a HIP graph (its
+ * stream is being captured), the call needs the sorted table resident and its scratch sized by a direct call of the same size before --
+ * else it returns BFT_GPU_E_ARG: nothing synchronises or allocates inside a capture. */
+int bft_gpu_query_prefixes_dev(bft_gpu* h, const void* d_prefixes, const void* d_lengths, uint64_t nb_prefixes, void* d_offsets, void* d_kmers_out,
+                               void* d_rows_out, void* d_colorsets_out, uint64_t cap, void* d_needed, void* hip_stream);
+
 /* A colour set as the reference's annotation bytes -- BFT_annotation::annot as get_annotation returns it
  * (include/bft.h:97, src/bft.c:363-387): mode 0 (bitmap, genome g <-> bit g+2), 1 (ranges) or 2 (id list), chosen the way the
  * reference chooses it: compute_best_mode re-decides at every insertion of a genome id and keeps the current mode on a size tie
