@@ -353,6 +353,29 @@ class BFT:
                                                         C.c_void_p(d_kmers_ptr or 0), C.c_void_p(d_rows_ptr or 0), C.c_void_p(d_colorsets_ptr or 0),
                                                         cap, C.c_void_p(d_needed_ptr or 0), C.c_void_p(stream or 0)))
 
+    def subgraph(self, kmers, colors=True):
+        """create_cdbg_from_bft_kmers (include/bft.h:179, src/bft.c:1353-1464) on the GPU: a new BFT holding those of the packed k-mers this index
+        stores, with their colour sets (colors) or all in one genome named after genome 0.  Duplicates collapse.  Returns (BFT, n_absent)."""
+        kmers = self._chk(kmers)
+        h = C.c_void_p()
+        absent = C.c_uint64()
+        _lib.check(self._lib.bft_gpu_subgraph(self._h, kmers.ctypes.data, len(kmers), 1 if colors else 0, C.byref(absent), C.byref(h)))
+        return BFT(self.k, device=self.device, _handle=h), int(absent.value)
+
+    def subgraph_dev(self, d_kmers_ptr, n, colors=True, stream=None):
+        """The same on a device-resident batch (bft_gpu_subgraph_dev): d_kmers is read in order on `stream`.  Returns (BFT, n_absent)."""
+        h = C.c_void_p()
+        absent = C.c_uint64()
+        _lib.check(self._lib.bft_gpu_subgraph_dev(self._h, C.c_void_p(d_kmers_ptr or 0), n, 1 if colors else 0, C.byref(absent), C.byref(h),
+                                                  C.c_void_p(stream or 0)))
+        return BFT(self.k, device=self.device, _handle=h), int(absent.value)
+
+    def genome_name(self, id_genome):
+        """The name of genome id_genome (the reference's filenames[id_genome]; "genome_<id>" for an id that was never named)."""
+        buf = C.create_string_buffer(4096)
+        _lib.check(self._lib.bft_gpu_genome_name(self._h, int(id_genome), buf, len(buf)))
+        return buf.value.decode()
+
 
 class BFTGroup:
     """One built index replicated on several GPUs of this process; host batches are sharded over them (bft_gpu_group_*)."""

@@ -575,6 +575,81 @@ bool prefix_matching(BFT* bft, char* prefix, BFT_func_ptr f, ...) {
     return true;
 }
 
+/* ---------------------------------------------------------------- sub-graphs */
+
+/* src/bft.c:1353-1464.  add_colors: one call of bft_gpu_subgraph -- the k-mers of the source with their colour sets, built on the GPU from the
+ * source's sorted table and dictionary instead of genome-id insertions one k-mer at a time; k-mers the source does not store are skipped (the
+ * reference's behaviour there is undefined: it reads the annotation of a k-mer that has none).  Otherwise, as the reference: every given k-mer
+ * goes into one new genome named bft->filenames[0], stored in the source or not. */
+BFT* create_cdbg_from_bft_kmers(BFT_kmer** bft_kmers, uint32_t nb_bft_kmers, BFT* bft, bool add_colors) {
+    NOT_NULL(bft, "create_sub_cdbg()");
+    NOT_NULL(bft_kmers, "create_sub_cdbg()");
+    const int k = bft->k, nb = bytes_of(k);
+    if (!add_colors) {
+        if (bft->nb_genomes <= 0) DIE("create_sub_cdbg(): the graph has no genome to name the new one after.\n");
+        char** kmers = malloc((size_t)(nb_bft_kmers ? nb_bft_kmers : 1) * sizeof(char*));
+        NOT_NULL(kmers, "create_sub_cdbg()");
+        for (uint32_t i = 0; i < nb_bft_kmers; i++) {
+            NOT_NULL(bft_kmers[i], "create_sub_cdbg()");
+            kmers[i] = bft_kmers[i]->kmer;
+        }
+        BFT* sub = create_cdbg(k, bft->treshold_compression);
+        insert_kmers_new_genome((int)nb_bft_kmers, kmers, bft->filenames[0], sub);
+        free(kmers);
+        return sub;
+    }
+    uint8_t* batch = malloc((size_t)(nb_bft_kmers ? nb_bft_kmers : 1) * (size_t)nb);
+    NOT_NULL(batch, "create_sub_cdbg()");
+    for (uint32_t i = 0; i < nb_bft_kmers; i++) {
+        NOT_NULL(bft_kmers[i], "create_sub_cdbg()");
+        NOT_NULL(bft_kmers[i]->kmer, "create_sub_cdbg()");
+        if (strlen(bft_kmers[i]->kmer) < (size_t)k || !pack_kmer(bft_kmers[i]->kmer, k, batch + (size_t)i * nb))
+            DIE("create_sub_cdbg(): Unexpected character encountered in k-mer.\n");
+    }
+    bft_gpu* g = NULL;
+    ck(bft_gpu_subgraph(bft->gpu, batch, nb_bft_kmers, 1, NULL, &g), "create_sub_cdbg()");
+    free(batch);
+    BFT* sub = new_root(k, bft->treshold_compression, g);
+    for (int i = 0; i < bft->nb_genomes; i++) push_name(sub, bft->filenames[i]); /* add_genomes_BFT_Root(bft->nb_genomes, bft->filenames, sub) */
+    return sub;
+}
+
+static int cmp_u32(const void* a, const void* b) {
+    const uint32_t x = *(const uint32_t*)a, y = *(const uint32_t*)b;
+    return x < y ? -1 : (x > y);
+}
+
+/* src/bft.c:1466-1684: list_id_genomes[0] ids follow in list_id_genomes[1..]; they are sorted in place, as the reference does, and every one
+ * must name an inserted genome.  The (k-mer, id) pairs are inserted; bft_kmer->res is looked up again, so that get_annotation(bft_kmer)
+ * answers the widened set.  bft_annot is not needed here (the reference reads the current set out of it). */
+void add_id_genomes(BFT_kmer* bft_kmer, BFT_annotation* bft_annot, BFT* bft, uint32_t* list_id_genomes) {
+    (void)bft_annot;
+    NOT_NULL(bft_kmer, "add_id_genomes()");
+    NOT_NULL(bft, "add_id_genomes()");
+    NOT_NULL(list_id_genomes, "add_id_genomes()");
+    if (list_id_genomes[0] == 0) return;
+    NOT_NULL(bft_kmer->kmer, "add_id_genomes()");
+    qsort(&list_id_genomes[1], list_id_genomes[0], sizeof(uint32_t), cmp_u32);
+    for (uint32_t j = list_id_genomes[0]; j >= 1; j--)
+        if (bft->nb_genomes <= 0 || list_id_genomes[j] > (uint32_t)bft->nb_genomes - 1)
+            DIE("add_id_genomes(): An attempt to update a k-mer with a genome id that has not been inserted in the BFT yet has been made.\n");
+    const int nb = bytes_of(bft->k);
+    uint8_t* packed = malloc((size_t)nb);
+    NOT_NULL(packed, "add_id_genomes()");
+    if (strlen(bft_kmer->kmer) < (size_t)bft->k || !pack_kmer(bft_kmer->kmer, bft->k, packed))
+        DIE("add_id_genomes(): Unexpected character encountered in k-mer.\n");
+    for (uint32_t j = 1; j <= list_id_genomes[0]; j++)
+        if (j == 1 || list_id_genomes[j] != list_id_genomes[j - 1]) ck(bft_gpu_insert_kmers(bft->gpu, packed, 1, list_id_genomes[j]), "add_id_genomes()");
+    BFT_kmer fresh;
+    locate(bft, packed, 1, &fresh, "add_id_genomes()");
+    if (bft_kmer->res != NULL) {
+        *bft_kmer->res = *fresh.res;
+        free(fresh.res);
+    } else
+        bft_kmer->res = fresh.res;
+    free(packed);
+}
+
 size_t write_kmer_ascii_to_disk(BFT_kmer* bft_kmer, BFT* bft, va_list args) { /* src/bft.c:299-308 */
     FILE* file = va_arg(args, FILE*);
     bft_kmer->kmer[bft->k] = '\n';

@@ -34,6 +34,7 @@
 #include "bft_prefix.h"
 #include "bft_scan.h"
 #include "bft_sort.h"
+#include "bft_subgraph.h"
 #include "bft_walk.h"
 
 #define BFT_BLOCK 256
@@ -1458,6 +1459,160 @@ struct StageScope {
     }
 };
 
+// Steps 5-7 of a build, from the point where the sorted table tk (nk rows), the colour set per row n_tcol and the dictionary n_cs_off / n_cs_ids
+// (32-bit ids) are final: containers, flat forms, k-mer hash (on the second stream), narrowing, commit into h, root tables.  Shared by
+// bft_gpu_build and bft_gpu_subgraph.  khf: the k-mer hash fill (prepared or not); tail / seg_off / npg: the interning's deferred tail and
+// its input (a default tail -- nothing pending -- where there was no interning); t0 / t1: start and end of the sort (bft_gpu_build_time).
+static int commit_image(bft_gpu* h, DevBuf& tk, DevBuf& n_tcol, DevBuf& n_cs_off, DevBuf& n_cs_ids, uint64_t nk, uint64_t n_sets, uint64_t n_ids, uint64_t np,
+                        KhFill& khf, BftInternTail& tail, DevBuf& seg_off, DevBuf& npg, double t0, double t1) {
+    const int W = h->W;
+    struct KhStart {  // (from here on tk, n_tcol and the number of colour sets are final)
+        bft_gpu* h; const uint64_t* tk; const uint32_t* tcol; uint64_t nk, n_sets; KhFill* f;
+        static void run(void* c, hipStream_t s) { KhStart* k = (KhStart*)c; kh_start(k->h, k->tk, k->tcol, k->nk, k->n_sets, *k->f, s, nullptr); }
+    } khs{h, tk.as<uint64_t>(), n_tcol.as<uint32_t>(), nk, n_sets, &khf};
+    // (started HERE instead -- beside the root's table passes -- the sort-based table build was measured too: 17.2-18.4 ms against 17.0)
+    // (and earlier still -- behind the root's prefix scans, or before them: 15.7 ms each way, round 5: the build is bound by the device's total work,
+    // not by either stream's chain)
+    const BftAssembleHook hook{tk.p ? &KhStart::run : nullptr, &khs};
+    const double t2 = now_ms();
+
+    // 5. containers, level by level, on the GPU
+    if (!tk.p) CK(tk.alloc(8));
+    BftDeviceIndex idx;
+    CK(bft_assemble_gpu(tk.as<uint64_t>(), nk, h->k, h->d_hashmod.as<uint32_t>(), h->stream, idx, &hook));
+    bft_trace_mark("containers assembled");
+    bft_stage("containers: concatenation", 0, h->stream);
+    double t3 = now_ms();
+    DevBuf n_ccx, n_f18buf, n_fentbuf;
+    uint64_t n_f18 = 0, n_fent = 0;
+    CK(bft_flatten_gpu(idx.ccs.as<BftCC>(), idx.n_ccs, idx.f2w.as<uint64_t>(), idx.clus.as<uint64_t>(), idx.child.as<uint64_t>(), h->opt_flat_min, h->stream,
+                       n_ccx, n_f18buf, n_fentbuf, n_f18, n_fent));
+    bft_trace_mark("flat forms");
+    bft_stage("flat forms of the big CCs", (double)(n_f18 + n_fent) * 8, h->stream);
+    bool kh_redo = false;
+    {   // the interning's deferred tail: done long ago; two lists with one signature (never seen outside the test hook) -> the exact interning
+        uint32_t collisions = 0;
+        CK(tail.wait(&collisions));
+        if (collisions) {
+            double ms_ = 0;
+            (void)kh_finish(h, khf, &ms_);  // (the table under construction holds the wrong colour sets, and reads the arrays replaced below)
+            khf.buf.release();
+            kh_redo = true;
+            CK(bft_intern_colors_gpu(seg_off.as<uint32_t>(), npg.as<uint32_t>(), nk, np, h->stream, n_tcol, n_cs_off, n_cs_ids, n_sets, n_ids, 0, nullptr, true));
+        }
+        seg_off.release();
+        npg.release();
+    }
+    const uint32_t new_cs_w = id_width(h->max_gid_seen);
+    DevBuf n_cs_ids_w;
+    bool narrowed_here = false;
+    if (!kh_redo && tail.narrow.p && tail.narrow_w == new_cs_w) {  // (done by the interning's tail on the side stream)
+        n_cs_ids_w.swap(tail.narrow);
+        n_cs_ids.release();
+    } else {
+        CK(narrow_ids(n_cs_ids, n_ids, new_cs_w, h->stream, n_cs_ids_w));
+        narrowed_here = new_cs_w < 4;
+    }
+    CK(wait_foreign_stream(h));  // queries a caller still has in flight on its own stream read the arrays released below
+    bft_trace_mark("ids narrowed, foreign stream waited");
+    bft_stage("dictionary ids narrowed", narrowed_here ? (double)n_ids * (4 + new_cs_w) : 0.0, h->stream);
+    double kh_ms = 0;
+    const bool kh_ok = !kh_redo && kh_finish(h, khf, &kh_ms);
+    bft_trace_mark("k-mer hash fill waited");
+    bft_stage("wait for the k-mer hash build", 0, h->stream);
+    if (h->inject_build_failure) {
+        h->inject_build_failure = false;
+        return fail(BFT_GPU_E_LIMIT, "injected build failure (test hook)");
+    }
+
+    // ---- commit: nothing above touched the handle; from here on nothing can fail before the image is whole ----
+    h->d_tcol.swap(n_tcol);
+    h->d_cs_off.swap(n_cs_off);
+    h->d_cs_ids.swap(n_cs_ids_w);
+    h->cs_w = new_cs_w;
+    h->n_sets = n_sets;
+    h->n_ids = n_ids;
+    h->cs_on_host = false;
+    h->cs_off.clear();
+    h->cs_ids.clear();
+    h->d_ccx.swap(n_ccx);
+    h->d_f18.swap(n_f18buf);
+    h->d_fent.swap(n_fentbuf);
+    h->n_f18 = n_f18;
+    h->n_fent = n_fent;
+    h->log_k.release();
+    h->log_g.release();
+    h->log_cap = 0;
+    h->d_nodes.swap(idx.nodes);
+    h->d_bfT.swap(idx.bfT);
+    h->d_ccs.swap(idx.ccs);
+    h->d_f2w.swap(idx.f2w);
+    h->d_clus.swap(idx.clus);
+    h->d_child.swap(idx.child);
+    h->d_uck.swap(idx.uck);
+    h->d_ucrow.swap(idx.ucrow);
+    h->d_tk.swap(tk);
+    h->n_pairs = np;
+    h->log_n = 0;
+    h->lb_end.clear();
+    h->lb_gid.clear();
+    h->log_comp = false;
+    h->log_g_sorted = true;
+    h->n_kmers = nk;
+    h->idx_sizes[0] = idx.n_nodes * sizeof(BftNode); h->idx_sizes[1] = idx.n_bf8 * 8; h->idx_sizes[2] = idx.n_ccs * sizeof(BftCC);
+    h->idx_sizes[3] = idx.n_f2w * 8; h->idx_sizes[4] = idx.n_clus * 8; h->idx_sizes[5] = idx.n_child * 8;
+    h->idx_sizes[6] = idx.n_uc * (uint64_t)W * 8; h->idx_sizes[7] = idx.n_uc * 4; h->idx_sizes[8] = nk * (uint64_t)W * 8;
+    h->root_ncc = (uint32_t)idx.root_ncc;
+    point_image(h, std::max<uint32_t>((uint32_t)h->genomes.size(), h->any_insert ? h->max_gid_seen + 1 : 0));
+    BftImage& im = h->im;
+
+    uint64_t* I = h->info;
+    I[0] = h->k;
+    I[1] = nk;
+    I[2] = idx.n_nodes;
+    I[3] = idx.n_ccs;
+    I[4] = idx.n_uc;
+    I[5] = idx.n_child_nodes;
+    I[6] = idx.n_prefixes;
+    I[7] = idx.n_ccs_s4;
+    I[8] = idx.max_ccs_per_node;
+    I[9] = np;
+    I[10] = n_sets;
+    I[11] = im.nb_genomes;
+    I[12] = image_bytes(h);
+    I[13] = idx.root_ncc;
+    I[14] = idx.root_uc;
+    h->root_ncc = (uint32_t)idx.root_ncc;
+    h->build_ms[0] = t1 - t0;
+    h->build_ms[1] = t2 - t1;
+    h->build_ms[2] = t3 - t2;
+    h->build_ms[3] = (double)h->front_redone;
+    h->built = true;
+    ensure_claim_counters(h);
+    bft_trace_mark("committed (buffers released)");
+    derive_root_direct(h);
+    if (kh_ok) kh_adopt(h, khf, kh_ms);  // built during the assembly
+    else kh_drop(h);
+    if (kh_redo) derive_kmer_hash(h);  // (after the exact interning: from the committed table and colour sets)
+    sync_walk_kh(h);
+    bft_trace_mark("root tables");
+    bft_stage("root tables", 0, h->stream);
+    derive_node_hash(h);
+    default_launch_shape(h);
+    I[12] = image_bytes(h);
+    h->table_dropped = false;
+    drop_table(h);  // ("compact_table")
+    bft_trace_mark("launch shape; done");
+    bft_stage("node hash, launch shape, compact table", 0, h->stream);
+    if (bft_trace_on()) {
+        std::lock_guard<std::mutex> lk(g_pool_mu);
+        fprintf(stderr, "[bft_gpu build] cache of released blocks: %zu blocks, %.1f MB; this process so far: %llu hipMalloc (%.2f ms), %llu hipFree on release (%.2f ms)\n", g_pool.size(),
+                g_pool_bytes / 1048576.0, (unsigned long long)g_malloc_calls, g_malloc_ms, (unsigned long long)g_free_calls, g_free_ms);
+    }
+    h->build_ms[4] = now_ms() - t3;
+    return BFT_GPU_OK;
+}
+
 extern "C" int bft_gpu_build(bft_gpu* h) {
     if (!h) return fail(BFT_GPU_E_ARG, "NULL handle");
     ENTER(h);
@@ -1692,153 +1847,9 @@ extern "C" int bft_gpu_build(bft_gpu* h) {
         CK(bft_count_pairs(n_tcol.as<uint32_t>(), nk, n_cs_off.as<uint32_t>(), h->stream, &total_pairs));
     }
     np = total_pairs;
-    struct KhStart {  // (from here on tk, n_tcol and the number of colour sets are final)
-        bft_gpu* h; const uint64_t* tk; const uint32_t* tcol; uint64_t nk, n_sets; KhFill* f;
-        static void run(void* c, hipStream_t s) { KhStart* k = (KhStart*)c; kh_start(k->h, k->tk, k->tcol, k->nk, k->n_sets, *k->f, s, nullptr); }
-    } khs{h, tk.as<uint64_t>(), n_tcol.as<uint32_t>(), nk, n_sets, &khf};
-    // (started HERE instead -- beside the root's table passes -- the sort-based table build was measured too: 17.2-18.4 ms against 17.0)
-    // (and earlier still -- behind the root's prefix scans, or before them: 15.7 ms each way, round 5: the build is bound by the device's total work,
-    // not by either stream's chain)
-    const BftAssembleHook hook{tk.p ? &KhStart::run : nullptr, &khs};
     bft_trace_mark("merge / bookkeeping");
     bft_stage("merge into the index", 0, h->stream);
-    double t2 = now_ms();
-
-    // 5. containers, level by level, on the GPU
-    if (!tk.p) CK(tk.alloc(8));
-    BftDeviceIndex idx;
-    CK(bft_assemble_gpu(tk.as<uint64_t>(), nk, h->k, h->d_hashmod.as<uint32_t>(), h->stream, idx, &hook));
-    bft_trace_mark("containers assembled");
-    bft_stage("containers: concatenation", 0, h->stream);
-    double t3 = now_ms();
-    DevBuf n_ccx, n_f18buf, n_fentbuf;
-    uint64_t n_f18 = 0, n_fent = 0;
-    CK(bft_flatten_gpu(idx.ccs.as<BftCC>(), idx.n_ccs, idx.f2w.as<uint64_t>(), idx.clus.as<uint64_t>(), idx.child.as<uint64_t>(), h->opt_flat_min, h->stream,
-                       n_ccx, n_f18buf, n_fentbuf, n_f18, n_fent));
-    bft_trace_mark("flat forms");
-    bft_stage("flat forms of the big CCs", (double)(n_f18 + n_fent) * 8, h->stream);
-    bool kh_redo = false;
-    {   // the interning's deferred tail: done long ago; two lists with one signature (never seen outside the test hook) -> the exact interning
-        uint32_t collisions = 0;
-        CK(tail.wait(&collisions));
-        if (collisions) {
-            double ms_ = 0;
-            (void)kh_finish(h, khf, &ms_);  // (the table under construction holds the wrong colour sets, and reads the arrays replaced below)
-            khf.buf.release();
-            kh_redo = true;
-            CK(bft_intern_colors_gpu(seg_off.as<uint32_t>(), npg.as<uint32_t>(), nk, np, h->stream, n_tcol, n_cs_off, n_cs_ids, n_sets, n_ids, 0, nullptr, true));
-        }
-        seg_off.release();
-        npg.release();
-    }
-    const uint32_t new_cs_w = id_width(h->max_gid_seen);
-    DevBuf n_cs_ids_w;
-    bool narrowed_here = false;
-    if (!kh_redo && tail.narrow.p && tail.narrow_w == new_cs_w) {  // (done by the interning's tail on the side stream)
-        n_cs_ids_w.swap(tail.narrow);
-        n_cs_ids.release();
-    } else {
-        CK(narrow_ids(n_cs_ids, n_ids, new_cs_w, h->stream, n_cs_ids_w));
-        narrowed_here = new_cs_w < 4;
-    }
-    CK(wait_foreign_stream(h));  // queries a caller still has in flight on its own stream read the arrays released below
-    bft_trace_mark("ids narrowed, foreign stream waited");
-    bft_stage("dictionary ids narrowed", narrowed_here ? (double)n_ids * (4 + new_cs_w) : 0.0, h->stream);
-    double kh_ms = 0;
-    const bool kh_ok = !kh_redo && kh_finish(h, khf, &kh_ms);
-    bft_trace_mark("k-mer hash fill waited");
-    bft_stage("wait for the k-mer hash build", 0, h->stream);
-    if (h->inject_build_failure) {
-        h->inject_build_failure = false;
-        return fail(BFT_GPU_E_LIMIT, "injected build failure (test hook)");
-    }
-
-    // ---- commit: nothing above touched the handle; from here on nothing can fail before the image is whole ----
-    h->d_tcol.swap(n_tcol);
-    h->d_cs_off.swap(n_cs_off);
-    h->d_cs_ids.swap(n_cs_ids_w);
-    h->cs_w = new_cs_w;
-    h->n_sets = n_sets;
-    h->n_ids = n_ids;
-    h->cs_on_host = false;
-    h->cs_off.clear();
-    h->cs_ids.clear();
-    h->d_ccx.swap(n_ccx);
-    h->d_f18.swap(n_f18buf);
-    h->d_fent.swap(n_fentbuf);
-    h->n_f18 = n_f18;
-    h->n_fent = n_fent;
-    h->log_k.release();
-    h->log_g.release();
-    h->log_cap = 0;
-    h->d_nodes.swap(idx.nodes);
-    h->d_bfT.swap(idx.bfT);
-    h->d_ccs.swap(idx.ccs);
-    h->d_f2w.swap(idx.f2w);
-    h->d_clus.swap(idx.clus);
-    h->d_child.swap(idx.child);
-    h->d_uck.swap(idx.uck);
-    h->d_ucrow.swap(idx.ucrow);
-    h->d_tk.swap(tk);
-    h->n_pairs = np;
-    h->log_n = 0;
-    h->lb_end.clear();
-    h->lb_gid.clear();
-    h->log_comp = false;
-    h->log_g_sorted = true;
-    h->n_kmers = nk;
-    h->idx_sizes[0] = idx.n_nodes * sizeof(BftNode); h->idx_sizes[1] = idx.n_bf8 * 8; h->idx_sizes[2] = idx.n_ccs * sizeof(BftCC);
-    h->idx_sizes[3] = idx.n_f2w * 8; h->idx_sizes[4] = idx.n_clus * 8; h->idx_sizes[5] = idx.n_child * 8;
-    h->idx_sizes[6] = idx.n_uc * (uint64_t)W * 8; h->idx_sizes[7] = idx.n_uc * 4; h->idx_sizes[8] = nk * (uint64_t)W * 8;
-    h->root_ncc = (uint32_t)idx.root_ncc;
-    point_image(h, std::max<uint32_t>((uint32_t)h->genomes.size(), h->any_insert ? h->max_gid_seen + 1 : 0));
-    BftImage& im = h->im;
-
-    uint64_t* I = h->info;
-    I[0] = h->k;
-    I[1] = nk;
-    I[2] = idx.n_nodes;
-    I[3] = idx.n_ccs;
-    I[4] = idx.n_uc;
-    I[5] = idx.n_child_nodes;
-    I[6] = idx.n_prefixes;
-    I[7] = idx.n_ccs_s4;
-    I[8] = idx.max_ccs_per_node;
-    I[9] = np;
-    I[10] = n_sets;
-    I[11] = im.nb_genomes;
-    I[12] = image_bytes(h);
-    I[13] = idx.root_ncc;
-    I[14] = idx.root_uc;
-    h->root_ncc = (uint32_t)idx.root_ncc;
-    h->build_ms[0] = t1 - t0;
-    h->build_ms[1] = t2 - t1;
-    h->build_ms[2] = t3 - t2;
-    h->build_ms[3] = (double)h->front_redone;
-    h->built = true;
-    ensure_claim_counters(h);
-    bft_trace_mark("committed (buffers released)");
-    derive_root_direct(h);
-    if (kh_ok) kh_adopt(h, khf, kh_ms);  // built during the assembly
-    else kh_drop(h);
-    if (kh_redo) derive_kmer_hash(h);  // (after the exact interning: from the committed table and colour sets)
-    sync_walk_kh(h);
-    bft_trace_mark("root tables");
-    bft_stage("root tables", 0, h->stream);
-    derive_node_hash(h);
-    default_launch_shape(h);
-    I[12] = image_bytes(h);
-    h->table_dropped = false;
-    drop_table(h);  // ("compact_table")
-    bft_trace_mark("launch shape; done");
-    bft_stage("node hash, launch shape, compact table", 0, h->stream);
-    if (bft_trace_on()) {
-        std::lock_guard<std::mutex> lk(g_pool_mu);
-        fprintf(stderr, "[bft_gpu build] cache of released blocks: %zu blocks, %.1f MB; this process so far: %llu hipMalloc (%.2f ms), %llu hipFree on release (%.2f ms)\n", g_pool.size(),
-                g_pool_bytes / 1048576.0, (unsigned long long)g_malloc_calls, g_malloc_ms, (unsigned long long)g_free_calls, g_free_ms);
-    }
-    h->build_ms[4] = now_ms() - t3;
-    return BFT_GPU_OK;
+    return commit_image(h, tk, n_tcol, n_cs_off, n_cs_ids, nk, n_sets, n_ids, np, khf, tail, seg_off, npg, t0, t1);
 }
 
 static int ensure_table(bft_gpu* h);
@@ -2009,7 +2020,7 @@ static int launch_query_kh(bft_gpu* h, const uint8_t* d_kmers, uint64_t n, uint6
 
 // Which kernel a batch takes: the k-mer hash answers presence and colour sets (one cache line per k-mer); rows -- positions in the
 // sorted table, what the reference keeps in resultPresence -- come from the container walk, as does everything on an image
-// without the table ("kmer_hash" 0, k >= 64, 2k % 64 == 0).  Same answers either way (tests/test_gpu_parity.py).
+// without the k-mer hash ("kmer_hash" 0, a table that could not be allocated or whose overflow list ran full: kh_wanted, kh_finish).  Same answers either way (tests/test_gpu_parity.py).
 static int launch_query(bft_gpu* h, const uint8_t* d_kmers, uint64_t n, uint64_t* d_bits64, uint32_t* d_rows, hipStream_t s, int rec_bytes = 0) {
     if (n == 0) return 0;
     const int rec = rec_bytes ? rec_bytes : h->B;
@@ -3458,6 +3469,182 @@ extern "C" int bft_gpu_query_prefixes(bft_gpu* h, const uint8_t* prefixes, const
     HIPCK(hipStreamSynchronize(s));
     pm_release(h, s);
     return BFT_GPU_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// sub-graphs (create_cdbg_from_bft_kmers, include/bft.h:179, src/bft.c:1353-1464): the batch looked up in the source, the found k-mers
+// sorted and de-duplicated, the used part of the dictionary renumbered (bft_subgraph.hip), then the common tail of a build (commit_image)
+// ------------------------------------------------------------------------------------------------
+struct SgEvent {
+    hipEvent_t e = nullptr;
+    ~SgEvent() { if (e) (void)hipEventDestroy(e); }
+};
+// d: a fresh handle with src's k and seeds.  The lookup runs on s (the caller's stream: d_kmers is read in its order), everything after it on
+// d's stream; the new launches are timed on src ("timing"), the stages recorded on d when src records them ("build_stages").
+static int subgraph_fill(bft_gpu* src, bft_gpu* d, const uint8_t* d_kmers, uint64_t n, bool colors, uint64_t* n_absent, hipStream_t s) {
+    const int W = src->W;
+    if (colors) {
+        d->genomes = src->genomes;
+        d->max_gid_seen = src->max_gid_seen;
+        d->any_insert = src->any_insert;
+    } else {  // (one genome, named after the source's genome 0)
+        if (!src->genomes.empty()) d->genomes.push_back(src->genomes[0]);
+        d->any_insert = true;
+    }
+    d->opt_build_stages = src->opt_build_stages;
+    CK(set_device(d));  // (from here on the cache hands out blocks for d's stream)
+    const hipStream_t ds = d->stream;
+    StageScope stage_scope(d);
+    const double t0 = now_ms();
+    SgEvent ev;
+    HIPCK(hipEventCreateWithFlags(&ev.e, hipEventDisableTiming));
+
+    // 1. lookup: the colour-set id of every found k-mer, from the k-mer hash or -- an image without one -- the walk's tcol[row]
+    DevBuf bits, cs, cnt, keys, vals;
+    CK(bits.alloc(((n + 63) / 64) * 8));
+    CK(cs.alloc(n * 4));
+    CK(cnt.alloc_zero(8, ds));
+    unsigned long long m = 0;
+    if (n) {
+        HIPCK(hipEventRecord(ev.e, ds));  // (the blocks above may still be in use on d's stream)
+        HIPCK(hipStreamWaitEvent(s, ev.e, 0));
+        src->im.emit_cs = 1;
+        const int rc = launch_query(src, d_kmers, n, bits.as<uint64_t>(), cs.as<uint32_t>(), s);
+        src->im.emit_cs = 0;
+        CK(rc);
+        CK(note_foreign_stream(src, s));
+        HIPCK(hipEventRecord(ev.e, s));
+        HIPCK(hipStreamWaitEvent(ds, ev.e, 0));
+        bft_stage("sub-graph: lookup in the source", (double)n * (src->B + 4) + (double)n / 8, ds);
+        // 2. the found ones as (T-form key, colour-set id) records
+        CK(keys.alloc(n * W * 8));
+        CK(vals.alloc(n * 4));
+        CK(timed_launch(src, ds, [&] {
+            return bft_sg_compact(W, d_kmers, n, src->k, src->B, bits.as<uint64_t>(), cs.as<uint32_t>(), keys.as<uint64_t>(), n, vals.as<uint32_t>(),
+                                  cnt.as<unsigned long long>(), ds);
+        }));
+        HIPCK(hipMemcpyAsync(&m, cnt.p, 8, hipMemcpyDeviceToHost, ds));
+        HIPCK(hipStreamSynchronize(ds));
+        bft_stage("sub-graph: found k-mers compacted", (double)n * (src->B + 4) + (double)m * (8 * W + 4), ds);
+    }
+    bits.release();
+    cs.release();
+    if (n_absent) *n_absent = n - m;
+
+    // 3. order (the library's sort, keys only: equal keys carry equal ids) and de-duplication (first record of every run: one scan)
+    DevBuf tk, tcol;
+    uint64_t nk = 0;
+    if (m) {
+        DevBuf sk, sg, pos, tmp;
+        CK(sk.alloc(m * W * 8));
+        CK(sg.alloc(m * 4));
+        CK(timed_launch(src, ds, [&] { return sort_pairs(d, keys.as<uint64_t>(), n, vals.as<uint32_t>(), m, sk.as<uint64_t>(), m, sg.as<uint32_t>(), true); }));
+        keys.release();
+        vals.release();
+        CK(pos.alloc((m + 1) * 4));
+        const BftSgHeads heads{sk.as<uint64_t>(), m, m, W};
+        CK(timed_launch(src, ds, [&] { return bft_scan::exclusive_sum<uint32_t>(heads, pos.as<uint32_t>(), m, ds, tmp, nullptr, true); }));
+        uint32_t nk32 = 0;
+        HIPCK(hipMemcpyAsync(&nk32, pos.as<uint32_t>() + m, 4, hipMemcpyDeviceToHost, ds));
+        HIPCK(hipStreamSynchronize(ds));
+        nk = nk32;
+        CK(tk.alloc(nk * W * 8));
+        CK(tcol.alloc(nk * 4));
+        CK(timed_launch(src, ds, [&] { return bft_sg_scatter(W, sk.as<uint64_t>(), m, sg.as<uint32_t>(), m, pos.as<uint32_t>(), tk.as<uint64_t>(), tcol.as<uint32_t>(), ds); }));
+        HIPCK(hipStreamSynchronize(ds));
+    } else {
+        CK(tcol.alloc(4));
+    }
+    bft_stage("sub-graph: sort + dedupe", (double)m * (8 * W + 4) * 6 + (double)nk * (8 * W + 4), ds);
+
+    // 4. the dictionary: the used sets of the source in their old order (colours), or the one set {0}
+    DevBuf cs_off, cs_ids;
+    uint64_t n_sets = 0, n_ids = 0, np = 0;
+    if (nk && colors) {
+        const uint64_t S = src->n_sets;
+        DevBuf used, new_id, id_pos, tmp;
+        CK(used.alloc_zero(S * 4, ds));
+        CK(new_id.alloc((S + 1) * 4));
+        CK(id_pos.alloc((S + 1) * 4));
+        const uint32_t* old_off = src->d_cs_off.as<uint32_t>();
+        CK(timed_launch(src, ds, [&] { return bft_sg_mark(tcol.as<uint32_t>(), nk, used.as<uint32_t>(), ds); }));
+        CK(timed_launch(src, ds, [&] { return bft_scan::exclusive_sum_ptr<uint32_t>(used.as<uint32_t>(), new_id.as<uint32_t>(), S, ds, tmp, nullptr, true); }));
+        const BftSgUsedLen lens{used.as<uint32_t>(), old_off, S};
+        CK(timed_launch(src, ds, [&] { return bft_scan::exclusive_sum<uint32_t>(lens, id_pos.as<uint32_t>(), S, ds, tmp, nullptr, true); }));
+        uint32_t tot[2] = {0, 0};
+        HIPCK(hipMemcpyAsync(&tot[0], new_id.as<uint32_t>() + S, 4, hipMemcpyDeviceToHost, ds));
+        HIPCK(hipMemcpyAsync(&tot[1], id_pos.as<uint32_t>() + S, 4, hipMemcpyDeviceToHost, ds));
+        HIPCK(hipStreamSynchronize(ds));
+        n_sets = tot[0];
+        n_ids = tot[1];
+        CK(cs_off.alloc((n_sets + 1) * 4));
+        CK(cs_ids.alloc(n_ids * 4));
+        CK(timed_launch(src, ds, [&] { return bft_sg_remap(tcol.as<uint32_t>(), nk, new_id.as<uint32_t>(), ds); }));
+        CK(timed_launch(src, ds, [&] {
+            return bft_sg_dict(used.as<uint32_t>(), new_id.as<uint32_t>(), id_pos.as<uint32_t>(), old_off, src->d_cs_ids.p, src->cs_w, S, cs_off.as<uint32_t>(),
+                               cs_ids.as<uint32_t>(), ds);
+        }));
+        CK(bft_count_pairs(tcol.as<uint32_t>(), nk, cs_off.as<uint32_t>(), ds, &np));
+        bft_stage("sub-graph: used part of the dictionary", (double)nk * 12 + (double)S * 16 + (double)n_ids * (src->cs_w + 4), ds);
+    } else if (nk) {
+        static const uint32_t one_set[3] = {0, 1, 0};  // cs_off = {0, 1}, cs_ids = {0}
+        CK(cs_off.alloc(8));
+        CK(cs_ids.alloc(4));
+        HIPCK(hipMemsetAsync(tcol.p, 0, nk * 4, ds));
+        HIPCK(hipMemcpyAsync(cs_off.p, one_set, 8, hipMemcpyHostToDevice, ds));
+        HIPCK(hipMemcpyAsync(cs_ids.p, one_set + 2, 4, hipMemcpyHostToDevice, ds));
+        n_sets = 1;
+        n_ids = 1;
+        np = nk;
+    } else {
+        CK(cs_off.alloc_zero(4, ds));
+        CK(cs_ids.alloc(4));
+    }
+    HIPCK(hipStreamSynchronize(ds));
+    const double t1 = now_ms();
+
+    // 5-7. containers, flat forms, k-mer hash, root tables, commit: the build's own tail
+    KhFill khf;
+    BftInternTail tail;  // (nothing deferred: no interning here)
+    DevBuf seg_off, npg;
+    return commit_image(d, tk, tcol, cs_off, cs_ids, nk, n_sets, n_ids, np, khf, tail, seg_off, npg, t0, t1);
+}
+
+static int subgraph_new(bft_gpu* src, const uint8_t* d_kmers, uint64_t n, int colors, uint64_t* n_absent, bft_gpu** out, hipStream_t s) {
+    if (n >= (1ull << 31)) return fail(BFT_GPU_E_LIMIT, "sub-graph batch of 2^31 k-mers or more");
+    if (stream_capturing(s)) return fail(BFT_GPU_E_ARG, "sub-graph recorded into a graph: it allocates and synchronises");
+    CK(ensure_built(src, false));
+    if (!(src->im.kh_lines != nullptr && !src->opt_walk_hash)) CK(ensure_table(src));  // (the walk answers: launch_query would bring the table back itself)
+    HIPCK(hipStreamSynchronize(src->stream));
+    bft_gpu* d = nullptr;
+    CK(bft_gpu_create_seeded(src->k, src->device, src->r1, src->r2, &d));
+    const int rc = subgraph_fill(src, d, d_kmers, n, colors != 0, n_absent, s);
+    if (rc) {
+        const std::string err = g_err;
+        bft_gpu_free(d);
+        return fail(rc, err);
+    }
+    *out = d;
+    return BFT_GPU_OK;
+}
+
+extern "C" int bft_gpu_subgraph_dev(bft_gpu* src, const void* d_kmers, uint64_t nb_kmers, int colors, uint64_t* n_absent, bft_gpu** out, void* hip_stream) {
+    if (!src || !out || (!d_kmers && nb_kmers)) return fail(BFT_GPU_E_ARG, "NULL argument");
+    *out = nullptr;
+    ENTER(src);
+    return subgraph_new(src, (const uint8_t*)d_kmers, nb_kmers, colors, n_absent, out, hip_stream ? (hipStream_t)hip_stream : src->stream);
+}
+
+extern "C" int bft_gpu_subgraph(bft_gpu* src, const uint8_t* kmers, uint64_t nb_kmers, int colors, uint64_t* n_absent, bft_gpu** out) {
+    if (!src || !out || (!kmers && nb_kmers)) return fail(BFT_GPU_E_ARG, "NULL argument");
+    *out = nullptr;
+    ENTER(src);
+    DevBuf dk;
+    if (nb_kmers) {
+        CK(dk.alloc(nb_kmers * src->B));
+        HIPCK(hipMemcpy(dk.p, kmers, nb_kmers * src->B, hipMemcpyHostToDevice));
+    }
+    return subgraph_new(src, dk.as<uint8_t>(), nb_kmers, colors, n_absent, out, src->stream);
 }
 
 // The colour set `cs` in the reference's annotation bytes (smallest of modes 0/1/2, compute_best_mode,

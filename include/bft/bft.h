@@ -18,8 +18,7 @@
  *   - insertions are collected on the GPU and the containers are rebuilt in bulk by the first query after them;
  *   - there is no CPU fallback: without a usable GPU every function reports the error and exits.
  * Not provided (outside the path): marking / flags, annotation set operations, prefix_matching_custom,
- * create_cdbg_from_bft_kmers, add_id_genomes, colour compression (write_BFT ignores compress_annotations and writes
- * uncompressed annotations, which the reference loads).
+ * colour compression (write_BFT ignores compress_annotations and writes uncompressed annotations, which the reference loads).
  */
 #ifndef BFT_GPU_COMPAT_BFT_H
 #define BFT_GPU_COMPAT_BFT_H
@@ -162,6 +161,16 @@ void v_iterate_over_kmers(BFT* bft, BFT_func_ptr f, va_list args);
  * matched.  The same set of k-mers as the reference; the order is the index's (ascending in its internal key), as for iterate_over_kmers,
  * not the reference's container order. ---- */
 bool prefix_matching(BFT* bft, char* prefix, BFT_func_ptr f, ...);
+
+/* ---- sub-graphs (include/bft.h:179-180, src/bft.c:1353-1684).  create_cdbg_from_bft_kmers: a new graph of the given k-mers (their ASCII
+ * kmer field is read).  add_colors: the k-mers bft stores, each with its colour set and bft's genomes, built on the GPU from bft's own tables
+ * (bft_gpu_subgraph); k-mers bft does not store are skipped -- the reference's behaviour there is undefined.  Otherwise every given k-mer goes
+ * into one new genome named bft->filenames[0], stored in bft or not, as in the reference.  add_id_genomes: list_id_genomes[0] ids follow
+ * (sorted in place, as the reference does); an id that names no inserted genome prints the reference's message and exits; the k-mer's
+ * colour set gains the others, and bft_kmer->res is looked up again so that get_annotation(bft_kmer) answers the widened set.  bft_annot is
+ * not read. ---- */
+BFT* create_cdbg_from_bft_kmers(BFT_kmer** bft_kmers, uint32_t nb_bft_kmers, BFT* bft, bool add_colors);
+void add_id_genomes(BFT_kmer* bft_kmer, BFT_annotation* bft_annot, BFT* bft, uint32_t* list_id_genomes);
 
 /* ---- disk (include/bft.h:175-176, src/bft.c:1090-1110, src/write_to_disk.c) ---- */
 void write_BFT(BFT* bft, char* filename, bool compress_annotations);

@@ -284,6 +284,20 @@ int bft_gpu_query_prefixes(bft_gpu* h, const uint8_t* prefixes, const uint8_t* l
 int bft_gpu_query_prefixes_dev(bft_gpu* h, const void* d_prefixes, const void* d_lengths, uint64_t nb_prefixes, void* d_offsets, void* d_kmers_out,
                                void* d_rows_out, void* d_colorsets_out, uint64_t cap, void* d_needed, void* hip_stream);
 
+/* create_cdbg_from_bft_kmers(bft_kmers, nb_bft_kmers, bft, add_colors) (include/bft.h:179, src/bft.c:1353-1464) without the genome-by-genome
+ * re-insertion: a new handle on src's device holding those of the nb_kmers k-mers (packed, reference layout, like every query) that src stores.
+ * colors != 0: each keeps its colour set; the new handle has src's genome names and count.
+ * colors == 0: one genome, named after src's genome 0; every k-mer's set is {0}.
+ * Duplicates collapse.  Absent k-mers are skipped and counted in *n_absent (may be NULL).  Same k and Bloom seeds as src.
+ * Options are the library defaults ("build_stages" follows src: the stages of the call are the new handle's; the new launches are counted in
+ * src's bft_gpu_kernel_time).  src is built first if it has pending insertions; its answers are unchanged.  The new handle is a full handle
+ * (queries, insertions, merges, bft_gpu_write_bft, bft_gpu_image_pack) and shares no device buffer with src: either may be freed first.
+ * At most 2^31 - 1 k-mers per call (BFT_GPU_E_LIMIT).  Synchronous: the handle is whole when the call returns. */
+int bft_gpu_subgraph(bft_gpu* src, const uint8_t* kmers, uint64_t nb_kmers, int colors, uint64_t* n_absent, bft_gpu** out);
+/* The same on a RESIDENT batch: d_kmers is read in order on hip_stream (NULL = src's stream); not inside a graph capture (BFT_GPU_E_ARG). */
+int bft_gpu_subgraph_dev(bft_gpu* src, const void* d_kmers, uint64_t nb_kmers, int colors, uint64_t* n_absent, bft_gpu** out,
+                         void* hip_stream);
+
 /* A colour set as the reference's annotation bytes -- BFT_annotation::annot as get_annotation returns it
  * (include/bft.h:97, src/bft.c:363-387): mode 0 (bitmap, genome g <-> bit g+2), 1 (ranges) or 2 (id list), chosen the way the
  * reference chooses it: compute_best_mode re-decides at every insertion of a genome id and keeps the current mode on a size tie
