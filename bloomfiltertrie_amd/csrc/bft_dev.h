@@ -35,7 +35,9 @@ struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;  // requested size
     size_t cap = 0;    // size of the block behind it
-    uint32_t tag = 0, tag2 = 0;  // the user's (bft_scan.h: launches so far, states the last one used); zero after every alloc
+    // the user's (bft_scan.h: launches so far, states the last one used); zero after every alloc.  A block that a scan uses must not be written by
+    // anything else -- a kernel, a memset, a sort's scratch -- unless that writer sets tag = 0: the next scan trusts tag and skips its zeroing.
+    uint32_t tag = 0, tag2 = 0;
     DevBuf() {}
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;

@@ -386,6 +386,7 @@ struct bft_gpu {
     bool sq_used = false;
     uint64_t sq_units = 0;
     DevBuf qc_cs, qc_tmp;            // scratch of the resident colour-list queries: colour-set id per k-mer, the scan's temporary (grown, never shrunk)
+    DevBuf qc_kh;                    // k_colors_kh's tile counter and states (bft_kh_colors_scratch_bytes): not qc_tmp, whose bft_scan state (tag) it would corrupt
     hipStream_t qc_stream = nullptr;
     hipEvent_t qc_ev = nullptr;  // where the last use of the scratch ends (the stream it ran on is the caller's: it may be gone by the next call)
     bool qc_used = false;  // bound on the blocks of k-mer positions the sequence kernel deals out (claim_counters)
@@ -530,6 +531,13 @@ static int timing_end(bft_gpu* h, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
     HIPCK(hipEventRecord(e1, s));
     h->pending_ev.push_back({e0, e1});
     return 0;
+}
+template <class F>
+static int timed_launch(bft_gpu* h, hipStream_t s, F&& launch) {
+    hipEvent_t e0, e1;
+    CK(timing_begin(h, s, &e0, &e1));
+    CK(launch());
+    return timing_end(h, s, e0, e1);
 }
 
 extern "C" void bft_gpu_free(bft_gpu* h) {
@@ -2318,17 +2326,15 @@ static int colors_core(bft_gpu* h, const uint8_t* d_kmers, uint64_t n, uint64_t*
     }
     if (fill && h->im.kh_lines != nullptr && !h->opt_walk_hash && bft_kh_has_kernels(h->W, h->im.kh.S) && h->im.nb_genomes < 65536u) {  // (k_colors_kh keeps list lengths in 16 bits)
         // through the k-mer hash: lookup, offsets and ids in ONE launch (k_colors_kh; the host entry point counts first and fills per chunk: the three steps below)
+        // (a block of its own: the kernel writes its counter and states raw, which a block of bft_scan's -- qc_tmp -- must never see)
         const size_t sb = bft_kh_colors_scratch_bytes(n);
-        if (h->qc_tmp.bytes < sb) {
+        if (h->qc_kh.bytes < sb) {
             if (h->qc_used) HIPCK(hipStreamSynchronize(s));
-            CK(h->qc_tmp.alloc(sb + sb / 2));
+            CK(h->qc_kh.alloc(sb + sb / 2));
         }
         h->qc_used = true;
         h->qc_stream = s;
-        hipEvent_t e0, e1;
-        CK(timing_begin(h, s, &e0, &e1));
-        CK(bft_kh_colors(h->im, d_kmers, n, h->B, d_bits64, d_offsets, d_ids, d_ids ? ids_cap : 0, d_needed, h->qc_tmp.p, s));
-        CK(timing_end(h, s, e0, e1));
+        CK(timed_launch(h, s, [&] { return bft_kh_colors(h->im, d_kmers, n, h->B, d_bits64, d_offsets, d_ids, d_ids ? ids_cap : 0, d_needed, h->qc_kh.p, s); }));
         if (!h->qc_ev && hipEventCreateWithFlags(&h->qc_ev, hipEventDisableTiming) != hipSuccess) { h->qc_ev = nullptr; (void)hipGetLastError(); }
         if (h->qc_ev && hipEventRecord(h->qc_ev, s) != hipSuccess) (void)hipGetLastError();
         return 0;
@@ -2351,8 +2357,11 @@ static int colors_core(bft_gpu* h, const uint8_t* d_kmers, uint64_t n, uint64_t*
     const BftCsLen len{d_cs, h->im.cs_off, n};
     CK((bft_scan::exclusive_sum<uint64_t>(len, d_offsets, n + 1, s, h->qc_tmp)));
     if (fill) {
-        hipLaunchKernelGGL(k_color_fill_cs, dim3(grid_for((n + 255) / 256)), dim3(256), 0, s, d_cs, h->im.cs_off, h->im.cs_ids, h->im.cs_w, d_offsets, n, ids_cap, d_ids, d_needed);
-        HIPCK(hipGetLastError());
+        CK(timed_launch(h, s, [&] {
+            hipLaunchKernelGGL(k_color_fill_cs, dim3(grid_for((n + 255) / 256)), dim3(256), 0, s, d_cs, h->im.cs_off, h->im.cs_ids, h->im.cs_w, d_offsets, n, ids_cap, d_ids, d_needed);
+            HIPCK(hipGetLastError());
+            return 0;
+        }));
     }
     if (!h->qc_ev && hipEventCreateWithFlags(&h->qc_ev, hipEventDisableTiming) != hipSuccess) { h->qc_ev = nullptr; (void)hipGetLastError(); }
     if (h->qc_ev && hipEventRecord(h->qc_ev, s) != hipSuccess) (void)hipGetLastError();
@@ -2401,8 +2410,12 @@ extern "C" int bft_gpu_query_colors(bft_gpu* h, const uint8_t* kmers, uint64_t n
         if (!overflow && ids && total + cnt <= ids_cap) {
             if (cnt) {
                 CK(dids.alloc(cnt * 4));
-                hipLaunchKernelGGL(k_color_fill_cs, dim3(grid_for((m + 255) / 256)), dim3(256), 0, h->stream, h->qc_cs.as<uint32_t>(), h->im.cs_off, h->im.cs_ids, h->im.cs_w,
-                                   doff.as<uint64_t>(), m, cnt, dids.as<uint32_t>(), (uint64_t*)nullptr);
+                CK(timed_launch(h, h->stream, [&] {
+                    hipLaunchKernelGGL(k_color_fill_cs, dim3(grid_for((m + 255) / 256)), dim3(256), 0, h->stream, h->qc_cs.as<uint32_t>(), h->im.cs_off, h->im.cs_ids, h->im.cs_w,
+                                       doff.as<uint64_t>(), m, cnt, dids.as<uint32_t>(), (uint64_t*)nullptr);
+                    HIPCK(hipGetLastError());
+                    return 0;
+                }));
                 HIPCK(hipMemcpyAsync(ids + total, dids.p, cnt * 4, hipMemcpyDeviceToHost, h->stream));
                 HIPCK(hipStreamSynchronize(h->stream));
             }
@@ -2439,6 +2452,8 @@ static int ensure_cs_bitmaps(bft_gpu* h) {
 // d_rowidx: the row of every k-mer (scratch: overwritten with the colour-set ids when the bitmap dictionary is used)
 static int launch_color_rows(bft_gpu* h, uint32_t* d_rowidx, uint64_t n, uint32_t rowbytes, uint8_t* d_out, hipStream_t s, bool are_colorsets = false) {
     CK(ensure_cs_bitmaps(h));
+    hipEvent_t e0, e1;
+    CK(timing_begin(h, s, &e0, &e1));
     if (h->has_cs_bm) {
         if (!are_colorsets)
             hipLaunchKernelGGL(k_row_colorsets, dim3(grid_for((n + 255) / 256)), dim3(256), 0, s, d_rowidx, h->im.tcol, n, d_rowidx);  // row -> colour set, in place
@@ -2496,7 +2511,7 @@ static int launch_color_rows(bft_gpu* h, uint32_t* d_rowidx, uint64_t n, uint32_
     else
         hipLaunchKernelGGL(k_color_rows, dim3(grid_for((n + 255) / 256)), dim3(256), 0, s, d_rowidx, h->im.tcol, h->im.cs_off, h->im.cs_ids, h->im.cs_w, n, rowbytes, d_out);
     HIPCK(hipGetLastError());
-    return 0;
+    return timing_end(h, s, e0, e1);
 }
 
 // device-resident colour rows: presence bits + CEIL(nb_genomes/8)-byte bitmap row per k-mer, no synchronisation
@@ -2514,8 +2529,10 @@ extern "C" int bft_gpu_query_color_rows_dev(bft_gpu* h, const void* d_kmers, uin
     const bool direct = h->has_cs_bm;
     // rows of 16 bytes and up through the k-mer hash: lookup and rows in one launch (the scratch array stays unused)
     if (direct && rowbytes >= 16 && ((uintptr_t)d_rows & 15u) == 0 && h->im.kh_lines != nullptr && !h->opt_walk_hash && bft_kh_has_kernels(h->W, h->im.kh.S)) {
-        CK(bft_kh_color_rows(h->im, (const uint8_t*)d_kmers, n, h->B, (uint64_t*)d_present_bits, h->d_cs_bm.as<uint8_t>() + CS_BM_SLACK, (rowbytes + 3) & ~3u, rowbytes,
-                             (uint8_t*)d_rows, h->device, s));
+        CK(timed_launch(h, s, [&] {
+            return bft_kh_color_rows(h->im, (const uint8_t*)d_kmers, n, h->B, (uint64_t*)d_present_bits, h->d_cs_bm.as<uint8_t>() + CS_BM_SLACK, (rowbytes + 3) & ~3u, rowbytes,
+                                     (uint8_t*)d_rows, h->device, s);
+        }));
         return note_foreign_stream(h, s);
     }
     if (!direct) CK(ensure_table(h));
@@ -2618,27 +2635,40 @@ static int query_sequences_core(bft_gpu* h, const char* d_seqs, const uint64_t* 
     CK(bft_zero_async(h->sq_codes.as<uint64_t>() + n_cw, (BFT_MAX_W + 2) * 8, s));
     CK(bft_zero_async(h->sq_bad.as<uint32_t>() + n_cw, (BFT_MAX_W + 2) * 4, s));
     if (n_cw)
-        hipLaunchKernelGGL(k_seq_encode, dim3(grid_for((n_cw + 255) / 256)), dim3(256), 0, s, d_seqs, total_chars, n_cw, h->sq_codes.as<uint64_t>(),
-                           h->sq_bad.as<uint32_t>());
+        CK(timed_launch(h, s, [&] {
+            hipLaunchKernelGGL(k_seq_encode, dim3(grid_for((n_cw + 255) / 256)), dim3(256), 0, s, d_seqs, total_chars, n_cw, h->sq_codes.as<uint64_t>(),
+                               h->sq_bad.as<uint32_t>());
+            HIPCK(hipGetLastError());
+            return 0;
+        }));
     for (uint64_t a = 0; a < n_seqs; a += chunk) {
         const uint64_t ns = std::min(chunk, n_seqs - a);
         const uint64_t* soff = d_seq_off + a;
-        hipLaunchKernelGGL(k_seq_plan, dim3(grid_for((ns + 256) / 256)), dim3(256), 0, s, soff, ns, h->k, h->sq_npos.as<uint64_t>());
-        CK(bft_scan::exclusive_sum_ptr<uint64_t>(h->sq_npos.as<uint64_t>(), h->sq_poff.as<uint64_t>(), ns + 1, s, h->sq_tmp));
-        hipLaunchKernelGGL(k_seq_tiles, dim3(256 * 4), dim3(256), 0, s, h->sq_poff.as<uint64_t>(), (uint32_t)ns, h->sq_tile.as<uint32_t>());
+        CK(timed_launch(h, s, [&] {  // (the plan: positions per read, their offsets, the tile table)
+            hipLaunchKernelGGL(k_seq_plan, dim3(grid_for((ns + 256) / 256)), dim3(256), 0, s, soff, ns, h->k, h->sq_npos.as<uint64_t>());
+            CK(bft_scan::exclusive_sum_ptr<uint64_t>(h->sq_npos.as<uint64_t>(), h->sq_poff.as<uint64_t>(), ns + 1, s, h->sq_tmp));
+            hipLaunchKernelGGL(k_seq_tiles, dim3(256 * 4), dim3(256), 0, s, h->sq_poff.as<uint64_t>(), (uint32_t)ns, h->sq_tile.as<uint32_t>());
+            HIPCK(hipGetLastError());
+            return 0;
+        }));
         h->sq_units = total_chars / 256 + 2;  // (k-mer positions <= characters: the blocks the kernel can deal out)
-        switch (h->W) {
-        case 1: CK(launch_seq_walk_w<1>(h, (uint32_t)ns, canonical, soff, s)); break;
-        case 2: CK(launch_seq_walk_w<2>(h, (uint32_t)ns, canonical, soff, s)); break;
-        case 3: CK(launch_seq_walk_w<3>(h, (uint32_t)ns, canonical, soff, s)); break;
-        default: CK(launch_seq_walk_w<4>(h, (uint32_t)ns, canonical, soff, s)); break;
-        }
+        CK(timed_launch(h, s, [&] {
+            switch (h->W) {
+            case 1: return launch_seq_walk_w<1>(h, (uint32_t)ns, canonical, soff, s);
+            case 2: return launch_seq_walk_w<2>(h, (uint32_t)ns, canonical, soff, s);
+            case 3: return launch_seq_walk_w<3>(h, (uint32_t)ns, canonical, soff, s);
+            default: return launch_seq_walk_w<4>(h, (uint32_t)ns, canonical, soff, s);
+            }
+        }));
         claims_launched(h, s);
         const uint32_t win = std::min<uint32_t>(SEQ_TALLY_G, (G + 63u) & ~63u);  // counters per wavefront: all genomes up to 2048
-        hipLaunchKernelGGL(k_seq_tally, dim3((unsigned)std::min<uint64_t>((ns + SEQ_TALLY_WAVES - 1) / SEQ_TALLY_WAVES, 256ull * 16)), dim3(64 * SEQ_TALLY_WAVES),
-                           (size_t)SEQ_TALLY_WAVES * win * 4, s, h->sq_cs.as<uint32_t>(), h->sq_poff.as<uint64_t>(), (uint32_t)ns, h->im.cs_off, h->im.cs_ids, h->im.cs_w, G, rowbytes,
-                           threshold, win, d_rows + a * rowbytes);
-        HIPCK(hipGetLastError());
+        CK(timed_launch(h, s, [&] {
+            hipLaunchKernelGGL(k_seq_tally, dim3((unsigned)std::min<uint64_t>((ns + SEQ_TALLY_WAVES - 1) / SEQ_TALLY_WAVES, 256ull * 16)), dim3(64 * SEQ_TALLY_WAVES),
+                               (size_t)SEQ_TALLY_WAVES * win * 4, s, h->sq_cs.as<uint32_t>(), h->sq_poff.as<uint64_t>(), (uint32_t)ns, h->im.cs_off, h->im.cs_ids, h->im.cs_w, G,
+                               rowbytes, threshold, win, d_rows + a * rowbytes);
+            HIPCK(hipGetLastError());
+            return 0;
+        }));
     }
     return 0;
 }
@@ -3332,13 +3362,6 @@ static bool stream_capturing(hipStream_t s) {
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
     return st != hipStreamCaptureStatusNone;
-}
-template <class F>
-static int timed_launch(bft_gpu* h, hipStream_t s, F&& launch) {
-    hipEvent_t e0, e1;
-    CK(timing_begin(h, s, &e0, &e1));
-    CK(launch());
-    return timing_end(h, s, e0, e1);
 }
 static uint64_t pm_bytes(uint64_t m) {
     auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };

@@ -18,7 +18,9 @@
 //     uses array L & 1 and zeroes, tile by tile, what launch L - 1 left in the other one (nobody reads that any more); the workgroup whose claim
 //     is the launch's last puts the tile counter back to zero.  The host zeroes a block once, when it is new (DevBuf::tag counts the launches,
 //     DevBuf::tag2 remembers how many states the last one used).  A CAPTURED launch cannot take part (it runs again with the arguments it was
-//     captured with): it is bracketed by zeroing kernels (not memset nodes: bft_zero_async) and leaves the block zeroed;
+//     captured with): it is bracketed by zeroing kernels (not memset nodes: bft_zero_async) and leaves the block zeroed.  So a scratch block
+//     belongs to scans alone: anything else that writes it (another kernel's counter and states, a sort's scratch) must set DevBuf::tag = 0
+//     afterwards, or the next scan claims tiles from a stale counter -- and runs none of them, or waits forever on a state nobody writes;
 //   * the grand total, which nearly every caller wants on the host or behind the last offset, is written by the last tile (total_slot, tail)
 //     instead of by a launch of its own.
 #pragma once

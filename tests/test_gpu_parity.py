@@ -985,6 +985,22 @@ def test_resident_id_lists_through_the_kmer_hash(k, ngen):
             hb, hoff, hids = t.query_colors(q)  # the host entry point is the same path on staged chunks
             assert (hb == obits).all() and (hoff == ooff).all() and (hids == oids).all()
             assert t.footprint()["kmer_table"] <= 8
+    # back to the k-mer hash: a host call (the scan), a resident call (k_colors_kh), a host call again -- the two keep apart scratch blocks
+    t.set_option("kmer_hash", 1)
+    for call in ("host", "dev", "host"):
+        if call == "host":
+            hb, hoff, hids = t.query_colors(q)
+            assert (hb == obits).all() and (hoff == ooff).all() and (hids == oids).all(), call
+        else:
+            off.fill_(-1)
+            ids.fill_(-1)
+            need.fill_(-1)
+            t.query_colors_dev(dq.data_ptr(), n, bits.data_ptr(), off.data_ptr(), ids.data_ptr(), total, need.data_ptr(), stream)
+            torch.cuda.synchronize()
+            assert int(need.item()) == total
+            assert (bits.cpu().numpy()[: (n + 7) // 8] == obits).all()
+            assert (off.cpu().numpy().astype(np.uint64) == ooff).all()
+            assert (ids.cpu().numpy().astype(np.uint32) == oids).all()
     t.close()
 
 
