@@ -9,15 +9,19 @@ resident in every GPU's HBM, 1.25x10^8 = 10^9 / 8 batched presence queries per G
 every answer of every shard checked against ground truth; for N > 1 the image is built on rank 0 and replicated by one RCCL broadcast
 (or rebuilt per rank: --replicate rebuild) and the presence bitmaps are all_gathered over xGMI, the gather of step i overlapping the
 kernel of step i+1.  k = 27: the reference rejects k = 31 (k must be a multiple of 9, src/main.c:61-63), so 27 is the
-oracle-checkable stand-in the survey prescribes; the same index at k = 31 is measured beside it (`k31`, ground truth only).
-Secondary blocks at N = 1 (never `value`): configs[1] (10-genome index, 10^8 queries), the container walk without the k-mer hash,
-sequence queries, host buffers (PCIe), the footprint of the image against the .bft file, the CPU baseline.
+oracle-checkable stand-in the survey prescribes; with --full the same index at k = 31 is measured beside it (`k31`, ground truth only).
+
+A plain run does only what the headline needs: set-up (index, resident batch), warm-up, the timed steps, the ground-truth check of the
+answers of the last step, --dump-outputs when given, and the JSON line.  Everything else is measured with --full alone: the roofline
+and its counter passes, and at N = 1 the secondary blocks (never `value`): k = 31, configs[1] (10-genome index, 10^8 queries), the
+container walk without the k-mer hash, sequence queries, host buffers (PCIe), the footprint of the image against the .bft file, the
+CPU baseline, the insertion bench and the check of the N > 1 path in a child process.
 
 A "step" = one pass of the hot path (one bft_gpu_query_presence_dev call) over the whole resident batch, followed for N > 1 by the
 RCCL all_gather of the presence bitmaps.  Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
 `python bench.py --gpus N` without torchrun starts the N ranks itself (fresh child processes, before this process touches a GPU).
 
-roofline: `traffic` = HBM bytes per launch from hardware counters collected IN THIS RUN (tools/pmc_live.py: rocprofv3 --pmc passes in
+roofline (--full): `traffic` = HBM bytes per launch from hardware counters collected IN THIS RUN (tools/pmc_live.py: rocprofv3 --pmc passes in
 child processes after the timed region -- same library, same workload generator and seed as the timed batch --: FETCH_SIZE + WRITE_SIZE as
 counted, `traffic_counted`, plus a calibrated correction for the coalesced query stream the fetch counter tallies at half, `stream_correction`),
 `achieved` = traffic / mean kernel time (HIP events on the launch stream), `frac` = achieved / 8 TB/s -- an estimate resting on that
@@ -74,11 +78,14 @@ def parse():
     ap.add_argument("--genome-len", type=int, default=2_000_000)
     ap.add_argument("--snp-rate", type=float, default=0.01)
     ap.add_argument("--queries", type=int, default=125_000_000, help="queries per GPU per step")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the roofline (with counter passes), and at N=1 the secondary blocks "
+                         "and the CPU baseline; the options below that name them apply to --full runs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=0, help="queries timed on the CPU baseline (0 = auto)")
-    ap.add_argument("--no-secondary", action="store_true", help="N=1: only the headline, the roofline and the CPU baseline")
-    ap.add_argument("--measure-ref-scan", action="store_true", help="also run the oracle's counting mode (bytes the reference's scan dereferences per query)")
-    ap.add_argument("--no-pmc", action="store_true", help="do not run the rocprofv3 counter passes (roofline from profiles/ if not stale)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full at N=1: only the headline, the roofline and the CPU baseline")
+    ap.add_argument("--measure-ref-scan", action="store_true", help="with --full: also run the oracle's counting mode (bytes the reference's scan dereferences per query)")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: do not run the rocprofv3 counter passes (roofline from profiles/ if not stale)")
     ap.add_argument("--force-dist", action="store_true", help="initialise RCCL and run the bitmap all_gather even with one rank (path check)")
     ap.add_argument("--replicate", choices=["rebuild", "broadcast"], default="broadcast",
                     help="N>1, how every rank gets the trie: rank 0 builds it and one RCCL broadcast replicates the image (default), "
@@ -354,7 +361,6 @@ def main():
         return
 
     value = nq * world * args.steps / elapsed / 1e6
-    fp = bft.footprint()
     out = {
         "metric": "M k-mers/sec queried (presenceNode)",
         "value": round(value, 3),
@@ -388,7 +394,7 @@ def main():
                   **{k_: round(v, 2) for k_, v in build_times.items() if not k_.startswith("_")}},
     }
     avg_ms = kern_ms / max(1, launches)
-    secondary = world == 1 and not args.no_secondary
+    secondary = args.full and world == 1 and not args.no_secondary
 
     # ---- secondary: the host-buffer entry point (H2D + kernel + D2H through bft_gpu_query_presence); never `value` ----
     if secondary:
@@ -405,7 +411,8 @@ def main():
 
     # ---- footprint: HBM bytes per part of the image against the .bft file of the same index (the reference's own measure of size) ----
     bft_path = None
-    if world == 1:
+    if args.full and world == 1:
+        fp = bft.footprint()
         try:
             shm = "/dev/shm" if os.path.isdir("/dev/shm") else tempfile.gettempdir()
             bft_path = os.path.join(shm, f"bench_{os.getpid()}.bft")
@@ -444,7 +451,7 @@ def main():
     # read_BFT_Root and queried with its isKmerPresent loop on all host cores; a counting-mode pass gives the bytes the
     # reference's scan dereferences per query (SURVEY 8d's S) ----
     ref_scan = None
-    if world == 1 and not args.no_cpu_baseline and bft_path and os.path.exists(bft_path):
+    if args.full and world == 1 and not args.no_cpu_baseline and bft_path and os.path.exists(bft_path):
         try:
             from oracle import oracle as O
             # the cores this process may run on: the affinity mask, cut by the cgroup's CPU quota when there is one
@@ -505,18 +512,19 @@ def main():
 
     # ---- roofline of the timed kernel: hardware counters of THIS library on THIS workload ----
     std = (genomes, args.genome_len, args.snp_rate, k) == (100, 2_000_000, 0.01, 27)
-    if std:
-        pmc, live = pmc_for("cfg4", nq, B, allow_live=(world == 1 and not args.no_pmc))
-    else:
-        pmc, live = {"error": "non-standard workload: no counter passes"}, False
-    out["roofline"] = roofline_block(pmc, nq, avg_ms, launches, "k_query_kh" if build_times.get("kmer_hash_lines") else "k_query", B, live)
-    if ref_scan is None and std:  # recorded by an earlier run of this bench with --measure-ref-scan (the oracle's counting mode on the same index)
-        rec = load_profile_json("r03/ref_scan_bytes_config4.json")
-        if rec:
-            ref_scan = rec.get("total")
-            out["reference_scan_bytes_per_query"] = dict(rec, source="profiles/r03/ref_scan_bytes_config4.json")
-    if ref_scan and out["roofline"].get("hbm_bytes_per_query"):
-        out["roofline"]["ref_scan_bytes_avoided"] = round(ref_scan / out["roofline"]["hbm_bytes_per_query"], 2)
+    if args.full:
+        if std:
+            pmc, live = pmc_for("cfg4", nq, B, allow_live=(world == 1 and not args.no_pmc))
+        else:
+            pmc, live = {"error": "non-standard workload: no counter passes"}, False
+        out["roofline"] = roofline_block(pmc, nq, avg_ms, launches, "k_query_kh" if build_times.get("kmer_hash_lines") else "k_query", B, live)
+        if ref_scan is None and std:  # recorded by an earlier run of this bench with --measure-ref-scan (the oracle's counting mode on the same index)
+            rec = load_profile_json("r03/ref_scan_bytes_config4.json")
+            if rec:
+                ref_scan = rec.get("total")
+                out["reference_scan_bytes_per_query"] = dict(rec, source="profiles/r03/ref_scan_bytes_config4.json")
+        if ref_scan and out["roofline"].get("hbm_bytes_per_query"):
+            out["roofline"]["ref_scan_bytes_avoided"] = round(ref_scan / out["roofline"]["hbm_bytes_per_query"], 2)
 
     if secondary:
         # ---- the same index through the container walk, three ways, each with its own counters (bft_gpu_set_option names in `options`):
@@ -670,11 +678,10 @@ def main():
 
     # ---- the N > 1 path with one rank, in a child process (this one never initialised RCCL): process group over RCCL, the image blob packed and
     # broadcast (always_copy: the rank unpacks the received blob instead of keeping its own handle), presence bitmaps all_gathered with the overlap
-    # pipeline, gathered shard == own bits, every answer checked -- so that the code an 8-GPU run takes is executed in every bench run ----
+    # pipeline, gathered shard == own bits, every answer checked -- so that the code an 8-GPU run takes is executed in every --full run ----
     if secondary and not args.force_dist:
         try:
-            cmd = [sys.executable, os.path.abspath(__file__), "--force-dist", "--steps", "3", "--warmup", "1", "--genomes", "10", "--queries", "20000000",
-                   "--no-secondary", "--no-cpu-baseline", "--no-pmc"]
+            cmd = [sys.executable, os.path.abspath(__file__), "--force-dist", "--steps", "3", "--warmup", "1", "--genomes", "10", "--queries", "20000000"]
             env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(29600 + os.getpid() % 300), RANK="0", LOCAL_RANK="0", WORLD_SIZE="1",
                        HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
             t0 = time.perf_counter()

@@ -58,3 +58,14 @@ def test_committed_counter_file_names_its_sources():
     for wl in ("cfg4", "cfg4k31", "cfg2"):
         assert "lib_source_hash" in d[wl] and d[wl]["queries_per_launch"] > 0 and "hbm_bytes_per_query" in d[wl]
         assert 60 < d[wl]["hbm_bytes_per_query"] < 100 and 1.0 < d[wl]["l2_misses_per_query"] < 1.3
+
+
+def test_full_is_opt_in(monkeypatch):
+    """a plain bench run measures the headline alone; everything beside it is asked for with --full"""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert a.full is False and (a.steps, a.warmup) == (3, 1)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-pmc"])
+    a = bench.parse()
+    assert a.full is True and a.no_pmc is True

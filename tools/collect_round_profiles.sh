@@ -5,8 +5,8 @@
 set -u
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/${1:-final}; mkdir -p "$OUT"
 strip() { grep -v "amdgpu.ids" ; }
-python3 bench.py --steps 20 --warmup 5 2> "$OUT/bench.err" | strip > "$OUT/bench.json"
-( cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/bench_trace" -o t -- python3 "$ROOT/bench.py" --steps 20 --warmup 5 --no-secondary --no-cpu-baseline --no-pmc > "$OUT/bench_under_rocprof.json" 2> "$OUT/bench_under_rocprof.err" )
+python3 bench.py --full --steps 20 --warmup 5 2> "$OUT/bench.err" | strip > "$OUT/bench.json"
+( cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/bench_trace" -o t -- python3 "$ROOT/bench.py" --full --steps 20 --warmup 5 --no-secondary --no-cpu-baseline --no-pmc > "$OUT/bench_under_rocprof.json" 2> "$OUT/bench_under_rocprof.err" )
 python3 profiles/summarize_rocpd.py "$(find "$OUT/bench_trace" -name '*.db' | head -1)" > "$OUT/bench_kernel_stats.txt" 2>&1
 rm -rf "$OUT/bench_trace"
 python3 - "$OUT" <<'PY'

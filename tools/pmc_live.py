@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Hardware counters of the query kernel of the library in this tree, collected NOW: `rocprofv3 --pmc` passes (one counter set per
 pass, --kernel-trace only, separate child processes) of tools/pmc_query.py on a BASELINE workload, parsed into per-launch and
-per-query figures.  bench.py calls collect() after its timed region (the counters then describe the very library that was timed);
+per-query figures.  bench.py --full calls collect() after its timed region (the counters then describe the very library that was timed);
 run as a script it writes the JSON under profiles/ (the fallback bench.py reads, guarded by the source hash, when no profiler is
 available).
 
