@@ -370,6 +370,25 @@ class BFT:
                                                   C.c_void_p(stream or 0)))
         return BFT(self.k, device=self.device, _handle=h), int(absent.value)
 
+    def simple_paths(self, min_shared=0):
+        """extract_simple_paths_to_disk / extract_simple_core_paths_to_disk (reference snippets.h, src/snippets.c:115-603) on the GPU: the simple
+        (non-branching) paths of the index as ASCII strings, in ascending row of their first k-mer.  min_shared = t: only k-mers of t genomes
+        or more, joined where they share t or more (0: plain simple paths; bft_gpu_simple_paths defines the paths)."""
+        n_paths, n_chars = C.c_uint64(), C.c_uint64()
+        _lib.check(self._lib.bft_gpu_simple_paths(self._h, int(min_shared), None, None, 0, 0, C.byref(n_paths), C.byref(n_chars)))
+        offsets = np.zeros(n_paths.value + 1, dtype=np.uint64)
+        seqs = np.zeros(max(1, n_chars.value), dtype=np.uint8)
+        _lib.check(self._lib.bft_gpu_simple_paths(self._h, int(min_shared), offsets.ctypes.data, seqs.ctypes.data, n_paths.value, n_chars.value,
+                                                  C.byref(n_paths), C.byref(n_chars)))
+        text = seqs[:n_chars.value].tobytes().decode()
+        return [text[int(offsets[i]):int(offsets[i + 1])] for i in range(n_paths.value)]
+
+    def simple_paths_dev(self, d_offsets_ptr, d_seqs_ptr, paths_cap, chars_cap, d_counts_ptr, min_shared=0, stream=None):
+        """Device-resident simple paths (bft_gpu_simple_paths_dev): {n_paths, n_chars, longest} (3 uint64) at d_counts_ptr always, the offsets
+        entries j <= paths_cap and the characters below chars_cap into the buffers that are not 0; no synchronisation."""
+        _lib.check(self._lib.bft_gpu_simple_paths_dev(self._h, int(min_shared), C.c_void_p(d_offsets_ptr or 0), C.c_void_p(d_seqs_ptr or 0), paths_cap,
+                                                      chars_cap, C.c_void_p(d_counts_ptr), C.c_void_p(stream or 0)))
+
     def genome_name(self, id_genome):
         """The name of genome id_genome (the reference's filenames[id_genome]; "genome_<id>" for an id that was never named)."""
         buf = C.create_string_buffer(4096)

@@ -12,6 +12,7 @@
 #include <string.h>
 
 #include "../../include/bft/bft.h"
+#include "../../include/bft/snippets.h"
 
 #define DIE(...) do { fprintf(stderr, __VA_ARGS__); exit(EXIT_FAILURE); } while (0)
 #define NOT_NULL(p, where) do { if ((p) == NULL) DIE("%s: NULL pointer\n", where); } while (0)
@@ -703,4 +704,43 @@ BFT* load_BFT(char* filename) {
         push_name(bft, name);
     }
     return bft;
+}
+
+/* ---------------------------------------------------------------- simple paths (<bft/snippets.h>) */
+
+/* src/snippets.c:306-344 and :563-603 without the walk: the file is opened first (the reference's ERROR on failure), then one
+ * bft_gpu_simple_paths call counts the paths and a second one fetches them; they are written one per line and the longest is reported. */
+static void simple_paths_to_disk(BFT* bft, uint32_t t, const char* filename, const char* open_error, const char* what, const char* where) {
+    FILE* file = fopen(filename, "w");
+    if (file == NULL) DIE("%s", open_error);
+    uint64_t n_paths = 0, n_chars = 0;
+    ck(bft_gpu_simple_paths(bft->gpu, t, NULL, NULL, 0, 0, &n_paths, &n_chars), where);
+    uint64_t* offsets = malloc((size_t)(n_paths + 1) * sizeof(uint64_t));
+    char* seqs = malloc((size_t)(n_chars ? n_chars : 1));
+    if (offsets == NULL || seqs == NULL) DIE("%s: out of memory\n", where);
+    ck(bft_gpu_simple_paths(bft->gpu, t, offsets, seqs, n_paths, n_chars, &n_paths, &n_chars), where);
+    uint64_t longest = 0;
+    for (uint64_t i = 0; i < n_paths; i++) {
+        const uint64_t len = offsets[i + 1] - offsets[i];
+        if (len > longest) longest = len;
+        if (fwrite(seqs + offsets[i], 1, (size_t)len, file) != len || fputc('\n', file) == EOF) DIE("%s: failed to write the output file.\n", where);
+    }
+    if (fclose(file) != 0) DIE("%s: failed to write the output file.\n", where);
+    free(offsets);
+    free(seqs);
+    printf("Longest simple %spath has %d nuc.\n", what, (int)longest);
+}
+
+void extract_simple_paths_to_disk(BFT* graph, char* filename_output) {
+    NOT_NULL(graph, "extract_simple_paths_to_disk()");
+    NOT_NULL(filename_output, "extract_simple_paths_to_disk()");
+    simple_paths_to_disk(graph, 0, filename_output, "extract_simple_paths_to_disk(): failed to create output file.\n", "", "extract_simple_paths_to_disk()");
+}
+
+void extract_simple_core_paths_to_disk(BFT* graph, double core_ratio, char* filename_output) {
+    NOT_NULL(graph, "extract_simple_core_paths_to_disk()");
+    NOT_NULL(filename_output, "extract_simple_core_paths_to_disk()");
+    const int t = (int)(core_ratio * graph->nb_genomes); /* (truncated, as src/snippets.c:366; a negative threshold holds for every k-mer) */
+    simple_paths_to_disk(graph, t > 0 ? (uint32_t)t : 0u, filename_output, "extract_simple_core_paths_to_disk(): failed to create/open output file.\n", "core ",
+                         "extract_simple_core_paths_to_disk()");
 }

@@ -31,6 +31,7 @@
 #include "bft_image.h"
 #include "bft_index.h"
 #include "bft_kh.h"
+#include "bft_paths.h"
 #include "bft_prefix.h"
 #include "bft_scan.h"
 #include "bft_sort.h"
@@ -395,6 +396,11 @@ struct bft_gpu {
     hipStream_t pm_stream = nullptr;
     hipEvent_t pm_ev = nullptr;    // where the last use of that scratch ends
     bool pm_used = false;
+    DevBuf sp_buf, sp_tmp;         // scratch of the simple paths (BftSpScratch, bft_paths.h) and their scans' temporary (grown, never shrunk)
+    uint64_t sp_m = 0;             // rows sp_buf has room for
+    hipStream_t sp_stream = nullptr;
+    hipEvent_t sp_ev = nullptr;    // where the last use of that scratch ends
+    bool sp_used = false;
     bool inject_build_failure = false;  // test hook: the next bft_gpu_build fails right before its commit point (one shot)
     bool opt_build_stages = false;      // "build_stages": the next builds record GPU time and bytes per stage (bft_gpu_build_stages)
     struct Stage { std::string name; double ms, bytes; };
@@ -553,6 +559,7 @@ extern "C" void bft_gpu_free(bft_gpu* h) {
     h->ext.clear();
     if (h->qc_ev) { (void)hipEventDestroy(h->qc_ev); h->qc_ev = nullptr; }
     if (h->pm_ev) { (void)hipEventDestroy(h->pm_ev); h->pm_ev = nullptr; }
+    if (h->sp_ev) { (void)hipEventDestroy(h->sp_ev); h->sp_ev = nullptr; }
     const hipStream_t s = h->stream;
     if (s) (void)hipStreamSynchronize(s);
     if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); h->stream2 = nullptr; }
@@ -1440,10 +1447,10 @@ static int split_dedupe_w1(bft_gpu* h, const uint64_t* src_k, const uint32_t* sr
 // "build_stages": the marks of one bft_gpu_build (bft_stage) become the handle's stage table when the build returns, however it returns
 struct StageScope {
     bft_gpu* h;
-    explicit StageScope(bft_gpu* hh) : h(hh) {
+    explicit StageScope(bft_gpu* hh, hipStream_t s = nullptr) : h(hh) {  // (s: the stream the first stage runs on, when not the handle's)
         t_stages_on = h->opt_build_stages;
         t_stage_marks.clear();
-        if (t_stages_on) bft_stage("start", 0, h->stream);
+        if (t_stages_on) bft_stage("start", 0, s ? s : h->stream);
     }
     ~StageScope() {
         if (!t_stages_on) return;
@@ -3491,6 +3498,160 @@ extern "C" int bft_gpu_query_prefixes(bft_gpu* h, const uint8_t* prefixes, const
     HIPCK(hipMemcpyAsync(offsets, doff.p, (n + 1) * 8, hipMemcpyDeviceToHost, s));
     HIPCK(hipStreamSynchronize(s));
     pm_release(h, s);
+    return BFT_GPU_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// simple paths (extract_simple_paths_to_disk / extract_simple_core_paths_to_disk, reference snippets.h, src/snippets.c:115-603): degrees,
+// links, pointer jumping and spelling over the sorted table (bft_paths.hip)
+// ------------------------------------------------------------------------------------------------
+static uint64_t sp_bytes(uint64_t m, int sb) {
+    auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
+    return al(((1ull << sb) + 1) * 4) + 3 * al(m * 4) + al(m) + 2 * al(m * 16) + al(m * 8);
+}
+// The handle's scratch for an index of n rows on stream s: its own block, shared with no other query; a call on another stream first waits for
+// the last use (an event of the handle's own).
+static int sp_scratch(bft_gpu* h, uint64_t n, hipStream_t s, BftSpScratch* p) {
+    if (h->sp_used && h->sp_stream != s) {
+        HIPCK(h->sp_ev ? hipEventSynchronize(h->sp_ev) : hipDeviceSynchronize());
+        h->sp_used = false;
+    }
+    const int sb = bft_sp_bucket_bits(h->k);
+    const size_t tb = bft_scan::scratch_bytes(n + 1);
+    if (h->sp_m < n || h->sp_buf.bytes < sp_bytes(h->sp_m, sb) || h->sp_tmp.bytes < tb) {
+        if (h->sp_used) HIPCK(hipStreamSynchronize(s));
+        if (h->sp_m < n || h->sp_buf.bytes < sp_bytes(h->sp_m, sb)) {
+            const uint64_t m = std::max(n, h->sp_m);
+            CK(h->sp_buf.alloc(sp_bytes(m, sb)));
+            h->sp_m = m;
+        }
+        if (h->sp_tmp.bytes < tb) CK(h->sp_tmp.alloc(tb));
+    }
+    const uint64_t m = h->sp_m;
+    auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
+    uint8_t* q = h->sp_buf.as<uint8_t>();
+    p->sb = sb;
+    p->start = (uint32_t*)q; q += al(((1ull << sb) + 1) * 4);
+    p->succ = (uint32_t*)q; q += al(m * 4);
+    p->indeg = (uint32_t*)q; q += al(m * 4);
+    p->pred = (uint32_t*)q; q += al(m * 4);
+    p->flags = q; q += al(m);
+    p->st[0] = (uint4*)q; q += al(m * 16);
+    p->st[1] = (uint4*)q; q += al(m * 16);
+    p->choff = (uint64_t*)q;
+    h->sp_used = true;
+    h->sp_stream = s;
+    return 0;
+}
+static void sp_release(bft_gpu* h, hipStream_t s) {
+    if (!h->sp_ev && hipEventCreateWithFlags(&h->sp_ev, hipEventDisableTiming) != hipSuccess) { h->sp_ev = nullptr; (void)hipGetLastError(); }
+    if (h->sp_ev && hipEventRecord(h->sp_ev, s) != hipSuccess) (void)hipGetLastError();
+}
+// Degrees, links, ranks, lengths and both scans on stream s: d_counts = {n_paths, n_chars, longest} (24 bytes, device); *fin: the jumps' last buffer.
+// With "build_stages" on, every step is a stage (bft_gpu_build_stages), its bytes those its algorithm reads and writes.
+static int sp_count(bft_gpu* h, uint32_t t, hipStream_t s, unsigned long long* d_counts, const BftSpScratch& p, int* fin) {
+    const uint64_t n = h->n_kmers;
+    const int W = h->W, k = h->k;
+    const uint64_t* tk = h->d_tk.as<uint64_t>();
+    const double nd = (double)n, rowb = 8.0 * W;
+    CK(bft_zero_async(d_counts, 24, s));
+    CK(bft_zero_async(p.indeg, n * 4, s));
+    CK(timed_launch(h, s, [&] { return bft_sp_buckets(W, tk, n, k, p, s); }));
+    bft_stage("simple paths: buckets of the table", (double)((1ull << p.sb) + 1) * 4, s);
+    CK(timed_launch(h, s, [&] { return bft_sp_degrees(W, tk, n, k, p, s); }));
+    bft_stage("simple paths: degrees and successors", nd * (2 * rowb + 4 + 4 + 12), s);
+    CK(timed_launch(h, s, [&] { return bft_sp_links(n, t, h->d_tcol.as<uint32_t>(), h->d_cs_off.as<uint32_t>(), h->d_cs_ids.p, h->cs_w, p, s); }));
+    bft_stage("simple paths: nodes and edges", nd * (12 + 8 + (t ? 8 : 0) + 1 + 16), s);
+    int cur = 0, rounds = 0;  // (ceil(log2(n + 1)) of them: no chain is longer than n, nothing is read back)
+    for (uint64_t span = 1; span < n + 1; span <<= 1, cur ^= 1, rounds++) CK(timed_launch(h, s, [&] { return bft_sp_jump(n, p, cur, s); }));
+    *fin = cur;
+    bft_stage("simple paths: pointer jumping", nd * 48 * rounds, s);
+    CK(timed_launch(h, s, [&] { return bft_sp_ends(n, k, p, cur, d_counts + 2, s); }));
+    bft_stage("simple paths: heads, tails, lengths", nd * (16 + 1 + 4 + 8 + 4), s);
+    const uint2* hd = bft_sp_hd(p, cur);
+    CK(timed_launch(h, s, [&] { return bft_scan::exclusive_sum<uint32_t>(BftSpHead{hd, n}, p.pred, n, s, h->sp_tmp, d_counts, false); }));
+    CK(timed_launch(h, s, [&] { return bft_scan::exclusive_sum<uint64_t>(BftSpHeadLen{hd, p.indeg, n}, p.choff, n, s, h->sp_tmp, d_counts + 1, false); }));
+    bft_stage("simple paths: two scans (paths, characters)", nd * (8 + 4 + 8 + 4 + 8), s);
+    return 0;
+}
+// offsets (paths_cap + 1 entries at most) and characters (chars_cap at most) of the paths sp_count counted
+static int sp_emit(bft_gpu* h, const BftSpScratch& p, int fin, uint64_t* d_offsets, uint64_t paths_cap, char* d_seqs, uint64_t chars_cap,
+                   const unsigned long long* d_counts, hipStream_t s) {
+    const uint64_t n = h->n_kmers;
+    if (d_offsets) CK(timed_launch(h, s, [&] { return bft_sp_offsets(n, p, fin, d_offsets, paths_cap, d_counts, s); }));
+    bft_stage("simple paths: offsets", (double)n * 8, s);
+    if (d_seqs) CK(timed_launch(h, s, [&] { return bft_sp_spell(h->W, h->d_tk.as<uint64_t>(), n, h->k, p, fin, d_seqs, chars_cap, s); }));
+    bft_stage("simple paths: spelling", (double)n * (8.0 * h->W + 8 + 8 + 1), s);
+    return 0;
+}
+static int sp_prepare(bft_gpu* h) {
+    CK(ensure_built(h));  // ("compact_table": the sorted table comes back, as for rows and prefixes)
+    if (h->n_kmers >= (1ull << 31)) return fail(BFT_GPU_E_LIMIT, "simple paths: at most 2^31 - 1 k-mers");
+    return 0;
+}
+
+extern "C" int bft_gpu_simple_paths_dev(bft_gpu* h, uint32_t min_shared, void* d_offsets, void* d_seqs, uint64_t paths_cap, uint64_t chars_cap, void* d_counts,
+                                        void* hip_stream) {
+    if (!h || !d_counts) return fail(BFT_GPU_E_ARG, "NULL argument");
+    ENTER(h);
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
+    if (stream_capturing(s)) return fail(BFT_GPU_E_ARG, "simple paths recorded into a graph: not supported (the table may have to come back, scratch may grow)");
+    CK(sp_prepare(h));
+    if (h->n_kmers == 0) {
+        CK(bft_zero_async(d_counts, 24, s));
+        if (d_offsets) CK(bft_zero_async(d_offsets, 8, s));
+        return note_foreign_stream(h, s);
+    }
+    BftSpScratch p;
+    CK(sp_scratch(h, h->n_kmers, s, &p));
+    {
+        StageScope stage_scope(h, s);
+        int fin = 0;
+        CK(sp_count(h, min_shared, s, (unsigned long long*)d_counts, p, &fin));
+        CK(sp_emit(h, p, fin, (uint64_t*)d_offsets, paths_cap, (char*)d_seqs, chars_cap, (const unsigned long long*)d_counts, s));
+    }
+    sp_release(h, s);
+    return note_foreign_stream(h, s);
+}
+
+// The host-buffer form: the paths are counted on the device, and the outputs filled only when the caps hold them all.
+extern "C" int bft_gpu_simple_paths(bft_gpu* h, uint32_t min_shared, uint64_t* offsets, char* seqs, uint64_t paths_cap, uint64_t chars_cap, uint64_t* n_paths,
+                                    uint64_t* n_chars) {
+    if (!h || !n_paths || !n_chars) return fail(BFT_GPU_E_ARG, "NULL argument");
+    ENTER(h);
+    CK(sp_prepare(h));
+    *n_paths = *n_chars = 0;
+    if (h->n_kmers == 0) {
+        if (offsets) offsets[0] = 0;
+        return BFT_GPU_OK;
+    }
+    const hipStream_t s = h->stream;
+    DevBuf dcnt;
+    CK(dcnt.alloc(24));
+    BftSpScratch p;
+    CK(sp_scratch(h, h->n_kmers, s, &p));
+    StageScope stage_scope(h);
+    int fin = 0;
+    CK(sp_count(h, min_shared, s, dcnt.as<unsigned long long>(), p, &fin));
+    unsigned long long cnt[3] = {0, 0, 0};
+    HIPCK(hipMemcpyAsync(cnt, dcnt.p, 24, hipMemcpyDeviceToHost, s));
+    HIPCK(hipStreamSynchronize(s));
+    *n_paths = cnt[0];
+    *n_chars = cnt[1];
+    if ((offsets && cnt[0] > paths_cap) || (seqs && cnt[1] > chars_cap)) {
+        sp_release(h, s);
+        return fail(BFT_GPU_E_NOSPACE, "simple path buffers too small");
+    }
+    if (offsets || seqs) {
+        DevBuf doff, dseq;
+        if (offsets) CK(doff.alloc((cnt[0] + 1) * 8));
+        if (seqs && cnt[1]) CK(dseq.alloc(cnt[1]));
+        CK(sp_emit(h, p, fin, offsets ? doff.as<uint64_t>() : nullptr, cnt[0], seqs ? dseq.as<char>() : nullptr, cnt[1], dcnt.as<unsigned long long>(), s));
+        if (offsets) HIPCK(hipMemcpyAsync(offsets, doff.p, (cnt[0] + 1) * 8, hipMemcpyDeviceToHost, s));
+        if (seqs && cnt[1]) HIPCK(hipMemcpyAsync(seqs, dseq.p, cnt[1], hipMemcpyDeviceToHost, s));
+        HIPCK(hipStreamSynchronize(s));
+    }
+    sp_release(h, s);
     return BFT_GPU_OK;
 }
 

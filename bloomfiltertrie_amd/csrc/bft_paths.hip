@@ -1,0 +1,279 @@
+// bft_paths.hip -- simple paths (unitigs) of the index (extract_simple_paths / extract_simple_core_paths, reference snippets.h, src/snippets.c:115-603)
+// over the sorted T-form table tk (one row per stored k-mer, rows in the bft_gpu_extract order):
+//   k_sp_buckets  first row of every bucket of the top bits of the T-form: a lower bound in tk starts inside one bucket (about 40 rows on the
+//                 config-3 index) instead of the whole table
+//   k_sp_degrees  one lane per row u.  The four successors x[1..k-1]+N of u differ in the last nucleotide only, which sits in the two lowest bits of
+//                 the T-form (k % 9 != 0) or in bits 2-3 of the last block (k % 9 == 0, the block is rotated): they lie in one interval of at most
+//                 16 rows, found by ONE lower bound.  Out-degree and the successor's row come from that interval; in-degrees and predecessors
+//                 are the same relation read backwards, so each successor found gets an atomic increment and u's row -- no second lookup
+//   k_sp_links    nodes (in <= 1, out <= 1, colour set of t genomes or more) and edges (u -> v: v is u's only successor, u is v's only
+//                 predecessor, both nodes, |C(u) & C(v)| >= t; the sorted id lists are merged, equal colour-set ids skip it), each decided
+//                 at both of its ends by the same predicate; the first state of the jumps
+//   k_sp_jump     ceil(log2(n + 1)) rounds of pointer jumping backwards along the edges.  A lane's state covers a window of 2^r nodes ending at
+//                 it: the node before the window, the window's length (steps to the head once the head is in it), the smallest row in the
+//                 window and the steps back to it.  A chain ends with {head, distance}; a cycle, which has no head, with {smallest row of
+//                 the cycle, distance from it}: the cycle is cut before its smallest row without a second pass
+//   k_sp_ends     {head, distance} per node; the tail (no edge out, or the edge back to the cycle's smallest row) writes its path's length at
+//                 the head; the longest path (an atomic from a wavefront only when it beats the counter's current value)
+//   (two scans: paths numbered by their heads in row order, BftSpHead; characters placed, BftSpHeadLen)
+//   k_sp_offsets  offsets[path] from the heads
+//   k_sp_spell    a head writes its k nucleotides, every other node its last one at offset + k - 1 + distance
+// No kernel needs LDS or scratch memory.
+#include <type_traits>
+
+#include "bft_dev.h"
+#include "bft_paths.h"
+#include "bft_walk.h"
+
+namespace {
+
+constexpr int SP_THREADS = 256;
+
+// the top sb bits of a T-form (2k bits in W words, word 0 most significant)
+template <int W>
+__device__ __forceinline__ uint32_t sp_top(const uint64_t* t, int k, int sb) {
+    const int tb = 2 * k - 64 * (W - 1);  // bits in word 0
+    if (tb >= sb) return (uint32_t)(t[0] >> (tb - sb));
+    uint64_t w1 = 0;
+#pragma unroll
+    for (int w = 1; w < W; w++)
+        if (w == 1) w1 = t[1];
+    return (uint32_t)((t[0] << (sb - tb)) | (w1 >> (64 - (sb - tb))));
+}
+
+template <int W>
+__global__ __launch_bounds__(SP_THREADS) void k_sp_buckets(const uint64_t* __restrict__ tk, uint32_t n, int k, int sb, uint32_t* __restrict__ start) {
+    const uint32_t nb = 1u << sb;
+    for (uint64_t b = blockIdx.x * (uint64_t)SP_THREADS + threadIdx.x; b <= nb; b += (uint64_t)gridDim.x * SP_THREADS) {
+        uint32_t lo = 0, hi = n;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            uint64_t r[W];
+            bft_load_row<W>(tk + (uint64_t)mid * W, r);
+            if (sp_top<W>(r, k, sb) < (uint32_t)b) lo = mid + 1;
+            else hi = mid;
+        }
+        start[b] = lo;
+    }
+}
+
+template <int W>
+__global__ __launch_bounds__(SP_THREADS) void k_sp_degrees(const uint64_t* __restrict__ tk, uint32_t n, int k, int sb, const uint32_t* __restrict__ start,
+                                                           uint32_t* __restrict__ succ, uint32_t* __restrict__ indeg, uint32_t* __restrict__ pred) {
+    const int vo = (k % 9) ? 0 : 2;  // where the last nucleotide sits in the T-form's last word
+    const uint64_t wild = 3ull << vo;
+    for (uint64_t u = blockIdx.x * (uint64_t)SP_THREADS + threadIdx.x; u < n; u += (uint64_t)gridDim.x * SP_THREADS) {
+        uint64_t t[W], x[W], y[W];
+        bft_load_row<W>(tk + u * W, t);
+        bft_x_from_tform<W>(t, k, x);
+        // the successor with nucleotide 0 last: drop the first nucleotide (the bits above 2k are zero, so the new last one is A)
+#pragma unroll
+        for (int w = 0; w < W; w++) y[w] = (x[w] >> 2) | (w + 1 < W ? x[w + 1] << 62 : 0ull);
+        bft_tform_from_x<W>(y, k, t);
+        const uint32_t b = sp_top<W>(t, k, sb), lo = start[b], hi = start[b + 1];
+        uint32_t r = lo + bft_rows_lower_bound<W>(tk + (uint64_t)lo * W, hi - lo, t);
+        uint32_t cnt = 0, v = BFT_SP_NONE;
+        for (; r < n; r++) {
+            uint64_t c[W];
+            bft_load_row<W>(tk + (uint64_t)r * W, c);
+            bool same = true;
+#pragma unroll
+            for (int w = 0; w < W - 1; w++) same = same && c[w] == t[w];
+            if (!same || c[W - 1] > (t[W - 1] | wild)) break;  // (rows at or after t: past the interval)
+            if ((c[W - 1] & ~wild) != t[W - 1]) continue;
+            cnt++;
+            v = r;
+            atomicAdd(&indeg[r], 1u);
+            pred[r] = (uint32_t)u;
+        }
+        succ[u] = cnt == 0 ? BFT_SP_NONE : cnt == 1 ? v : BFT_SP_MANY;
+    }
+}
+
+__device__ __forceinline__ uint32_t sp_set_size(const uint32_t* cs_off, uint32_t cs) { return cs_off[cs + 1] - cs_off[cs]; }
+
+__device__ __forceinline__ bool sp_node(uint32_t i, uint32_t t, const uint32_t* succ, const uint32_t* indeg, const uint32_t* tcol, const uint32_t* cs_off) {
+    return indeg[i] <= 1u && succ[i] != BFT_SP_MANY && (t == 0u || sp_set_size(cs_off, tcol[i]) >= t);
+}
+
+// |C(a) & C(b)| >= t for two sorted id lists
+__device__ bool sp_shared(uint32_t ca, uint32_t cb, uint32_t t, const uint32_t* cs_off, const void* cs_ids, uint32_t cs_w) {
+    if (t == 0u || ca == cb) return true;  // (a node's own set has t ids or more)
+    uint32_t i = cs_off[ca], ie = cs_off[ca + 1], j = cs_off[cb], je = cs_off[cb + 1], got = 0;
+    while (i < ie && j < je) {
+        if (got + min(ie - i, je - j) < t) return false;
+        const uint32_t a = bft_cs_id_at(cs_ids, cs_w, i), b = bft_cs_id_at(cs_ids, cs_w, j);
+        if (a == b) {
+            if (++got >= t) return true;
+            i++;
+            j++;
+        } else if (a < b) i++;
+        else j++;
+    }
+    return got >= t;
+}
+
+__global__ __launch_bounds__(SP_THREADS) void k_sp_links(uint32_t n, uint32_t t, const uint32_t* __restrict__ tcol, const uint32_t* __restrict__ cs_off,
+                                                         const void* __restrict__ cs_ids, uint32_t cs_w, const uint32_t* __restrict__ succ,
+                                                         const uint32_t* __restrict__ indeg, const uint32_t* __restrict__ pred, uint8_t* __restrict__ flags,
+                                                         uint4* __restrict__ st) {
+    for (uint64_t i0 = blockIdx.x * (uint64_t)SP_THREADS + threadIdx.x; i0 < n; i0 += (uint64_t)gridDim.x * SP_THREADS) {
+        const uint32_t i = (uint32_t)i0;
+        uint32_t f = 0, back = i;
+        if (sp_node(i, t, succ, indeg, tcol, cs_off)) {
+            f = BFT_SP_NODE;
+            const uint32_t v = succ[i];
+            if (v < n && v != i && sp_node(v, t, succ, indeg, tcol, cs_off) && sp_shared(tcol[i], tcol[v], t, cs_off, cs_ids, cs_w)) f |= BFT_SP_OUT;
+            // (pred[] is written only where a successor was found; with indeg 1 it is the one predecessor, and succ[u] == i says i is u's only successor)
+            const uint32_t u = indeg[i] == 1u ? pred[i] : i;
+            if (u != i && succ[u] == i && sp_node(u, t, succ, indeg, tcol, cs_off) && sp_shared(tcol[u], tcol[i], t, cs_off, cs_ids, cs_w)) {
+                f |= BFT_SP_IN;
+                back = u;
+            }
+        }
+        flags[i] = (uint8_t)f;
+        st[i] = make_uint4(back, back != i ? 1u : 0u, i, 0u);
+    }
+}
+
+__global__ __launch_bounds__(SP_THREADS) void k_sp_jump(uint32_t n, const uint4* __restrict__ src, uint4* __restrict__ dst) {
+    for (uint64_t i = blockIdx.x * (uint64_t)SP_THREADS + threadIdx.x; i < n; i += (uint64_t)gridDim.x * SP_THREADS) {
+        const uint4 a = src[i];
+        if (a.y == 0u) {  // a head, a lone node or a row outside every path: nothing behind it
+            dst[i] = a;
+            continue;
+        }
+        const uint4 b = src[a.x];
+        const bool mine = a.z <= b.z;  // (ties: the nearer occurrence)
+        dst[i] = make_uint4(b.x, a.y + b.y, mine ? a.z : b.z, mine ? a.w : a.y + b.w);
+    }
+}
+
+__global__ __launch_bounds__(SP_THREADS) void k_sp_ends(uint32_t n, int k, const uint4* __restrict__ st, const uint8_t* __restrict__ flags,
+                                                        const uint32_t* __restrict__ succ, uint2* __restrict__ hd, uint32_t* __restrict__ len,
+                                                        unsigned long long* __restrict__ longest) {
+    // (every lane of a wavefront runs the same iterations: the wavefront's maximum is combined with shuffles)
+    for (uint64_t i0 = blockIdx.x * (uint64_t)SP_THREADS + (threadIdx.x & ~63u); i0 < n; i0 += (uint64_t)gridDim.x * SP_THREADS) {
+        const uint64_t i = i0 + (threadIdx.x & 63u);
+        uint32_t mx = 0;
+        if (i < n) {
+            const uint32_t f = flags[i];
+            uint2 o = make_uint2(BFT_SP_NONE, 0u);
+            if (f & BFT_SP_NODE) {
+                const uint4 s = st[i];
+                const bool cyc = (flags[s.x] & BFT_SP_IN) != 0;  // (the end of a chain's jumps is its head, which no edge enters)
+                o = cyc ? make_uint2(s.z, s.w) : make_uint2(s.x, s.y);
+                const bool tail = cyc ? succ[i] == s.z : !(f & BFT_SP_OUT);
+                if (tail) {
+                    len[o.x] = (uint32_t)k + o.y;
+                    mx = (uint32_t)k + o.y;
+                }
+            }
+            hd[i] = o;
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, d));
+        // (only a wavefront that beats what the counter already holds takes the atomic: one per wavefront serialises on the one address,
+        // 7.4 ms for the 7x10^5 wavefronts of the config-3 index)
+        if ((threadIdx.x & 63u) == 0 && mx && mx > __hip_atomic_load(longest, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(longest, (unsigned long long)mx);
+    }
+}
+
+__global__ __launch_bounds__(SP_THREADS) void k_sp_offsets(uint32_t n, const uint2* __restrict__ hd, const uint32_t* __restrict__ pid,
+                                                           const uint64_t* __restrict__ choff, uint64_t* __restrict__ offsets, uint64_t paths_cap,
+                                                           const unsigned long long* __restrict__ counts) {
+    for (uint64_t i = blockIdx.x * (uint64_t)SP_THREADS + threadIdx.x; i < n; i += (uint64_t)gridDim.x * SP_THREADS) {
+        if (i == 0) {
+            const uint64_t np = counts[0];
+            if (np <= paths_cap) offsets[np] = counts[1];
+        }
+        if (hd[i].x != (uint32_t)i) continue;
+        const uint64_t p = pid[i];
+        if (p <= paths_cap) offsets[p] = choff[i];
+    }
+}
+
+template <int W>
+__global__ __launch_bounds__(SP_THREADS) void k_sp_spell(const uint64_t* __restrict__ tk, uint32_t n, int k, const uint2* __restrict__ hd,
+                                                         const uint64_t* __restrict__ choff, char* __restrict__ seqs, uint64_t cap) {
+    for (uint64_t i = blockIdx.x * (uint64_t)SP_THREADS + threadIdx.x; i < n; i += (uint64_t)gridDim.x * SP_THREADS) {
+        const uint2 o = hd[i];
+        if (o.x == BFT_SP_NONE) continue;
+        const uint64_t base = choff[o.x];
+        uint64_t t[W], x[W];
+        bft_load_row<W>(tk + i * W, t);
+        bft_x_from_tform<W>(t, k, x);
+        int j0 = o.y ? k - 1 : 0;
+        uint64_t pos = base + (o.y ? (uint64_t)(k - 1) + o.y : 0ull);
+        for (int j = j0; j < k && pos < cap; j++, pos++) {
+            uint64_t wv = 0;
+#pragma unroll
+            for (int w = 0; w < W; w++)
+                if (w == (j >> 5)) wv = x[w];
+            seqs[pos] = "ACGT"[(wv >> (2 * (j & 31))) & 3ull];
+        }
+    }
+}
+
+template <class F>
+int sp_dispatch(int W, F&& f) {
+    switch (W) {
+    case 1: f(std::integral_constant<int, 1>()); break;
+    case 2: f(std::integral_constant<int, 2>()); break;
+    case 3: f(std::integral_constant<int, 3>()); break;
+    default: f(std::integral_constant<int, 4>()); break;
+    }
+    HIPCK(hipGetLastError());
+    return 0;
+}
+dim3 sp_grid(uint64_t n) { return dim3(bft_grid_for((n + SP_THREADS - 1) / SP_THREADS)); }
+
+}  // namespace
+
+int bft_sp_buckets(int W, const uint64_t* d_tk, uint64_t n, int k, const BftSpScratch& p, hipStream_t s) {
+    const uint64_t nb = (1ull << p.sb) + 1;
+    return sp_dispatch(W, [&](auto KW) { hipLaunchKernelGGL((k_sp_buckets<KW>), sp_grid(nb), dim3(SP_THREADS), 0, s, d_tk, (uint32_t)n, k, p.sb, p.start); });
+}
+
+int bft_sp_degrees(int W, const uint64_t* d_tk, uint64_t n, int k, const BftSpScratch& p, hipStream_t s) {
+    if (n == 0) return 0;
+    return sp_dispatch(W, [&](auto KW) {
+        hipLaunchKernelGGL((k_sp_degrees<KW>), sp_grid(n), dim3(SP_THREADS), 0, s, d_tk, (uint32_t)n, k, p.sb, p.start, p.succ, p.indeg, p.pred);
+    });
+}
+
+int bft_sp_links(uint64_t n, uint32_t t, const uint32_t* d_tcol, const uint32_t* d_cs_off, const void* d_cs_ids, uint32_t cs_w, const BftSpScratch& p, hipStream_t s) {
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_sp_links, sp_grid(n), dim3(SP_THREADS), 0, s, (uint32_t)n, t, d_tcol, d_cs_off, d_cs_ids, cs_w, p.succ, p.indeg, p.pred, p.flags, p.st[0]);
+    HIPCK(hipGetLastError());
+    return 0;
+}
+
+int bft_sp_jump(uint64_t n, const BftSpScratch& p, int from, hipStream_t s) {
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_sp_jump, sp_grid(n), dim3(SP_THREADS), 0, s, (uint32_t)n, p.st[from], p.st[from ^ 1]);
+    HIPCK(hipGetLastError());
+    return 0;
+}
+
+int bft_sp_ends(uint64_t n, int k, const BftSpScratch& p, int fin, unsigned long long* d_longest, hipStream_t s) {
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_sp_ends, sp_grid(n), dim3(SP_THREADS), 0, s, (uint32_t)n, k, p.st[fin], p.flags, p.succ, reinterpret_cast<uint2*>(p.st[fin ^ 1]), p.indeg,
+                       d_longest);
+    HIPCK(hipGetLastError());
+    return 0;
+}
+
+int bft_sp_offsets(uint64_t n, const BftSpScratch& p, int fin, uint64_t* d_offsets, uint64_t paths_cap, const unsigned long long* d_counts, hipStream_t s) {
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_sp_offsets, sp_grid(n), dim3(SP_THREADS), 0, s, (uint32_t)n, bft_sp_hd(p, fin), p.pred, p.choff, d_offsets, paths_cap, d_counts);
+    HIPCK(hipGetLastError());
+    return 0;
+}
+
+int bft_sp_spell(int W, const uint64_t* d_tk, uint64_t n, int k, const BftSpScratch& p, int fin, char* d_seqs, uint64_t chars_cap, hipStream_t s) {
+    if (n == 0 || chars_cap == 0) return 0;
+    return sp_dispatch(W, [&](auto KW) {
+        hipLaunchKernelGGL((k_sp_spell<KW>), sp_grid(n), dim3(SP_THREADS), 0, s, d_tk, (uint32_t)n, k, bft_sp_hd(p, fin), p.choff, d_seqs, chars_cap);
+    });
+}

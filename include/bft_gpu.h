@@ -298,6 +298,30 @@ int bft_gpu_subgraph(bft_gpu* src, const uint8_t* kmers, uint64_t nb_kmers, int 
 int bft_gpu_subgraph_dev(bft_gpu* src, const void* d_kmers, uint64_t nb_kmers, int colors, uint64_t* n_absent, bft_gpu** out,
                          void* hip_stream);
 
+/* Simple (non-branching) paths, or unitigs: extract_simple_paths_to_disk(bft, filename) and extract_simple_core_paths_to_disk(bft, core_ratio,
+ * filename) (reference snippets.h, src/snippets.c:115-603) without the disk, for a threshold t = min_shared on shared genomes (0: plain simple
+ * paths; the core form passes (int)(core_ratio * nb_genomes)).
+ *   degrees  the successors of a stored k-mer x are the stored x[1..k-1]+N, its predecessors the stored N+x[0..k-2] (not canonical); they
+ *            always count the whole index;
+ *   nodes    stored k-mers with in-degree <= 1, out-degree <= 1 and a colour set of t genomes or more (branching k-mers are in no path);
+ *   edges    u -> v when v is u's only successor, u is v's only predecessor, both are nodes, v != u and |C(u) & C(v)| >= t;
+ *   paths    the maximal chains of edges, spelled as their first k-mer plus the last nucleotide of each following one (a lone node: its k-mer).
+ *            A cycle is spelled from its k-mer of smallest row, for m + k - 1 nucleotides (m k-mers); a k-mer that is its own only neighbour
+ *            is a lone node.  Paths come in ascending row of their first k-mer (the bft_gpu_extract order).
+ * seqs: ASCII ACGT, no separators; offsets: n_paths + 1 entries, in characters (path i is seqs[offsets[i], offsets[i + 1])).
+ * Host form (like bft_gpu_query_prefixes): offsets holds paths_cap + 1 entries, seqs chars_cap characters; with both NULL the call only counts;
+ * when a cap is too small nothing is written, *n_paths / *n_chars are set and BFT_GPU_E_NOSPACE is returned.
+ * min_shared above the number of genomes gives no path.  Pending insertions are built first; the handle's answers do not change ("compact_table":
+ * the sorted table comes back, as for rows and prefixes).  Launches are counted in bft_gpu_kernel_time; with "build_stages" on, the call's steps
+ * become the stages bft_gpu_build_stages reports.  At most 2^31 - 1 k-mers (BFT_GPU_E_LIMIT). */
+int bft_gpu_simple_paths(bft_gpu* h, uint32_t min_shared, uint64_t* offsets, char* seqs, uint64_t paths_cap, uint64_t chars_cap, uint64_t* n_paths,
+                         uint64_t* n_chars);
+/* The same into device buffers on hip_stream (NULL = the handle's stream), without host synchronisation: d_counts (3 x uint64) always receives
+ * {n_paths, n_chars, longest path in characters}; d_offsets (may be NULL) receives the entries j <= paths_cap of the offsets, d_seqs (may be NULL)
+ * the characters below chars_cap.  Not inside a graph capture (BFT_GPU_E_ARG). */
+int bft_gpu_simple_paths_dev(bft_gpu* h, uint32_t min_shared, void* d_offsets, void* d_seqs, uint64_t paths_cap, uint64_t chars_cap, void* d_counts,
+                             void* hip_stream);
+
 /* A colour set as the reference's annotation bytes -- BFT_annotation::annot as get_annotation returns it
  * (include/bft.h:97, src/bft.c:363-387): mode 0 (bitmap, genome g <-> bit g+2), 1 (ranges) or 2 (id list), chosen the way the
  * reference chooses it: compute_best_mode re-decides at every insertion of a genome id and keeps the current mode on a size tie
