@@ -19,6 +19,9 @@ bool bft_kh_has_kernels(int W, uint32_t S);
 // Nothing is synchronised; the transients live in `sc`, which the caller keeps until s has drained.
 struct BftKhScratch { DevBuf b[7]; };
 int bft_kh_sort(const uint64_t* d_tk, const uint32_t* d_vals, uint64_t n, int k, int W, const BftKhGeo& g, BftKhScratch& sc, hipStream_t s);
+// test hooks (bft_gpu_test_sort_ex, bft_gpu_test_sort_tile): the sort of u32 keys + KhRec<W> records (8 W + 4 bytes, packed) from plain arrays
+int bft_kh_test_sort(int W, int shape, const uint32_t* keys, const void* recs, uint64_t n, unsigned b0, unsigned b1, uint32_t* ok, void* orec, hipStream_t s, uint32_t* h_dbase);
+uint32_t bft_kh_test_sort_tile(int W, int shape);
 int bft_kh_lay(uint64_t n, int k, int W, const BftKhGeo& g, uint64_t* d_kh, uint64_t* d_ovf_k, uint32_t* d_ovf_v, uint32_t* d_status, BftKhScratch& sc, hipStream_t s);
 // every (k-mer, value) of the table, unordered, word w of k-mer j at d_keys[w * stride + j]; *d_cnt (zeroed by the caller) = how many
 int bft_kh_dump(const BftImage& im, uint64_t* d_keys, uint64_t stride, uint32_t* d_vals, unsigned long long* d_cnt, hipStream_t s);

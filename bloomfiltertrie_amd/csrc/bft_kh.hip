@@ -652,6 +652,33 @@ static int kh_lay_w(uint64_t n, int k, const BftKhGeo& g, uint64_t* d_kh, uint64
     return 0;  // (the transients stay in `sc` until the caller has seen `s` drain)
 }
 
+// test hook (bft_gpu_test_sort_ex): u32 keys + packed KhRec<W> records from plain arrays, in the shape of the sort by home line (BACK) and in BIG
+template <int W>
+static int kh_test_sort_w(int shape, const uint32_t* keys, const void* recs, uint64_t n, unsigned b0, unsigned b1, uint32_t* ok, void* orec, hipStream_t s, uint32_t* h_dbase) {
+    typedef bft_rs::PtrIn<uint32_t, KhRec<W>> In;
+    const In in{keys, (const KhRec<W>*)recs};
+    if (shape == bft_rs::SHAPE_BACK) return bft_rs::sort_test_run<uint32_t, KhRec<W>, In, bft_rs::SHAPE_BACK>(in, n, ok, (KhRec<W>*)orec, b0, b1, s, h_dbase);
+    if (shape == bft_rs::SHAPE_BIG) return bft_rs::sort_test_run<uint32_t, KhRec<W>, In, bft_rs::SHAPE_BIG>(in, n, ok, (KhRec<W>*)orec, b0, b1, s, h_dbase);
+    return bft_fail(BFT_GPU_E_ARG, "test sort: shape");
+}
+int bft_kh_test_sort(int W, int shape, const uint32_t* keys, const void* recs, uint64_t n, unsigned b0, unsigned b1, uint32_t* ok, void* orec, hipStream_t s, uint32_t* h_dbase) {
+    switch (W) {
+    case 1: return kh_test_sort_w<1>(shape, keys, recs, n, b0, b1, ok, orec, s, h_dbase);
+    case 2: return kh_test_sort_w<2>(shape, keys, recs, n, b0, b1, ok, orec, s, h_dbase);
+    case 3: return kh_test_sort_w<3>(shape, keys, recs, n, b0, b1, ok, orec, s, h_dbase);
+    case 4: return kh_test_sort_w<4>(shape, keys, recs, n, b0, b1, ok, orec, s, h_dbase);
+    default: return bft_fail(BFT_GPU_E_ARG, "test sort: W");
+    }
+}
+template <int W>
+static uint32_t kh_test_tile_w(int shape) {
+    return shape == bft_rs::SHAPE_BACK ? bft_rs::tile_entries<uint32_t, KhRec<W>, bft_rs::SHAPE_BACK>()
+         : shape == bft_rs::SHAPE_BIG  ? bft_rs::tile_entries<uint32_t, KhRec<W>, bft_rs::SHAPE_BIG>() : 0u;
+}
+uint32_t bft_kh_test_sort_tile(int W, int shape) {
+    return W == 1 ? kh_test_tile_w<1>(shape) : W == 2 ? kh_test_tile_w<2>(shape) : W == 3 ? kh_test_tile_w<3>(shape) : W == 4 ? kh_test_tile_w<4>(shape) : 0u;
+}
+
 int bft_kh_sort(const uint64_t* d_tk, const uint32_t* d_vals, uint64_t n, int k, int W, const BftKhGeo& g, BftKhScratch& sc, hipStream_t s) {
     switch (W) {
     case 1: return kh_sort_w<1>(d_tk, d_vals, n, k, g, sc, s);

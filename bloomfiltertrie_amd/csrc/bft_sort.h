@@ -889,6 +889,15 @@ static inline int rank_mode(hipStream_t s, int force = -1) {
     return mode;
 }
 
+// what the last sort of this host thread ran (host side only; tests/test_gpu_sort_scan_edges.py asks for it through bft_gpu_test_sort_last)
+enum { RUN_COPY = 0, RUN_TILE = 1, RUN_RANGED = 2, RUN_CHAINED = 3, RUN_NONE = 0xFF };
+struct RunRecord {
+    uint32_t regime = RUN_NONE, P = 0, tiles = 0, ranges = 0, tpr = 0, tile = 0;
+    uint32_t bit[MAXP] = {}, nbits[MAXP] = {};
+    uint32_t nch[MAXP] = {}, lbg[MAXP] = {};  // chained passes: chains, look-back groups launched (1 or GMAX); 0 for a ranged pass
+};
+extern thread_local RunRecord g_bft_rs_last;  // (bft_gpu.hip)
+
 // scratch of one sort call (u32 words)
 struct Layout {
     size_t heads, cnt, states, zero_words;  // zeroed before every call: [P][64]; the later passes' (chain, digit) counters; [P - 1][max_tiles][DIGITS]
@@ -902,12 +911,18 @@ struct Layout {
 template <class K, class V, class In, int THREADS, int IPT>
 int sort_cfg(In in, uint64_t n, K* out_k, V* out_v, K* tmp_k, V* tmp_v, unsigned begin_bit, unsigned end_bit, hipStream_t s, DevBuf& scratch, const uint32_t** last_dbase) {
     if (last_dbase) *last_dbase = nullptr;
+    RunRecord& rec = g_bft_rs_last;
+    rec = RunRecord();
     if (n >= (1ull << 31) - 1) return bft_fail(BFT_GPU_E_LIMIT, "internal: radix sort of 2^31 entries or more");
     if (end_bit < begin_bit || end_bit - begin_bit > (unsigned)(MAXP * DBITS) || end_bit > sizeof(K) * 8) return bft_fail(BFT_GPU_E_ARG, "internal: radix sort bit range");
     constexpr uint32_t TILE = (uint32_t)THREADS * IPT;
     const Plan pl = make_plan(begin_bit, end_bit);
     if (n == 0) return 0;
+    rec.P = (uint32_t)pl.P;
+    rec.tile = TILE;
+    for (int p = 0; p < pl.P; p++) { rec.bit[p] = pl.bit[p]; rec.nbits[p] = pl.nbits[p]; }
     if (pl.P == 0) {
+        rec.regime = RUN_COPY;
         hipLaunchKernelGGL((k_rs_copy<K, V, In>), dim3(bft_grid_for((n + 255) / 256)), dim3(256), 0, s, in, (uint32_t)n, out_k, out_v);
         HIPCK(hipGetLastError());
         return 0;
@@ -921,8 +936,12 @@ int sort_cfg(In in, uint64_t n, K* out_k, V* out_v, K* tmp_k, V* tmp_v, unsigned
     const uint32_t tiles = (uint32_t)((n + TILE - 1) / TILE);
     const uint32_t wgs = std::min<uint32_t>(tiles, (uint32_t)std::min(1024, cus * per_cu));  // (<= 1024 ranges: k_rs_rowscan)
     const uint32_t tpr = (tiles + wgs - 1) / wgs, ranges = (tiles + tpr - 1) / tpr;
+    rec.tiles = tiles;
+    rec.tpr = tpr;
+    rec.ranges = ranges;
     constexpr int HT = THREADS;  // (the histogram kernel in the shape of the passes: a 1024-thread workgroup waits long for a CU beside another stream's small ones)
     if (tiles == 1) {  // one tile: every pass in one workgroup's LDS
+        rec.regime = RUN_TILE;
         if (ballot) {
             lds_limit<&k_rs_tiny<K, V, In, THREADS, IPT, true>>((int)lds);
             hipLaunchKernelGGL((k_rs_tiny<K, V, In, THREADS, IPT, true>), dim3(1), dim3(THREADS), lds, s, in, out_k, out_v, (uint32_t)n, pl);
@@ -940,6 +959,8 @@ int sort_cfg(In in, uint64_t n, K* out_k, V* out_v, K* tmp_k, V* tmp_v, unsigned
         // the look-back's round trips and the chains' bookkeeping.
         const size_t words = (size_t)2 * DIGITS + (size_t)CT * 2 + (size_t)ranges * DIGITS + 8;
         if (scratch.bytes < words * 4) CK(scratch.alloc(words * 4));
+        scratch.tag = 0;  // (the block is written here: a scan that shares it must zero it again, bft_scan.h)
+        rec.regime = RUN_RANGED;
         uint32_t* W = scratch.as<uint32_t>();
         uint32_t *tot = W, *dbase = W + DIGITS, *chain = W + 2 * DIGITS, *partial = W + 2 * DIGITS + 2 * CT;
         const K* src_k = nullptr;
@@ -991,6 +1012,8 @@ int sort_cfg(In in, uint64_t n, K* out_k, V* out_v, K* tmp_k, V* tmp_v, unsigned
         L.total_words = o;
     }
     if (scratch.bytes < L.total_words * 4) CK(scratch.alloc(L.total_words * 4));
+    scratch.tag = 0;  // (as above)
+    rec.regime = RUN_CHAINED;
     uint32_t* W = scratch.as<uint32_t>();
     HIPCK(hipMemsetAsync(W, 0, L.zero_words * 4, s));
     lds_limit<&k_rs_hist<K, In, HT>>(160 * 1024 - 64);
@@ -1038,6 +1061,8 @@ int sort_cfg(In in, uint64_t n, K* out_k, V* out_v, K* tmp_k, V* tmp_v, unsigned
             constexpr int GMAX = THREADS / (DIGITS / 4);
             const uint32_t nchp = 1u << pl.cb[p];
             uint32_t grid = std::min<uint32_t>(tiles + nchp, (uint32_t)(cus * per_cu));
+            rec.nch[p] = nchp;
+            rec.lbg[p] = 1;
             // (the one-group form where the grid is small enough for it -- unless it uses scratch memory: for 8-byte keys without a payload it
             // spills five registers, the eight-group form none, and a kernel with scratch starts ~0.13 ms late behind kernels without)
             if (grid <= nchp * 4u && ballot) {
@@ -1046,6 +1071,7 @@ int sort_cfg(In in, uint64_t n, K* out_k, V* out_v, K* tmp_k, V* tmp_v, unsigned
                 BFT_RS_LAUNCH1(false, 1);
             } else {
                 grid = std::min<uint32_t>(grid, nchp * 4u * GMAX);
+                rec.lbg[p] = GMAX;
                 if (ballot) BFT_RS_LAUNCH1(true, GMAX);
                 else BFT_RS_LAUNCH1(false, GMAX);
             }
@@ -1070,25 +1096,28 @@ int sort_cfg(In in, uint64_t n, K* out_k, V* out_v, K* tmp_k, V* tmp_v, unsigned
 // build's second stream: a BACK and a LIGHT workgroup fit one CU together, so the persistent workgroups of the one sort do not keep the
 // other's from being placed (side by side in the BIG shape the (node, CC) sorts of the assembly took 1.6 ms instead of 0.3).
 enum { SHAPE_BIG = 0, SHAPE_LIGHT = 1, SHAPE_BACK = 2 };
+template <class K, class V>
+constexpr size_t entry_bytes() { return sizeof(K) + (std::is_same<V, NoVal>::value ? 0 : sizeof(V)); }
+template <int SHAPE>
+constexpr int shape_threads() { return SHAPE == SHAPE_LIGHT ? 256 : SHAPE == SHAPE_BACK ? 1024 : BFT_RS_BIG_THREADS; }
+template <int SHAPE, size_t E>
+constexpr int shape_ipt() {
+    if (SHAPE == SHAPE_LIGHT) return E <= 8 ? 12 : E <= 12 ? 8 : E <= 16 ? 6 : E <= 24 ? 4 : E <= 32 ? 3 : 2;
+    if (SHAPE == SHAPE_BACK) return E <= 8 ? 8 : E <= 12 ? 5 : E <= 16 ? 4 : E <= 24 ? 3 : E <= 32 ? 2 : 1;
+    // (ten 8-byte keys per thread, not twelve: at twelve the chained pass spills two registers, and a kernel that uses scratch memory starts
+    // ~0.13 ms late whenever the kernels before it used none -- the runtime hands the queue's scratch back and has to find it again)
+#ifdef BFT_RS_BIG_IPT
+    if (E <= 8) return BFT_RS_BIG_IPT;
+#endif
+    return E <= 8 ? 12 : E <= 12 ? 8 : E <= 16 ? 6 : E <= 24 ? 4 : E <= 32 ? 3 : 2;
+}
+// the entries of one tile of sort<K, V, In, SHAPE> (the one-tile / ranged boundary)
+template <class K, class V, int SHAPE>
+constexpr uint32_t tile_entries() { return (uint32_t)shape_threads<SHAPE>() * (uint32_t)shape_ipt<SHAPE, entry_bytes<K, V>()>(); }
 template <class K, class V, class In, int SHAPE = SHAPE_BIG>
 int sort(In in, uint64_t n, K* out_k, V* out_v, K* tmp_k, V* tmp_v, unsigned begin_bit, unsigned end_bit, hipStream_t s, DevBuf& scratch, const uint32_t** last_dbase = nullptr) {
-    constexpr size_t E = sizeof(K) + (std::is_same<V, NoVal>::value ? 0 : sizeof(V));
-    if constexpr (SHAPE == SHAPE_LIGHT) {
-        constexpr int IPT = E <= 8 ? 12 : E <= 12 ? 8 : E <= 16 ? 6 : E <= 24 ? 4 : E <= 32 ? 3 : 2;
-        return sort_cfg<K, V, In, 256, IPT>(in, n, out_k, out_v, tmp_k, tmp_v, begin_bit, end_bit, s, scratch, last_dbase);
-    } else if constexpr (SHAPE == SHAPE_BACK) {
-        constexpr int IPT = E <= 8 ? 8 : E <= 12 ? 5 : E <= 16 ? 4 : E <= 24 ? 3 : E <= 32 ? 2 : 1;
-        return sort_cfg<K, V, In, 1024, IPT>(in, n, out_k, out_v, tmp_k, tmp_v, begin_bit, end_bit, s, scratch, last_dbase);
-    } else {
-        // (ten 8-byte keys per thread, not twelve: at twelve the chained pass spills two registers, and a kernel that uses scratch memory starts
-        // ~0.13 ms late whenever the kernels before it used none -- the runtime hands the queue's scratch back and has to find it again)
-        constexpr int IPT_BIG = E <= 8 ? 12 : E <= 12 ? 8 : E <= 16 ? 6 : E <= 24 ? 4 : E <= 32 ? 3 : 2;
-#ifdef BFT_RS_BIG_IPT
-        return sort_cfg<K, V, In, BFT_RS_BIG_THREADS, (E <= 8 ? BFT_RS_BIG_IPT : IPT_BIG)>(in, n, out_k, out_v, tmp_k, tmp_v, begin_bit, end_bit, s, scratch, last_dbase);
-#else
-        return sort_cfg<K, V, In, BFT_RS_BIG_THREADS, IPT_BIG>(in, n, out_k, out_v, tmp_k, tmp_v, begin_bit, end_bit, s, scratch, last_dbase);
-#endif
-    }
+    constexpr size_t E = entry_bytes<K, V>();
+    return sort_cfg<K, V, In, shape_threads<SHAPE>(), shape_ipt<SHAPE, E>()>(in, n, out_k, out_v, tmp_k, tmp_v, begin_bit, end_bit, s, scratch, last_dbase);
 }
 
 // the same with the buffers between the passes and the scratch taken from the device-memory cache for the duration of the call (they go back
@@ -1109,6 +1138,21 @@ int sort_pairs(const K* in_k, const V* in_v, uint64_t n, K* out_k, V* out_v, uns
 template <class K>
 int sort_keys(const K* in_k, uint64_t n, K* out_k, unsigned begin_bit, unsigned end_bit, hipStream_t s) {
     return sort_in<K, NoVal, PtrIn<K, NoVal>>(PtrIn<K, NoVal>{in_k, nullptr}, n, out_k, (NoVal*)nullptr, begin_bit, end_bit, s);
+}
+
+// (test hooks) sort_in, synchronised, with the last pass's digit starts copied to h_dbase (512 words; left as they are where the sort made none)
+template <class K, class V, class In, int SHAPE>
+int sort_test_run(In in, uint64_t n, K* out_k, V* out_v, unsigned begin_bit, unsigned end_bit, hipStream_t s, uint32_t* h_dbase) {
+    DevBuf tk, tv, scratch;
+    if (begin_bit <= end_bit && end_bit - begin_bit <= (unsigned)(MAXP * DBITS) && make_plan(begin_bit, end_bit).P > 1 && n) {
+        CK(tk.alloc(n * sizeof(K)));
+        if (!std::is_same<V, NoVal>::value) CK(tv.alloc(n * sizeof(V)));
+    }
+    const uint32_t* db = nullptr;
+    CK((sort<K, V, In, SHAPE>(in, n, out_k, out_v, tk.as<K>(), tv.as<V>(), begin_bit, end_bit, s, scratch, &db)));
+    if (h_dbase && db) HIPCK(hipMemcpyAsync(h_dbase, db, DIGITS * 4, hipMemcpyDeviceToHost, s));
+    HIPCK(hipStreamSynchronize(s));
+    return 0;
 }
 
 }  // namespace bft_rs
