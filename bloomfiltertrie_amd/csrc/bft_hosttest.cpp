@@ -236,6 +236,149 @@ extern "C" int bft_hosttest_kh_verify(const uint64_t* tk, const uint32_t* vals, 
     default: return kh_verify<4>(tk, vals, n, k, g, lines, n_lines, ovf_k, ovf_v, n_ovf);
     }
 }
+// bft_kh_geometry for the given inputs, in the order of geo_out (13, the overflow count, is 0; 11 is the displacement bound maxd)
+extern "C" void bft_hosttest_kh_geometry_of(int k, uint64_t n, uint64_t n_values, uint32_t load_pct, uint32_t* geo) {
+    BftKhHostTable tab;
+    tab.g = bft_kh_geometry(k, n, n_values, load_pct);
+    tab.max_d = tab.g.maxd;
+    geo_out(tab, geo);
+}
+// home line of every packed k-mer under bft_kh_geometry(k, n, n_values, load_pct) (tests gather k-mers of a few neighbouring home lines
+// into runs of full lines that end in the overflow list)
+extern "C" void bft_hosttest_kh_homes_of(const uint8_t* q, uint64_t nq, int k, uint64_t n, uint64_t n_values, uint32_t load_pct, uint64_t* out) {
+    const BftKhGeo g = bft_kh_geometry(k, n, n_values, load_pct);
+    std::vector<uint64_t> tq;
+    tform_any(q, nq, k, tq);
+    const int W = bft_words_for_k(k);
+    for (uint64_t i = 0; i < nq; i++) {
+        switch (W) {
+        case 1: { BftKhKey<1> kk; bft_kh_key<1>(&tq[i], k, g, kk); out[i] = kk.home; } break;
+        case 2: { BftKhKey<2> kk; bft_kh_key<2>(&tq[i * 2], k, g, kk); out[i] = kk.home; } break;
+        case 3: { BftKhKey<3> kk; bft_kh_key<3>(&tq[i * 3], k, g, kk); out[i] = kk.home; } break;
+        default: { BftKhKey<4> kk; bft_kh_key<4>(&tq[i * 4], k, g, kk); out[i] = kk.home; } break;
+        }
+    }
+}
+// Every (key width, slots per line) bft_kh_geometry picks for k = 9 .. 126, n < 2^31 distinct k-mers (and n <= 4^k), any number of
+// values 1 .. n and any load of 10 .. 80 per cent, with one example each: out rows of 6 words {W, S, k, n, n_values, load}, at most cap
+// rows; returns the number of rows, or a negative number when the fast scan below disagreed with bft_kh_geometry.
+//
+// The geometry depends on n only through want = ceil(100 n / (S load)) of each S: through floor(log2(want)) and m = ceil(want / 2^abits).
+// So n runs over the smallest n of every interval where none of those changes (and over the powers of two, where the largest value
+// width changes), and at each n the twenty candidates of bft_kh_geometry are laid out once per number of hashed bits hb (their lines
+// and q bits depend on k through hb alone): for a value width cb the winner is the candidate of fewest lines (ties: the earlier) whose
+// body holds cb value bits, so every value width is covered by walking the candidates by lines.  The examples take the largest value
+// width of their range (a body filled to the last bit where the range ends on the fit) and the smallest n.  Geometries with
+// nl + BFT_KH_TAIL_LINES >= 2^32 are not built by the product and are skipped.
+extern "C" int64_t bft_hosttest_kh_reachable(uint64_t* out, uint32_t cap) {
+    struct Cand { uint64_t nl; uint32_t qb, S, idx; };
+    std::vector<uint64_t> ex(5 * 16 * 4, 0);  // [W * 16 + S] -> {k, n, n_values, load}, n = 0: not reached
+    std::vector<uint64_t> ns;
+    uint64_t checked = 0;
+    int64_t bad = 0;
+    // k grouped by (hb, bound on n): k < 16 holds at most 4^k < 2^31 distinct k-mers
+    std::vector<std::pair<std::pair<uint32_t, uint64_t>, std::vector<int>>> groups;
+    for (int k = 9; k <= 126; k++) {
+        const uint32_t hb = bft_kh_geometry(k, 1, 1, 50).hb;  // (hb, restb: functions of k alone)
+        const uint64_t nmax = k < 16 ? (1ull << (2 * k)) + 1 : 1ull << 31;  // n < nmax
+        size_t gi = 0;
+        while (gi < groups.size() && groups[gi].first != std::make_pair(hb, nmax)) gi++;
+        if (gi == groups.size()) groups.push_back({{hb, nmax}, {}});
+        groups[gi].second.push_back(k);
+    }
+    for (const auto& grp : groups) {
+        const uint32_t hb = grp.first.first;
+        const uint64_t nmax = grp.first.second;
+        auto abits_of = [hb](uint32_t lg) {
+            uint32_t abits = lg > 4 ? lg - 4 : 0;
+            if (abits > hb) abits = hb;
+            if (hb - abits > 27u) abits = hb - 27u;
+            return abits;
+        };
+        for (uint32_t load = 10; load <= 80; load++) {
+            ns.clear();
+            for (uint32_t c = 0; c < 31; c++)
+                if ((1ull << c) < nmax) ns.push_back(1ull << c);
+            for (uint32_t S = 1; S <= BFT_KH_MAX_SLOTS; S++) {
+                const uint64_t per = (uint64_t)S * load, wmax = ((nmax - 1) * 100ull + per - 1) / per;
+                auto add = [&](uint64_t w) {  // the smallest n with want >= w
+                    if (w >= 1 && w <= wmax) ns.push_back((w - 1) * per / 100 + 1);
+                };
+                for (uint32_t lg = 0; (1ull << lg) <= wmax; lg++) {
+                    const uint32_t abits = abits_of(lg);
+                    const uint64_t lo = 1ull << lg, hi = 2ull << lg;
+                    add(lo);
+                    add(lo + 1);
+                    for (uint64_t j = lo >> abits; (j << abits) + 1 < hi; j++)
+                        if ((j << abits) + 1 > lo) add((j << abits) + 1);
+                }
+            }
+            std::sort(ns.begin(), ns.end());
+            ns.erase(std::unique(ns.begin(), ns.end()), ns.end());
+            for (uint64_t n : ns) {
+                // the candidates of bft_kh_geometry, in its order, then by lines (ties in that order: an insertion sort keeps it)
+                Cand cs[2 * BFT_KH_MAX_SLOTS];
+                uint32_t nc = 0;
+                for (uint32_t S = BFT_KH_MAX_SLOTS; S >= 1; S--) {
+                    for (uint32_t pow2 = 0; pow2 < 2; pow2++) {
+                        const uint64_t per = (uint64_t)S * load;
+                        uint64_t want = (n * 100ull + per - 1) / per;
+                        if (want < 1) want = 1;
+                        uint32_t lg = 63u - (uint32_t)__builtin_clzll(want);  // floor(log2(want))
+                        if (pow2) {
+                            if (want == (1ull << lg)) continue;
+                            lg++;
+                            want = 1ull << lg;
+                        }
+                        const uint32_t abits = abits_of(lg), t = hb - abits;
+                        uint64_t m = (want + (1ull << abits) - 1) >> abits;
+                        if (m < 2) m = 2;
+                        const uint64_t span = ((1ull << t) + m - 1) / m;
+                        const uint32_t qb = span > 1 ? std::min(32u, 64u - (uint32_t)__builtin_clzll(span - 1)) : 0u;  // bits of span - 1
+                        cs[nc] = {m << abits, qb, S, nc};
+                        nc++;
+                    }
+                }
+                for (uint32_t a = 1; a < nc; a++)
+                    for (uint32_t b = a; b > 0 && cs[b].nl < cs[b - 1].nl; b--) std::swap(cs[b], cs[b - 1]);
+                const int cbmax = (int)bft_kh_value_bits(n);  // (n_values <= n)
+                for (int k : grp.second) {
+                    const int W = bft_words_for_k(k);
+                    const uint32_t restb = 2u * (uint32_t)k - hb;
+                    int covered = 0;  // value widths 1 .. covered have their winner
+                    for (uint32_t c = 0; c < nc && covered < cbmax; c++) {
+                        const uint32_t S = cs[c].S, f = bft_kh_field_bits(S), kb = restb + cs[c].qb > f ? restb + cs[c].qb : f;
+                        const int fit = S == 1 ? 64 : (int)(8u * bft_kh_body_bytes(S) + f) - (int)BFT_KH_DBITS_FOR(S) - (int)kb;  // the largest cb the body holds
+                        if (fit <= covered) continue;
+                        const int cb = std::min(fit, cbmax);
+                        covered = cb;
+                        if (cs[c].nl + BFT_KH_TAIL_LINES >= (1ull << 32)) continue;
+                        const uint64_t nv = 1ull << (cb - 1);  // (values 0 .. n_values - 1 need cb bits from 2^(cb - 1) on)
+                        uint64_t* e = &ex[(W * 16 + S) * 4];
+                        const bool take = e[1] == 0 || n < e[1];
+                        if (take || (checked++ & 255u) == 0) {  // (the scan against the geometry itself: every example and a sample of the rest)
+                            const BftKhGeo g = bft_kh_geometry(k, n, nv, load);
+                            if (g.S != S || g.nl != cs[c].nl || g.cb != (uint32_t)cb || g.restb != restb) bad++;
+                        }
+                        if (take) { e[0] = (uint64_t)k; e[1] = n; e[2] = nv; e[3] = load; }
+                    }
+                }
+            }
+        }
+    }
+    if (bad) return -bad;
+    uint32_t rows = 0;
+    for (int ws = 0; ws < 5 * 16; ws++)
+        if (ex[ws * 4 + 1]) {
+            if (rows < cap) {
+                uint64_t* o = out + (size_t)rows * 6;
+                o[0] = (uint64_t)(ws / 16); o[1] = (uint64_t)(ws % 16);
+                for (int i = 0; i < 4; i++) o[2 + i] = ex[ws * 4 + i];
+            }
+            rows++;
+        }
+    return rows;
+}
 // geometry of the host table: out[0..13] (12: displacement bits, 13: k-mers in the overflow list) = slots per line, field bits, body bytes, value bits, key bits, q bits, hashed bits, bits below,
 // t, m, home lines, largest displacement
 extern "C" void bft_hosttest_kh_geometry(void* hv, uint32_t* out) { geo_out(((HostTrie*)hv)->kh, out); }
