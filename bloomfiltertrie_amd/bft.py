@@ -389,6 +389,27 @@ class BFT:
         _lib.check(self._lib.bft_gpu_simple_paths_dev(self._h, int(min_shared), C.c_void_p(d_offsets_ptr or 0), C.c_void_p(d_seqs_ptr or 0), paths_cap,
                                                       chars_cap, C.c_void_p(d_counts_ptr), C.c_void_p(stream or 0)))
 
+    def components(self, genome_ids=()):
+        """get_nb_connected_component (reference snippets.h, src/snippets.c:605-960) on the GPU: the connected components of the index, or of the
+        sub-graph of k-mers that carry every genome id of genome_ids (strictly increasing; bft_gpu_components defines them).  Returns
+        (labels: uint32 per row in the extract order, 0xFFFFFFFF for a non-member; sizes: uint64 per component, numbered by smallest row)."""
+        ids = np.ascontiguousarray(genome_ids, dtype=np.uint32)
+        pids = ids.ctypes.data if len(ids) else None
+        counts = np.zeros(3, dtype=np.uint64)
+        _lib.check(self._lib.bft_gpu_components(self._h, pids, len(ids), None, 0, None, 0, counts.ctypes.data))
+        labels = np.zeros(int(self.info()["kmers"]), dtype=np.uint32)
+        sizes = np.zeros(int(counts[0]), dtype=np.uint64)
+        _lib.check(self._lib.bft_gpu_components(self._h, pids, len(ids), labels.ctypes.data, len(labels), sizes.ctypes.data, len(sizes),
+                                                counts.ctypes.data))
+        return labels, sizes
+
+    def components_dev(self, d_labels_ptr, d_sizes_ptr, sizes_cap, d_counts_ptr, genome_ids=(), stream=None):
+        """Device-resident components (bft_gpu_components_dev): {n_components, n_members, largest} (3 uint64) at d_counts_ptr always, the labels
+        of every row and the sizes below sizes_cap into the buffers that are not 0; no synchronisation."""
+        ids = np.ascontiguousarray(genome_ids, dtype=np.uint32)
+        _lib.check(self._lib.bft_gpu_components_dev(self._h, ids.ctypes.data if len(ids) else None, len(ids), C.c_void_p(d_labels_ptr or 0),
+                                                    C.c_void_p(d_sizes_ptr or 0), sizes_cap, C.c_void_p(d_counts_ptr), C.c_void_p(stream or 0)))
+
     def genome_name(self, id_genome):
         """The name of genome id_genome (the reference's filenames[id_genome]; "genome_<id>" for an id that was never named)."""
         buf = C.create_string_buffer(4096)

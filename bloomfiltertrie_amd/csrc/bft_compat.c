@@ -744,3 +744,76 @@ void extract_simple_core_paths_to_disk(BFT* graph, double core_ratio, char* file
     simple_paths_to_disk(graph, t > 0 ? (uint32_t)t : 0u, filename_output, "extract_simple_core_paths_to_disk(): failed to create/open output file.\n", "core ",
                          "extract_simple_core_paths_to_disk()");
 }
+
+/* ---------------------------------------------------------------- connected components (<bft/snippets.h>) */
+
+/* BFS, DFS, BFS_subgraph and DFS_subgraph (src/snippets.c:605-822) walk from one k-mer and mark what they visit: this library has no vertex marks.
+ * They exist so that a program can hand them to get_nb_connected_component, which tells them apart by their addresses; called in any other way
+ * they stop the program. */
+#define NEEDS_MARKING(where) DIE("%s: vertex marking is not provided; pass it to get_nb_connected_component() to count components.\n", where)
+size_t BFS(BFT_kmer* kmer, BFT* graph, va_list args) { (void)kmer; (void)graph; (void)args; NEEDS_MARKING("BFS()"); }
+size_t BFS_subgraph(BFT_kmer* kmer, BFT* graph, va_list args) { (void)kmer; (void)graph; (void)args; NEEDS_MARKING("BFS_subgraph()"); }
+size_t DFS(BFT_kmer* kmer, BFT* graph, va_list args) { (void)kmer; (void)graph; (void)args; NEEDS_MARKING("DFS()"); }
+size_t DFS_subgraph(BFT_kmer* kmer, BFT* graph, va_list args) { (void)kmer; (void)graph; (void)args; NEEDS_MARKING("DFS_subgraph()"); }
+
+/* src/snippets.c:824-881: the k-mer's sorted id list is walked against the requested ids in the order given, and the walk stops at the first list
+ * id above the one looked for.  True only when nb_id_genomes > 0, the ids are strictly increasing and all of them are in the k-mer's set. */
+bool is_in_subgraph(BFT_kmer* kmer, BFT* graph, int nb_id_genomes, const va_list args) {
+    NOT_NULL(kmer, "is_in_subgraph()");
+    NOT_NULL(graph, "is_in_subgraph()");
+    BFT_annotation* annot = get_annotation(kmer);
+    uint32_t* list_ids = get_list_id_genomes(annot, graph);
+    free_BFT_annotation(annot);
+    int j = 0;
+    if (nb_id_genomes > 0 && list_ids[0] >= (uint32_t)nb_id_genomes) {
+        va_list cpy;
+#pragma GCC diagnostic push
+#pragma GCC diagnostic ignored "-Wdiscarded-qualifiers"
+        va_copy(cpy, args); /* (the reference's signature takes a const va_list; va_copy only reads it) */
+#pragma GCC diagnostic pop
+        uint32_t curr = va_arg(cpy, uint32_t);
+        for (uint32_t i = 1; i <= list_ids[0]; i++) {
+            if (list_ids[i] == curr) {
+                if (++j == nb_id_genomes) break;
+                curr = va_arg(cpy, uint32_t);
+            } else if (list_ids[i] > curr)
+                break;
+        }
+        va_end(cpy);
+    }
+    free(list_ids);
+    return nb_id_genomes > 0 && j == nb_id_genomes;
+}
+
+/* src/snippets.c:915-960: get_nb_connected_component(graph, int* nb, BFT_func_ptr f[, int nb_id_genomes, uint32_t id...]) ADDS the number of
+ * connected components to *nb.  One bft_gpu_components count instead of one traversal per k-mer: f = BFS or DFS counts the whole graph,
+ * BFS_subgraph or DFS_subgraph the sub-graph induced by the k-mers that carry every id.  As in the reference, nb_id_genomes <= 0 or ids that are
+ * not strictly increasing match no k-mer (is_in_subgraph): they add 0. */
+void get_nb_connected_component(BFT* graph, ...) {
+    NOT_NULL(graph, "get_nb_connected_component()");
+    va_list args;
+    va_start(args, graph);
+    int* nb = va_arg(args, int*);
+    BFT_func_ptr f = va_arg(args, BFT_func_ptr);
+    NOT_NULL(nb, "get_nb_connected_component()");
+    uint64_t counts[3] = {0, 0, 0};
+    if (f == BFS || f == DFS)
+        ck(bft_gpu_components(graph->gpu, NULL, 0, NULL, 0, NULL, 0, counts), "get_nb_connected_component()");
+    else if (f == BFS_subgraph || f == DFS_subgraph) {
+        const int nb_ids = va_arg(args, int);
+        if (nb_ids > 0) {
+            uint32_t* ids = malloc((size_t)nb_ids * sizeof(uint32_t));
+            NOT_NULL(ids, "get_nb_connected_component()");
+            bool increasing = true;
+            for (int i = 0; i < nb_ids; i++) {
+                ids[i] = va_arg(args, uint32_t);
+                if (i && ids[i] <= ids[i - 1]) increasing = false;
+            }
+            if (increasing) ck(bft_gpu_components(graph->gpu, ids, (uint32_t)nb_ids, NULL, 0, NULL, 0, counts), "get_nb_connected_component()");
+            free(ids);
+        }
+    } else
+        DIE("get_nb_connected_component(): the traversal function must be BFS, DFS, BFS_subgraph or DFS_subgraph.\n");
+    va_end(args);
+    *nb += (int)counts[0];
+}

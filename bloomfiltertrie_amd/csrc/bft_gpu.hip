@@ -31,6 +31,7 @@
 #include "bft_image.h"
 #include "bft_index.h"
 #include "bft_kh.h"
+#include "bft_components.h"
 #include "bft_paths.h"
 #include "bft_prefix.h"
 #include "bft_scan.h"
@@ -402,6 +403,11 @@ struct bft_gpu {
     hipStream_t sp_stream = nullptr;
     hipEvent_t sp_ev = nullptr;    // where the last use of that scratch ends
     bool sp_used = false;
+    DevBuf cc_buf, cc_tmp;         // scratch of the connected components (BftCcScratch, bft_components.h) and their scans' temporary (grown, never shrunk)
+    uint64_t cc_m = 0, cc_sets = 0; // rows and colour sets cc_buf has room for
+    hipStream_t cc_stream = nullptr;
+    hipEvent_t cc_ev = nullptr;    // where the last use of that scratch ends
+    bool cc_used = false;
     bool inject_build_failure = false;  // test hook: the next bft_gpu_build fails right before its commit point (one shot)
     bool opt_build_stages = false;      // "build_stages": the next builds record GPU time and bytes per stage (bft_gpu_build_stages)
     struct Stage { std::string name; double ms, bytes; };
@@ -561,6 +567,7 @@ extern "C" void bft_gpu_free(bft_gpu* h) {
     if (h->qc_ev) { (void)hipEventDestroy(h->qc_ev); h->qc_ev = nullptr; }
     if (h->pm_ev) { (void)hipEventDestroy(h->pm_ev); h->pm_ev = nullptr; }
     if (h->sp_ev) { (void)hipEventDestroy(h->sp_ev); h->sp_ev = nullptr; }
+    if (h->cc_ev) { (void)hipEventDestroy(h->cc_ev); h->cc_ev = nullptr; }
     const hipStream_t s = h->stream;
     if (s) (void)hipStreamSynchronize(s);
     if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); h->stream2 = nullptr; }
@@ -3792,6 +3799,148 @@ extern "C" int bft_gpu_simple_paths(bft_gpu* h, uint32_t min_shared, uint64_t* o
         HIPCK(hipStreamSynchronize(s));
     }
     sp_release(h, s);
+    return BFT_GPU_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// connected components (get_nb_connected_component with BFS / DFS / BFS_subgraph / DFS_subgraph, reference snippets.h, src/snippets.c:605-960):
+// membership, a lock-free union-find over the successor edges, numbering and sizes over the sorted table (bft_components.hip)
+// ------------------------------------------------------------------------------------------------
+static uint64_t cc_bytes(uint64_t m, uint64_t sets, int sb) {
+    auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
+    return al(((1ull << sb) + 1) * 4) + 2 * al(m * 4) + al(sets);
+}
+// The handle's scratch for an index of n rows and n_sets colour sets on stream s: its own block, shared with no other query; a call on another
+// stream first waits for the last use (an event of the handle's own).
+static int cc_scratch(bft_gpu* h, uint64_t n, uint64_t n_sets, hipStream_t s, BftCcScratch* p) {
+    if (h->cc_used && h->cc_stream != s) {
+        HIPCK(h->cc_ev ? hipEventSynchronize(h->cc_ev) : hipDeviceSynchronize());
+        h->cc_used = false;
+    }
+    const int sb = bft_sp_bucket_bits(h->k);
+    const size_t tb = bft_scan::scratch_bytes(n + 1);
+    if (h->cc_m < n || h->cc_sets < n_sets || h->cc_buf.bytes < cc_bytes(h->cc_m, h->cc_sets, sb) || h->cc_tmp.bytes < tb) {
+        if (h->cc_used) HIPCK(hipStreamSynchronize(s));
+        if (h->cc_m < n || h->cc_sets < n_sets || h->cc_buf.bytes < cc_bytes(h->cc_m, h->cc_sets, sb)) {
+            const uint64_t m = std::max(n, h->cc_m), ns = std::max(n_sets, h->cc_sets);
+            CK(h->cc_buf.alloc(cc_bytes(m, ns, sb)));
+            h->cc_m = m;
+            h->cc_sets = ns;
+        }
+        if (h->cc_tmp.bytes < tb) CK(h->cc_tmp.alloc(tb));
+    }
+    auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
+    uint8_t* q = h->cc_buf.as<uint8_t>();
+    p->sp = BftSpScratch{};
+    p->sp.sb = sb;
+    p->sp.start = (uint32_t*)q; q += al(((1ull << sb) + 1) * 4);
+    p->parent = (uint32_t*)q; q += al(h->cc_m * 4);
+    p->num = (uint32_t*)q; q += al(h->cc_m * 4);
+    p->member = q;
+    h->cc_used = true;
+    h->cc_stream = s;
+    return 0;
+}
+static void cc_release(bft_gpu* h, hipStream_t s) {
+    if (!h->cc_ev && hipEventCreateWithFlags(&h->cc_ev, hipEventDisableTiming) != hipSuccess) { h->cc_ev = nullptr; (void)hipGetLastError(); }
+    if (h->cc_ev && hipEventRecord(h->cc_ev, s) != hipSuccess) (void)hipGetLastError();
+}
+// Membership, forest, numbering, labels and sizes on stream s: d_counts = {n_components, n_members, largest} (24 bytes, device); the labels stay in
+// p.num, the sizes in p.parent.  d_labels / d_sizes (may be NULL): the labels, the sizes below sizes_cap.  The number of launches depends on nb alone.
+// With "build_stages" on, every step is a stage (bft_gpu_build_stages), its bytes those its algorithm reads and writes.
+static int cc_run(bft_gpu* h, const uint32_t* ids, uint32_t nb, hipStream_t s, unsigned long long* d_counts, const BftCcScratch& p, uint32_t* d_labels,
+                  uint64_t* d_sizes, uint64_t sizes_cap) {
+    const uint64_t n = h->n_kmers, ns = h->n_sets;
+    const int W = h->W, k = h->k;
+    const uint64_t* tk = h->d_tk.as<uint64_t>();
+    const double nd = (double)n, rowb = 8.0 * W;
+    CK(bft_zero_async(d_counts, 24, s));
+    for (uint32_t j = 0; j < nb; j += BFT_CC_IDS)
+        CK(timed_launch(h, s, [&] { return bft_cc_sets(ns, h->d_cs_off.as<uint32_t>(), h->d_cs_ids.p, h->cs_w, ids + j, nb - j, j == 0, p, s); }));
+    if (nb) bft_stage("components: members among the colour sets", (double)ns * 9 + (double)h->n_ids * h->cs_w, s);
+    CK(timed_launch(h, s, [&] { return bft_cc_init(n, nb ? h->d_tcol.as<uint32_t>() : nullptr, p, s); }));
+    bft_stage("components: members", nd * (4 + (nb ? 5 : 0)), s);
+    CK(timed_launch(h, s, [&] { return bft_sp_buckets(W, tk, n, k, p.sp, s); }));
+    bft_stage("components: buckets of the table", (double)((1ull << p.sp.sb) + 1) * 4, s);
+    CK(timed_launch(h, s, [&] { return bft_cc_hook(W, tk, n, k, p, s); }));
+    bft_stage("components: successors and hooking", nd * (2 * rowb + 4 + 4 + 8), s);
+    CK(timed_launch(h, s, [&] { return bft_cc_flatten(n, p, s); }));
+    bft_stage("components: roots", nd * 12, s);
+    CK(timed_launch(h, s, [&] { return bft_scan::exclusive_sum<uint32_t>(BftCcMember{p.parent}, p.num, n, s, h->cc_tmp, d_counts + 1, false); }));
+    CK(timed_launch(h, s, [&] { return bft_scan::exclusive_sum<uint32_t>(BftCcRoot{p.parent}, p.num, n, s, h->cc_tmp, d_counts, false); }));
+    bft_stage("components: two scans (members, components)", nd * 16, s);
+    CK(timed_launch(h, s, [&] { return bft_cc_label(n, p, d_labels, s); }));
+    bft_stage("components: labels", nd * (4 + 4 + 4 + 4 + (d_labels ? 4 : 0)), s);
+    CK(timed_launch(h, s, [&] { return bft_cc_count(n, p, s); }));
+    bft_stage("components: sizes", nd * 4, s);
+    CK(timed_launch(h, s, [&] { return bft_cc_sizes(n, p, d_sizes, sizes_cap, d_counts, s); }));
+    bft_stage("components: sizes out, largest", 0.0, s);  // (n_components entries: not known on the host without a read-back)
+    return 0;
+}
+static int cc_prepare(bft_gpu* h) {
+    CK(ensure_built(h));  // ("compact_table": the sorted table comes back, as for rows, prefixes and simple paths)
+    if (h->n_kmers >= (1ull << 31)) return fail(BFT_GPU_E_LIMIT, "components: at most 2^31 - 1 k-mers");
+    return 0;
+}
+
+extern "C" int bft_gpu_components_dev(bft_gpu* h, const uint32_t* genome_ids, uint32_t nb_ids, void* d_labels, void* d_sizes, uint64_t sizes_cap, void* d_counts,
+                                      void* hip_stream) {
+    if (!h || !d_counts || (nb_ids && !genome_ids)) return fail(BFT_GPU_E_ARG, "NULL argument");
+    for (uint32_t j = 1; j < nb_ids; j++)
+        if (genome_ids[j] <= genome_ids[j - 1]) return fail(BFT_GPU_E_ARG, "components: genome ids must be strictly increasing");
+    ENTER(h);
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
+    if (stream_capturing(s)) return fail(BFT_GPU_E_ARG, "components recorded into a graph: not supported (the table may have to come back, scratch may grow)");
+    CK(cc_prepare(h));
+    if (h->n_kmers == 0) {
+        CK(bft_zero_async(d_counts, 24, s));
+        return note_foreign_stream(h, s);
+    }
+    BftCcScratch p;
+    CK(cc_scratch(h, h->n_kmers, h->n_sets, s, &p));
+    {
+        StageScope stage_scope(h, s);
+        CK(cc_run(h, genome_ids, nb_ids, s, (unsigned long long*)d_counts, p, (uint32_t*)d_labels, (uint64_t*)d_sizes, sizes_cap));
+    }
+    cc_release(h, s);
+    return note_foreign_stream(h, s);
+}
+
+// The host-buffer form: the components are counted on the device, and the outputs filled only when the caps hold them all.
+extern "C" int bft_gpu_components(bft_gpu* h, const uint32_t* genome_ids, uint32_t nb_ids, uint32_t* labels, uint64_t labels_cap, uint64_t* sizes,
+                                  uint64_t sizes_cap, uint64_t* counts) {
+    if (!h || !counts || (nb_ids && !genome_ids)) return fail(BFT_GPU_E_ARG, "NULL argument");
+    for (uint32_t j = 1; j < nb_ids; j++)
+        if (genome_ids[j] <= genome_ids[j - 1]) return fail(BFT_GPU_E_ARG, "components: genome ids must be strictly increasing");
+    ENTER(h);
+    CK(cc_prepare(h));
+    counts[0] = counts[1] = counts[2] = 0;
+    const uint64_t n = h->n_kmers;
+    if (n == 0) return BFT_GPU_OK;
+    const hipStream_t s = h->stream;
+    DevBuf dcnt;
+    CK(dcnt.alloc(24));
+    BftCcScratch p;
+    CK(cc_scratch(h, n, h->n_sets, s, &p));
+    StageScope stage_scope(h);
+    CK(cc_run(h, genome_ids, nb_ids, s, dcnt.as<unsigned long long>(), p, nullptr, nullptr, 0));
+    unsigned long long cnt[3] = {0, 0, 0};
+    HIPCK(hipMemcpyAsync(cnt, dcnt.p, 24, hipMemcpyDeviceToHost, s));
+    HIPCK(hipStreamSynchronize(s));
+    for (int i = 0; i < 3; i++) counts[i] = cnt[i];
+    if ((labels && labels_cap < n) || (sizes && sizes_cap < cnt[0])) {
+        cc_release(h, s);
+        return fail(BFT_GPU_E_NOSPACE, "component buffers too small");
+    }
+    DevBuf dsz;
+    if (sizes && cnt[0]) {  // (the counters are 32-bit in the scratch: widened by a second pass of the last kernel)
+        CK(dsz.alloc(cnt[0] * 8));
+        CK(timed_launch(h, s, [&] { return bft_cc_sizes(n, p, dsz.as<uint64_t>(), cnt[0], dcnt.as<unsigned long long>(), s); }));
+        HIPCK(hipMemcpyAsync(sizes, dsz.p, cnt[0] * 8, hipMemcpyDeviceToHost, s));
+    }
+    if (labels) HIPCK(hipMemcpyAsync(labels, p.num, n * 4, hipMemcpyDeviceToHost, s));
+    if (labels || sizes) HIPCK(hipStreamSynchronize(s));
+    cc_release(h, s);
     return BFT_GPU_OK;
 }
 

@@ -2,9 +2,8 @@
 // over the sorted T-form table tk (one row per stored k-mer, rows in the bft_gpu_extract order):
 //   k_sp_buckets  first row of every bucket of the top bits of the T-form: a lower bound in tk starts inside one bucket (about 40 rows on the
 //                 config-3 index) instead of the whole table
-//   k_sp_degrees  one lane per row u.  The four successors x[1..k-1]+N of u differ in the last nucleotide only, which sits in the two lowest bits of
-//                 the T-form (k % 9 != 0) or in bits 2-3 of the last block (k % 9 == 0, the block is rotated): they lie in one interval of at most
-//                 16 rows, found by ONE lower bound.  Out-degree and the successor's row come from that interval; in-degrees and predecessors
+//   k_sp_degrees  one lane per row u.  The four successors x[1..k-1]+N of u lie in one interval of at most 16 rows, found by ONE lower bound
+//                 (bft_for_each_successor, bft_succ.h).  Out-degree and the successor's row come from that interval; in-degrees and predecessors
 //                 are the same relation read backwards, so each successor found gets an atomic increment and u's row -- no second lookup
 //   k_sp_links    nodes (in <= 1, out <= 1, colour set of t genomes or more) and edges (u -> v: v is u's only successor, u is v's only
 //                 predecessor, both nodes, |C(u) & C(v)| >= t; the sorted id lists are merged, equal colour-set ids skip it), each decided
@@ -23,23 +22,11 @@
 
 #include "bft_dev.h"
 #include "bft_paths.h"
-#include "bft_walk.h"
+#include "bft_succ.h"
 
 namespace {
 
 constexpr int SP_THREADS = 256;
-
-// the top sb bits of a T-form (2k bits in W words, word 0 most significant)
-template <int W>
-__device__ __forceinline__ uint32_t sp_top(const uint64_t* t, int k, int sb) {
-    const int tb = 2 * k - 64 * (W - 1);  // bits in word 0
-    if (tb >= sb) return (uint32_t)(t[0] >> (tb - sb));
-    uint64_t w1 = 0;
-#pragma unroll
-    for (int w = 1; w < W; w++)
-        if (w == 1) w1 = t[1];
-    return (uint32_t)((t[0] << (sb - tb)) | (w1 >> (64 - (sb - tb))));
-}
 
 template <int W>
 __global__ __launch_bounds__(SP_THREADS) void k_sp_buckets(const uint64_t* __restrict__ tk, uint32_t n, int k, int sb, uint32_t* __restrict__ start) {
@@ -60,32 +47,14 @@ __global__ __launch_bounds__(SP_THREADS) void k_sp_buckets(const uint64_t* __res
 template <int W>
 __global__ __launch_bounds__(SP_THREADS) void k_sp_degrees(const uint64_t* __restrict__ tk, uint32_t n, int k, int sb, const uint32_t* __restrict__ start,
                                                            uint32_t* __restrict__ succ, uint32_t* __restrict__ indeg, uint32_t* __restrict__ pred) {
-    const int vo = (k % 9) ? 0 : 2;  // where the last nucleotide sits in the T-form's last word
-    const uint64_t wild = 3ull << vo;
     for (uint64_t u = blockIdx.x * (uint64_t)SP_THREADS + threadIdx.x; u < n; u += (uint64_t)gridDim.x * SP_THREADS) {
-        uint64_t t[W], x[W], y[W];
-        bft_load_row<W>(tk + u * W, t);
-        bft_x_from_tform<W>(t, k, x);
-        // the successor with nucleotide 0 last: drop the first nucleotide (the bits above 2k are zero, so the new last one is A)
-#pragma unroll
-        for (int w = 0; w < W; w++) y[w] = (x[w] >> 2) | (w + 1 < W ? x[w + 1] << 62 : 0ull);
-        bft_tform_from_x<W>(y, k, t);
-        const uint32_t b = sp_top<W>(t, k, sb), lo = start[b], hi = start[b + 1];
-        uint32_t r = lo + bft_rows_lower_bound<W>(tk + (uint64_t)lo * W, hi - lo, t);
         uint32_t cnt = 0, v = BFT_SP_NONE;
-        for (; r < n; r++) {
-            uint64_t c[W];
-            bft_load_row<W>(tk + (uint64_t)r * W, c);
-            bool same = true;
-#pragma unroll
-            for (int w = 0; w < W - 1; w++) same = same && c[w] == t[w];
-            if (!same || c[W - 1] > (t[W - 1] | wild)) break;  // (rows at or after t: past the interval)
-            if ((c[W - 1] & ~wild) != t[W - 1]) continue;
+        bft_for_each_successor<W>(tk, n, k, sb, start, u, [&](uint32_t r) {
             cnt++;
             v = r;
             atomicAdd(&indeg[r], 1u);
             pred[r] = (uint32_t)u;
-        }
+        });
         succ[u] = cnt == 0 ? BFT_SP_NONE : cnt == 1 ? v : BFT_SP_MANY;
     }
 }

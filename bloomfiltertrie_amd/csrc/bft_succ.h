@@ -1,0 +1,50 @@
+// bft_succ.h -- the successor search over the sorted T-form table tk shared by the whole-graph kernels (simple paths, bft_paths.hip; connected
+// components, bft_components.hip): the bucket of a T-form's top bits, and every stored successor x[1..k-1]+N of a row with ONE lower bound.
+// Device code only, header only.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "bft_dev.h"
+#include "bft_walk.h"
+
+// the top sb bits of a T-form (2k bits in W words, word 0 most significant)
+template <int W>
+__device__ __forceinline__ uint32_t sp_top(const uint64_t* t, int k, int sb) {
+    const int tb = 2 * k - 64 * (W - 1);  // bits in word 0
+    if (tb >= sb) return (uint32_t)(t[0] >> (tb - sb));
+    uint64_t w1 = 0;
+#pragma unroll
+    for (int w = 1; w < W; w++)
+        if (w == 1) w1 = t[1];
+    return (uint32_t)((t[0] << (sb - tb)) | (w1 >> (64 - (sb - tb))));
+}
+
+// f(r) for every stored successor r of row u, in ascending row.  The four successors of u differ in the last nucleotide only, which sits in the two
+// lowest bits of the T-form (k % 9 != 0) or in bits 2-3 of the last block (k % 9 == 0, the block is rotated): they lie in one interval of at most
+// 16 rows, found by ONE lower bound inside the bucket (start[], 2^sb + 1 entries) of the successor with nucleotide 0 last.
+template <int W, class F>
+__device__ __forceinline__ void bft_for_each_successor(const uint64_t* __restrict__ tk, uint32_t n, int k, int sb, const uint32_t* __restrict__ start,
+                                                       uint64_t u, F&& f) {
+    const int vo = (k % 9) ? 0 : 2;  // where the last nucleotide sits in the T-form's last word
+    const uint64_t wild = 3ull << vo;
+    uint64_t t[W], x[W], y[W];
+    bft_load_row<W>(tk + u * W, t);
+    bft_x_from_tform<W>(t, k, x);
+    // the successor with nucleotide 0 last: drop the first nucleotide (the bits above 2k are zero, so the new last one is A)
+#pragma unroll
+    for (int w = 0; w < W; w++) y[w] = (x[w] >> 2) | (w + 1 < W ? x[w + 1] << 62 : 0ull);
+    bft_tform_from_x<W>(y, k, t);
+    const uint32_t b = sp_top<W>(t, k, sb), lo = start[b], hi = start[b + 1];
+    uint32_t r = lo + bft_rows_lower_bound<W>(tk + (uint64_t)lo * W, hi - lo, t);
+    for (; r < n; r++) {
+        uint64_t c[W];
+        bft_load_row<W>(tk + (uint64_t)r * W, c);
+        bool same = true;
+#pragma unroll
+        for (int w = 0; w < W - 1; w++) same = same && c[w] == t[w];
+        if (!same || c[W - 1] > (t[W - 1] | wild)) break;  // (rows at or after t: past the interval)
+        if ((c[W - 1] & ~wild) != t[W - 1]) continue;
+        f(r);
+    }
+}

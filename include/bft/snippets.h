@@ -1,21 +1,25 @@
 /*
- * <bft/snippets.h> -- the simple-path snippets of GuillaumeHolley/BloomFilterTrie (reference include/snippets.h, src/snippets.c), served by
- * the MI355X library: one batched GPU pass over the whole index (bft_gpu_simple_paths, include/bft_gpu.h) instead of a walk that asks for
- * the successors, predecessors and marks of one k-mer at a time.
+ * <bft/snippets.h> -- the simple-path and connected-component snippets of GuillaumeHolley/BloomFilterTrie (reference include/snippets.h,
+ * src/snippets.c), served by the MI355X library: one batched GPU pass over the whole index (bft_gpu_simple_paths, bft_gpu_components,
+ * include/bft_gpu.h) instead of a walk that asks for the successors, predecessors and marks of one k-mer at a time.
  *
  * The paths are those bft_gpu_simple_paths defines: maximal chains of k-mers with in- and out-degree <= 1 (degrees over the whole graph),
  * each spelled as its first k-mer plus the last nucleotide of every following one; a cycle is cut before its k-mer of smallest row.  They are
  * written one per line in ascending row of their first k-mer (the order of iterate_over_kmers); the reference writes them in the order its
  * walk happens to reach them, and that order also decides where it starts a cycle (INTEGRATION.md lists every difference).
  *
+ * The traversals BFS, DFS, BFS_subgraph, DFS_subgraph, the predicate is_in_subgraph and get_nb_connected_component are declared in
+ * <bft/snippets_traversal.h>, which this header includes.
+ *
  * Not provided: the per-k-mer callbacks extract_simple_paths and extract_core_simple_paths (they need marking), the k-mer class extractors
- * extract_core_kmers / extract_dispensable_kmers / extract_singleton_kmers / extract_pangenome_kmers_to_disk, and the traversals BFS, DFS and
- * get_nb_connected_component (they need marking too; BFS is an empty stub in the reference).
+ * extract_core_kmers / extract_dispensable_kmers / extract_singleton_kmers / extract_pangenome_kmers_to_disk, cdbg_traversal and
+ * nb_connected_components as a callback (they need marking too).
  */
 #ifndef BFT_GPU_COMPAT_SNIPPETS_H
 #define BFT_GPU_COMPAT_SNIPPETS_H
 
 #include "bft.h"
+#include "snippets_traversal.h"
 
 #ifdef __cplusplus
 extern "C" {

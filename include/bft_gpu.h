@@ -322,6 +322,29 @@ int bft_gpu_simple_paths(bft_gpu* h, uint32_t min_shared, uint64_t* offsets, cha
 int bft_gpu_simple_paths_dev(bft_gpu* h, uint32_t min_shared, void* d_offsets, void* d_seqs, uint64_t paths_cap, uint64_t chars_cap, void* d_counts,
                              void* hip_stream);
 
+/* Connected components: get_nb_connected_component(bft, &nb, BFS | DFS) and (..., BFS_subgraph | DFS_subgraph, nb_id_genomes, ids...) (reference
+ * snippets.h, src/snippets.c:605-960) without the walk, over the whole graph (nb_ids = 0) or the sub-graph of genome_ids.
+ *   vertices  the stored k-mers; in a sub-graph, only the members: k-mers whose colour set holds EVERY id of genome_ids;
+ *   edges     x - y when y is a stored x[1..k-1]+N or a stored N+x[0..k-2] (the 8 neighbours of get_neighbors, undirected; not canonical); in
+ *             a sub-graph only between two members (the induced sub-graph: BFS_subgraph / DFS_subgraph mark non-members visited but never expand
+ *             or count them);
+ *   labels    components are numbered 0 .. n_components - 1 in ascending row of their smallest row (the bft_gpu_extract order); labels[row] is the
+ *             component of that row, 0xFFFFFFFF for a non-member.  Labels do not depend on scheduling.
+ * genome_ids (host, nb_ids of them) must be strictly increasing (BFT_GPU_E_ARG otherwise); an id at or above the number of genomes matches no k-mer.
+ * counts: {n_components, n_members, largest component in k-mers}.
+ * Host form: labels holds labels_cap entries (n_kmers are needed), sizes sizes_cap (n_components are needed): sizes[c] is the number of member
+ * k-mers of component c; with both NULL the call only counts; when a cap is too small nothing is written, counts is set and BFT_GPU_E_NOSPACE is
+ * returned.  Pending insertions are built first; the handle's answers do not change ("compact_table": the sorted table comes back, as for rows and
+ * prefixes).  Launches are counted in bft_gpu_kernel_time; with "build_stages" on, the call's steps become the stages bft_gpu_build_stages
+ * reports.  An empty index gives {0, 0, 0}.  At most 2^31 - 1 k-mers (BFT_GPU_E_LIMIT). */
+int bft_gpu_components(bft_gpu* h, const uint32_t* genome_ids, uint32_t nb_ids, uint32_t* labels, uint64_t labels_cap, uint64_t* sizes, uint64_t sizes_cap,
+                       uint64_t* counts);
+/* The same into device buffers on hip_stream (NULL = the handle's stream), without host synchronisation (genome_ids stays a host array: the ids
+ * travel as kernel arguments): d_counts (3 x uint64) always receives the counts; d_labels (may be NULL) n_kmers labels, d_sizes (may be NULL) the
+ * sizes of the components below sizes_cap.  The number of launches does not depend on the data.  Not inside a graph capture (BFT_GPU_E_ARG). */
+int bft_gpu_components_dev(bft_gpu* h, const uint32_t* genome_ids, uint32_t nb_ids, void* d_labels, void* d_sizes, uint64_t sizes_cap, void* d_counts,
+                           void* hip_stream);
+
 /* A colour set as the reference's annotation bytes -- BFT_annotation::annot as get_annotation returns it
  * (include/bft.h:97, src/bft.c:363-387): mode 0 (bitmap, genome g <-> bit g+2), 1 (ranges) or 2 (id list), chosen the way the
  * reference chooses it: compute_best_mode re-decides at every insertion of a genome id and keeps the current mode on a size tie
