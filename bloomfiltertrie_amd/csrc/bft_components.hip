@@ -19,6 +19,8 @@
 
 #include "bft_components.h"
 #include "bft_dev.h"
+#include "bft_handle.h"
+#include "bft_scan.h"
 #include "bft_succ.h"
 
 namespace {
@@ -234,4 +236,128 @@ int bft_cc_sizes(uint64_t n, const BftCcScratch& p, uint64_t* d_sizes, uint64_t 
     hipLaunchKernelGGL(k_cc_sizes, cc_grid(n), dim3(CC_THREADS), 0, s, (const uint32_t*)p.parent, d_sizes, sizes_cap, d_counts);
     HIPCK(hipGetLastError());
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the C-ABI entry points: the handle's scratch, the chain of launches, the host-buffer form
+// ------------------------------------------------------------------------------------------------
+// the arrays of a block with room for m rows and `sets` colour sets (p->sp.sb set), from `base` on; returns the block's size
+static size_t cc_carve(uint64_t m, uint64_t sets, uint8_t* base, BftCcScratch* p) {
+    Carver c{base};
+    c.take(p->sp.start, ((1ull << p->sp.sb) + 1) * 4);
+    c.take(p->parent, m * 4);
+    c.take(p->num, m * 4);
+    c.take(p->member, sets);
+    return c.off;
+}
+// The handle's scratch (h->cc: HandleScratch, bft_handle.h) for an index of n rows and n_sets colour sets on stream s: its own block, shared with no
+// other query, sized exactly.
+static int cc_scratch(bft_gpu* h, uint64_t n, uint64_t n_sets, hipStream_t s, BftCcScratch* p) {
+    CK(h->cc.acquire(s, false));  // (the entry points refuse a capturing stream)
+    p->sp = BftSpScratch{};
+    p->sp.sb = bft_sp_bucket_bits(h->k);
+    h->cc_m = std::max(n, h->cc_m);
+    h->cc_sets = std::max(n_sets, h->cc_sets);
+    CK(h->cc.grow(h->cc_buf, cc_carve(h->cc_m, h->cc_sets, nullptr, p), 0));
+    CK(h->cc.grow(h->cc_tmp, bft_scan::scratch_bytes(n + 1), 0));
+    cc_carve(h->cc_m, h->cc_sets, h->cc_buf.as<uint8_t>(), p);
+    return 0;
+}
+// Membership, forest, numbering, labels and sizes on stream s: d_counts = {n_components, n_members, largest} (24 bytes, device); the labels stay in
+// p.num, the sizes in p.parent.  d_labels / d_sizes (may be NULL): the labels, the sizes below sizes_cap.  The number of launches depends on nb alone.
+// With "build_stages" on, every step is a stage (bft_gpu_build_stages), its bytes those its algorithm reads and writes.
+static int cc_run(bft_gpu* h, const uint32_t* ids, uint32_t nb, hipStream_t s, unsigned long long* d_counts, const BftCcScratch& p, uint32_t* d_labels,
+                  uint64_t* d_sizes, uint64_t sizes_cap) {
+    const uint64_t n = h->n_kmers, ns = h->n_sets;
+    const int W = h->W, k = h->k;
+    const uint64_t* tk = h->d_tk.as<uint64_t>();
+    const double nd = (double)n, rowb = 8.0 * W;
+    CK(bft_zero_async(d_counts, 24, s));
+    for (uint32_t j = 0; j < nb; j += BFT_CC_IDS)
+        CK(bft_timed_launch(h, s, [&] { return bft_cc_sets(ns, h->d_cs_off.as<uint32_t>(), h->d_cs_ids.p, h->cs_w, ids + j, nb - j, j == 0, p, s); }));
+    if (nb) bft_stage("components: members among the colour sets", (double)ns * 9 + (double)h->n_ids * h->cs_w, s);
+    CK(bft_timed_launch(h, s, [&] { return bft_cc_init(n, nb ? h->d_tcol.as<uint32_t>() : nullptr, p, s); }));
+    bft_stage("components: members", nd * (4 + (nb ? 5 : 0)), s);
+    CK(bft_timed_launch(h, s, [&] { return bft_sp_buckets(W, tk, n, k, p.sp, s); }));
+    bft_stage("components: buckets of the table", (double)((1ull << p.sp.sb) + 1) * 4, s);
+    CK(bft_timed_launch(h, s, [&] { return bft_cc_hook(W, tk, n, k, p, s); }));
+    bft_stage("components: successors and hooking", nd * (2 * rowb + 4 + 4 + 8), s);
+    CK(bft_timed_launch(h, s, [&] { return bft_cc_flatten(n, p, s); }));
+    bft_stage("components: roots", nd * 12, s);
+    CK(bft_timed_launch(h, s, [&] { return bft_scan::exclusive_sum<uint32_t>(BftCcMember{p.parent}, p.num, n, s, h->cc_tmp, d_counts + 1, false); }));
+    CK(bft_timed_launch(h, s, [&] { return bft_scan::exclusive_sum<uint32_t>(BftCcRoot{p.parent}, p.num, n, s, h->cc_tmp, d_counts, false); }));
+    bft_stage("components: two scans (members, components)", nd * 16, s);
+    CK(bft_timed_launch(h, s, [&] { return bft_cc_label(n, p, d_labels, s); }));
+    bft_stage("components: labels", nd * (4 + 4 + 4 + 4 + (d_labels ? 4 : 0)), s);
+    CK(bft_timed_launch(h, s, [&] { return bft_cc_count(n, p, s); }));
+    bft_stage("components: sizes", nd * 4, s);
+    CK(bft_timed_launch(h, s, [&] { return bft_cc_sizes(n, p, d_sizes, sizes_cap, d_counts, s); }));
+    bft_stage("components: sizes out, largest", 0.0, s);  // (n_components entries: not known on the host without a read-back)
+    return 0;
+}
+static int cc_prepare(bft_gpu* h) {
+    CK(bft_ensure_built(h));  // ("compact_table": the sorted table comes back, as for rows, prefixes and simple paths)
+    if (h->n_kmers >= (1ull << 31)) return bft_fail(BFT_GPU_E_LIMIT, "components: at most 2^31 - 1 k-mers");
+    return 0;
+}
+
+extern "C" int bft_gpu_components_dev(bft_gpu* h, const uint32_t* genome_ids, uint32_t nb_ids, void* d_labels, void* d_sizes, uint64_t sizes_cap, void* d_counts,
+                                      void* hip_stream) {
+    if (!h || !d_counts || (nb_ids && !genome_ids)) return bft_fail(BFT_GPU_E_ARG, "NULL argument");
+    for (uint32_t j = 1; j < nb_ids; j++)
+        if (genome_ids[j] <= genome_ids[j - 1]) return bft_fail(BFT_GPU_E_ARG, "components: genome ids must be strictly increasing");
+    ENTER(h);
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
+    if (bft_stream_capturing(s)) return bft_fail(BFT_GPU_E_ARG, "components recorded into a graph: not supported (the table may have to come back, scratch may grow)");
+    CK(cc_prepare(h));
+    if (h->n_kmers == 0) {
+        CK(bft_zero_async(d_counts, 24, s));
+        return bft_note_foreign_stream(h, s);
+    }
+    BftCcScratch p;
+    CK(cc_scratch(h, h->n_kmers, h->n_sets, s, &p));
+    {
+        StageScope stage_scope(h, s);
+        CK(cc_run(h, genome_ids, nb_ids, s, (unsigned long long*)d_counts, p, (uint32_t*)d_labels, (uint64_t*)d_sizes, sizes_cap));
+    }
+    h->cc.release();
+    return bft_note_foreign_stream(h, s);
+}
+
+// The host-buffer form: the components are counted on the device, and the outputs filled only when the caps hold them all.
+extern "C" int bft_gpu_components(bft_gpu* h, const uint32_t* genome_ids, uint32_t nb_ids, uint32_t* labels, uint64_t labels_cap, uint64_t* sizes,
+                                  uint64_t sizes_cap, uint64_t* counts) {
+    if (!h || !counts || (nb_ids && !genome_ids)) return bft_fail(BFT_GPU_E_ARG, "NULL argument");
+    for (uint32_t j = 1; j < nb_ids; j++)
+        if (genome_ids[j] <= genome_ids[j - 1]) return bft_fail(BFT_GPU_E_ARG, "components: genome ids must be strictly increasing");
+    ENTER(h);
+    CK(cc_prepare(h));
+    counts[0] = counts[1] = counts[2] = 0;
+    const uint64_t n = h->n_kmers;
+    if (n == 0) return BFT_GPU_OK;
+    const hipStream_t s = h->stream;
+    DevBuf dcnt;
+    CK(dcnt.alloc(24));
+    BftCcScratch p;
+    CK(cc_scratch(h, n, h->n_sets, s, &p));
+    StageScope stage_scope(h);
+    CK(cc_run(h, genome_ids, nb_ids, s, dcnt.as<unsigned long long>(), p, nullptr, nullptr, 0));
+    unsigned long long cnt[3] = {0, 0, 0};
+    HIPCK(hipMemcpyAsync(cnt, dcnt.p, 24, hipMemcpyDeviceToHost, s));
+    HIPCK(hipStreamSynchronize(s));
+    for (int i = 0; i < 3; i++) counts[i] = cnt[i];
+    if ((labels && labels_cap < n) || (sizes && sizes_cap < cnt[0])) {
+        h->cc.release();
+        return bft_fail(BFT_GPU_E_NOSPACE, "component buffers too small");
+    }
+    DevBuf dsz;
+    if (sizes && cnt[0]) {  // (the counters are 32-bit in the scratch: widened by a second pass of the last kernel)
+        CK(dsz.alloc(cnt[0] * 8));
+        CK(bft_timed_launch(h, s, [&] { return bft_cc_sizes(n, p, dsz.as<uint64_t>(), cnt[0], dcnt.as<unsigned long long>(), s); }));
+        HIPCK(hipMemcpyAsync(sizes, dsz.p, cnt[0] * 8, hipMemcpyDeviceToHost, s));
+    }
+    if (labels) HIPCK(hipMemcpyAsync(labels, p.num, n * 4, hipMemcpyDeviceToHost, s));
+    if (labels || sizes) HIPCK(hipStreamSynchronize(s));
+    h->cc.release();
+    return BFT_GPU_OK;
 }

@@ -1,5 +1,5 @@
-// bft_gpu.hip -- the C-ABI of include/bft_gpu.h: handle, device-memory cache, insertion log, bulk build, query entry points,
-// residency / probe tuning, .bft files, image replication.  One translation unit with its device code:
+// bft_gpu.hip -- the C-ABI of include/bft_gpu.h: handle (bft_handle.h), device-memory cache, insertion log, bulk build, k-mer and sequence query entry
+// points, residency / probe tuning, .bft files, image replication (prefixes, sub-graphs, paths, components: beside their kernels).  With its device code:
 //   bft_kernels_query.h  k_pack_to_tform (packed 2-bit k-mers -> T-form words: the per-level rev[]/rotation work of
 //                        src/presenceNode.c:1327-1371 done once per k-mer), k_query_kh / k_branching_kh (the same queries through the
 //                        k-mer hash: one cache line per k-mer), k_query / k_query8 / k_query6 (batched isKmerPresent as a container walk,
@@ -27,16 +27,14 @@
 #include "../../include/bft_gpu.h"
 #include "bft_dev.h"
 #include "bft_file.h"
+#include "bft_handle.h"
 #include "bft_hash.h"
 #include "bft_image.h"
 #include "bft_index.h"
 #include "bft_kh.h"
-#include "bft_components.h"
 #include "bft_paths.h"
-#include "bft_prefix.h"
 #include "bft_scan.h"
 #include "bft_sort.h"
-#include "bft_subgraph.h"
 #include "bft_walk.h"
 
 #define BFT_BLOCK 256
@@ -54,7 +52,7 @@ int bft_fail(int code, const std::string& msg) {
 }
 static int fail(int code, const std::string& msg) { return bft_fail(code, msg); }
 
-static double now_ms() {
+double bft_now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 // BFT_GPU_TRACE_BUILD=1: host-side timeline of bft_gpu_build on stderr (where the host waits, allocates, reads counts back)
@@ -63,7 +61,7 @@ static double g_trace_t0 = 0, g_trace_last = 0;
 bool bft_trace_on(void) { return g_trace; }
 void bft_trace_mark(const char* what) {
     if (!g_trace) return;
-    const double t = now_ms();
+    const double t = bft_now_ms();
     if (!what) { g_trace_t0 = g_trace_last = t; return; }
     fprintf(stderr, "[bft_gpu build] %8.3f ms (+%.3f) %s\n", t - g_trace_t0, t - g_trace_last, what);
     g_trace_last = t;
@@ -175,11 +173,11 @@ int bft_pool_alloc(void** p, size_t n, size_t* cap) {
         *cap = take.cap;
         return 0;
     }
-    const double t_m0 = now_ms();
+    const double t_m0 = bft_now_ms();
     hipError_t e = hipMalloc(p, n);
     {
         std::lock_guard<std::mutex> lk(g_pool_mu);
-        g_malloc_ms += now_ms() - t_m0;
+        g_malloc_ms += bft_now_ms() - t_m0;
         g_malloc_calls++;
     }
     if (e != hipSuccess) {
@@ -212,10 +210,10 @@ void bft_pool_release(void* p, size_t cap) {
             keep = false;
     }
     if (!keep) {
-        const double t0 = now_ms();
+        const double t0 = bft_now_ms();
         (void)hipFree(p);
         std::lock_guard<std::mutex> lk(g_pool_mu);
-        g_free_ms += now_ms() - t0;
+        g_free_ms += bft_now_ms() - t0;
         g_free_calls++;
     }
 }
@@ -251,192 +249,20 @@ extern "C" uint64_t bft_gpu_cache_release(void) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// handle
+// handle (struct bft_gpu: bft_handle.h)
 // ------------------------------------------------------------------------------------------------
-struct bft_gpu {
-    int k = 0, L = 0, W = 0, B = 0, device = 0, r1 = 0, r2 = 0;
-    hipStream_t stream = nullptr;
-    std::vector<std::string> genomes;
-    uint32_t max_gid_seen = 0;
-    bool any_insert = false;
-    bool log_g_sorted = true;   // the log's genome ids are non-decreasing
-    uint32_t log_last_gid = 0;
-    uint64_t opt_flush_pairs = 1ull << 30;  // "flush_pairs": the log is merged into the index before it holds this many pairs
-
-    // Small host batches (the per-k-mer calls of <bft/bft.h>, 4096-byte file chunks): a pinned, device-mapped staging
-    // block the kernels read and write directly -- one launch + one stream wait instead of two staged copies around it.
-    uint8_t* pin = nullptr;  // [PIN_IN bytes of k-mers | bits | rows | colour sets]
-    // Host batches of insertKmers up to a megabyte (a genome of a many-colour collection: 2000 calls of 20 000 k-mers on config 5): a ring
-    // of pinned, device-mapped slots -- the batch is copied into the next slot, the packing kernel reads it there over the link, an
-    // event says when the slot is free again; nothing waits for the GPU (95 -> ~35 us per call).
-    static constexpr size_t RING_SLOT = (size_t)1 << 20;
-    static constexpr int RING_SLOTS = 8;
-    uint8_t* ring = nullptr;
-    hipEvent_t ring_ev[RING_SLOTS] = {};
-    bool ring_busy[RING_SLOTS] = {};
-    int ring_next = 0;
-    ~bft_gpu() {
-        if (pin) (void)hipHostFree(pin);
-        for (int i = 0; i < RING_SLOTS; i++)
-            if (ring_ev[i]) (void)hipEventDestroy(ring_ev[i]);
-        if (ring) (void)hipHostFree(ring);
-        if (kh_ctr) (void)hipFree(kh_ctr);
-        for (int i = 0; i < KH_CTR_SLOTS; i++)
-            if (kh_ctr_ev[i]) (void)hipEventDestroy(kh_ctr_ev[i]);
-    }
-
-    // pending insert log (SoA: W key arrays of log_cap entries, then genome ids)
-    DevBuf log_k, log_g;
-    uint64_t log_n = 0, log_cap = 0;
-    // One-word keys with room for a genome id beside them (k <= 28: 63 - 2k >= 7 bits) are logged as the COMPOSITES T << log_gb | genome the build's
-    // root-prefix split sorts: 8 bytes per pair written at insert time and read by the split's histogram and first pass instead of 12 (no id array:
-    // log_g stays empty).  A genome id beyond 2^log_gb, ids that do not ascend, or the general sort ("build_composite" 0) turn the log back
-    // into k-mers + ids first (k_log_decompose).
-    bool log_comp = false;
-    uint32_t log_gb = 0;
-    // the insert calls behind the log: positions [lb_end[j - 1], lb_end[j]) carry genome lb_gid[j] -- the multi-word sort reads a pair's id out of this
-    // table (a search in a few cached words) instead of gathering it from the log (a fabric request per pair)
-    std::vector<uint64_t> lb_end;
-    std::vector<uint32_t> lb_gid;
-    int opt_comp_log = 1;  // "composite_log": 0 = always k-mers + ids (a test hook: same image)
-
-    uint64_t n_pairs = 0;  // distinct (k-mer, genome) pairs the index holds = sum of the sizes of its k-mers' colour sets
-
-    // image
-    bool built = false;
-    uint64_t n_kmers = 0;
-    DevBuf d_hashmod, d_nodes, d_bfT, d_ccs, d_f2w, d_clus, d_child, d_tk, d_tcol, d_uck, d_ucrow, d_cs_off, d_cs_ids, d_cs_bm;
-    DevBuf d_ccx, d_f18, d_fent;  // derived: flat form of the big CCs (bft_flatten_gpu)
-    DevBuf d_rdir, d_rstart;      // derived: root direct table (BFT_RDIR_*, k_root_direct) and root range table (BFT_RSTART_*), optional
-    DevBuf d_rq;                  // derived: root quartile table (BFT_RQ_*, k_root_quartiles), optional
-    int opt_root_quartiles = 1;   // "root_quartiles"
-    bool rq_ok = false;
-    DevBuf d_nph;                 // derived: node prefix hash (BFT_NPH_*, k_nph_fill), optional
-    int opt_node_hash = 1;        // "node_hash": 1 = derived when the image has no k-mer hash (the walk then answers every query), 2 = always, 0 = never
-    uint64_t nph_inserted = 0, nph_dropped = 0;
-    DevBuf d_kh, d_rspec;         // derived: k-mer hash (BFT_KH_*, bft_kh_build), optional; one "special" bit per root prefix for the walk (sync_walk_kh)
-    DevBuf d_kh_ovf_k, d_kh_ovf_v; // its overflow list (sorted k-mers, values)
-    uint32_t kh_ovf_n = 0;
-    uint64_t kh_lines = 0;        // home lines
-    bool opt_kmer_hash = true;    // "kmer_hash"
-    bool opt_walk_hash = false;   // "walk_hash": presence / colour queries through the container walk, which looks plain root groups up in the table's regions
-    bool opt_compact = true;      // "compact_table" (default on): the sorted table and the colour set per k-mer are dropped once the k-mer hash holds them (ensure_table)
-    bool table_dropped = false;   // d_tk / d_tcol are not resident: the k-mer hash is the only copy
-    uint32_t opt_kh_load = 55;    // "kmer_hash_load": per cent of the slots of the home lines in use (55: 47.9 G k-mers/s at 15.0 B per k-mer on the config-4 share;
-                                  // 50: 48.4 / 16.6; 60: 45.7 / 13.5; 70: 39.3 / 11.7 -- profiles/r04/kh_forms.jsonl)
-    double kh_ms = 0;             // GPU time of the last fill
-    hipStream_t stream2 = nullptr; // bft_gpu_build fills the k-mer hash here while the containers are assembled on `stream`
-    int opt_root_direct = 3;      // "root_direct": 0 = containers, 1 = direct table, 2 = direct table + range table, 3 = 1 or 2, whichever
-                                  // measured faster on this image (tune_residency)
-    bool rstart_ok = false;       // d_rstart holds the range table of the current image
-    int tuned_rstart = -1;        // result of that measurement (-1 = none)
-    double rstart_tune_ms[2] = {0, 0};
-    uint64_t n_f18 = 0, n_fent = 0;
-    uint32_t opt_flat_min = BFT_TRESH_SUF_PREF;  // CCs with at least this many prefixes get the flat form ("flat_min")
-    bool has_cs_bm = false, cs_bm_tried = false;
-    bool opt_no_composite = false;  // test hook ("build_composite" 0): the general sort + flag-array path also for ordered one-word keys
-    uint32_t front_redone = 0;      // root-prefix buckets of the last build whose order check failed (bft_front.hip)
-    int opt_msd = 1;                // "build_msd": root-prefix buckets + bucket sorts for 2^20 pairs and more (1), always (2: test hook), never (0)
-    uint32_t msd_max_bucket = 0;    // largest root-prefix bucket of the last build's sort (0: one device-wide sort)
-    BftImage im;
-    std::vector<uint32_t> hashmod;
-    std::vector<uint32_t> cs_off, cs_ids;  // host copy of the colour-set dictionary, fetched on first use (host_colorsets)
-    uint64_t n_sets = 0, n_ids = 0;
-    uint32_t cs_w = 4;  // bytes per genome id of the resident dictionary d_cs_ids (1 / 2 / 4: narrow_ids)
-    bool cs_on_host = false;
-    uint64_t info[16] = {0};
-    double build_ms[5] = {0, 0, 0, 0, 0};
-
-    // kernel timing: off until bft_gpu_kernel_time / set_option("timing", 1) asks for it; events are pooled per handle
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending_ev;
-    std::vector<hipEvent_t> free_ev;
-    double kernel_ms = 0;
-    uint64_t kernel_launches = 0;
-    bool timing = false;
-    // last work the *_dev entry points put on a caller's stream: image arrays are not released or rewritten before it is done
-    struct ExtEv { hipStream_t stream; hipEvent_t ev; bool pending; };
-    std::vector<ExtEv> ext;  // one event per caller stream seen (a double-buffered caller alternates between two: neither call blocks the host)
-    uint32_t root_ncc = 0;
-    uint64_t idx_sizes[9] = {0};
-    // The container walk (k_query*): how it sits on a CU and how it probes suffix groups.  0 = by rule from the shape of the index
-    // (default_launch_shape), or -- after bft_gpu_set_option("tune", 1) -- as measured on the image (tune_residency).
-    int opt_wgs_per_cu = 0;   // 1 / 2 workgroups of 1024 threads per CU, 3 = two of 768
-    int tuned_wgs = 0;
-    int opt_probe = 0;        // suffix-group probe: 4 or 8 rows per block (BftImage::probe_big)
-    int tuned_probe = 0;
-    double tune_ms[3] = {0, 0, 0};  // best time of the tuning batch per residency 1 / 2 / 3
-    int opt_grid_mult = 1;    // grid = resident workgroups x this
-    // The k-mer hash kernels claim their blocks of k-mers from a counter instead of splitting them by workgroup number (k_query_kh,
-    // bft_kh.hip): one counter per stream that launches them -- launches of one stream follow each other, so a counter has one user at
-    // a time; it only grows, every launch with a range of its own (bft_claims.h).  Batches too small to matter take the static split.
-    int opt_query_dynamic = 1;
-    uint64_t opt_query_dynamic_min = (uint64_t)1 << 16;  // batches below this many k-mers (lines of work for the branching kernel) keep the static split
-    uint64_t claims_static_launches = 0;  // launches that wanted a counter and found every slot taken by streams with work still in flight
-    uint32_t opt_query_chunk = 4;  // largest claim, in blocks of 256 k-mers (4 = every claim: the smaller the window of the query stream the
-                                   // resident workgroups read at a time, the better -- 2.61 / 2.62 / 2.65 / 2.70 ms at 4 / 16 / 32 / 64)
-    static constexpr int KH_CTR_SLOTS = 32;
-    unsigned long long* kh_ctr = nullptr;  // (its own hipMalloc, not a block of the cache: nothing that was released while still in flight may write here)
-    hipStream_t kh_ctr_stream[KH_CTR_SLOTS] = {};
-    unsigned long long kh_ctr_base[KH_CTR_SLOTS] = {};  // where the next launch's range of the slot's counter starts (bft_claims.h)
-    uint64_t kh_ctr_tick[KH_CTR_SLOTS] = {};            // last use: a handle queried on more streams than slots recycles the least recently used
-    uint64_t kh_ctr_clock = 0;
-    hipEvent_t kh_ctr_ev[KH_CTR_SLOTS] = {};            // end of the slot's last launch (recorded once half of the slots are in use)
-    int kh_ctr_pending = -1;
-    int kh_ctr_used = 0;
-    bool kh_ctr_failed = false;
-    DevBuf sq_codes, sq_bad, sq_npos, sq_poff, sq_tmp, sq_cs, sq_tile;  // scratch of the sequence queries (grown, never shrunk)
-    hipStream_t sq_stream = nullptr;
-    bool sq_used = false;
-    uint64_t sq_units = 0;
-    DevBuf qc_cs, qc_tmp;            // scratch of the resident colour-list queries: colour-set id per k-mer, the scan's temporary (grown, never shrunk)
-    DevBuf qc_kh;                    // k_colors_kh's tile counter and states (bft_kh_colors_scratch_bytes): not qc_tmp, whose bft_scan state (tag) it would corrupt
-    hipStream_t qc_stream = nullptr;
-    hipEvent_t qc_ev = nullptr;  // where the last use of the scratch ends (the stream it ran on is the caller's: it may be gone by the next call)
-    bool qc_used = false;  // bound on the blocks of k-mer positions the sequence kernel deals out (claim_counters)
-    DevBuf pm_buf, pm_tmp;         // scratch of the prefix queries (BftPmScratch, bft_prefix.h) and their scans' temporary (grown, never shrunk)
-    uint64_t pm_n = 0;             // prefixes pm_buf has room for
-    hipStream_t pm_stream = nullptr;
-    hipEvent_t pm_ev = nullptr;    // where the last use of that scratch ends
-    bool pm_used = false;
-    DevBuf sp_buf, sp_tmp;         // scratch of the simple paths (BftSpScratch, bft_paths.h) and their scans' temporary (grown, never shrunk)
-    uint64_t sp_m = 0;             // rows sp_buf has room for
-    hipStream_t sp_stream = nullptr;
-    hipEvent_t sp_ev = nullptr;    // where the last use of that scratch ends
-    bool sp_used = false;
-    DevBuf cc_buf, cc_tmp;         // scratch of the connected components (BftCcScratch, bft_components.h) and their scans' temporary (grown, never shrunk)
-    uint64_t cc_m = 0, cc_sets = 0; // rows and colour sets cc_buf has room for
-    hipStream_t cc_stream = nullptr;
-    hipEvent_t cc_ev = nullptr;    // where the last use of that scratch ends
-    bool cc_used = false;
-    bool inject_build_failure = false;  // test hook: the next bft_gpu_build fails right before its commit point (one shot)
-    bool opt_build_stages = false;      // "build_stages": the next builds record GPU time and bytes per stage (bft_gpu_build_stages)
-    struct Stage { std::string name; double ms, bytes; };
-    std::vector<Stage> stages;          // of the last build
-};
-
 static int grid_for(uint64_t nblk) { return bft_grid_for(nblk); }
 // rows per probe block of the suffix-group search ("query_probe": 4 or 8) -> BftImage::probe_big
 static uint32_t probe_mode(int rows) { return rows == 8 ? 1u : 0u; }
 
-static int set_device(bft_gpu* h) {
+int bft_set_device(bft_gpu* h) {
     HIPCK(hipSetDevice(h->device));
     bft_pool_set_stream(h->device, h->stream);
     return 0;
 }
 
-// Every ABI call makes the handle's GPU current; the caller's current device is put back when the call returns.
-struct DeviceScope {
-    int prev = -1;
-    DeviceScope() { if (hipGetDevice(&prev) != hipSuccess) { prev = -1; (void)hipGetLastError(); } }
-    ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-#define ENTER(h)     \
-    DeviceScope ds_; \
-    CK(set_device(h))
-
-// A *_dev entry point launched on a caller's stream: remember where that work ends.
 #define BFT_MAX_EXT_STREAMS 8
-static int note_foreign_stream(bft_gpu* h, hipStream_t s) {
+int bft_note_foreign_stream(bft_gpu* h, hipStream_t s) {
     if (s == h->stream) return 0;
     bft_gpu::ExtEv* slot = nullptr;
     for (auto& e : h->ext)
@@ -528,7 +354,7 @@ static void drain_events(bft_gpu* h) {
 }
 
 // Timed launches: a pair of pooled events around the kernel (no event is created on the launch path once the pool is warm).
-static int timing_begin(bft_gpu* h, hipStream_t s, hipEvent_t* e0, hipEvent_t* e1) {
+int bft_timing_begin(bft_gpu* h, hipStream_t s, hipEvent_t* e0, hipEvent_t* e1) {
     *e0 = *e1 = nullptr;
     if (!h->timing) return 0;
     if (h->pending_ev.size() >= 4096) drain_events(h);
@@ -539,18 +365,11 @@ static int timing_begin(bft_gpu* h, hipStream_t s, hipEvent_t* e0, hipEvent_t* e
     HIPCK(hipEventRecord(*e0, s));
     return 0;
 }
-static int timing_end(bft_gpu* h, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+int bft_timing_end(bft_gpu* h, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
     if (!e0) return 0;
     HIPCK(hipEventRecord(e1, s));
     h->pending_ev.push_back({e0, e1});
     return 0;
-}
-template <class F>
-static int timed_launch(bft_gpu* h, hipStream_t s, F&& launch) {
-    hipEvent_t e0, e1;
-    CK(timing_begin(h, s, &e0, &e1));
-    CK(launch());
-    return timing_end(h, s, e0, e1);
 }
 
 extern "C" void bft_gpu_free(bft_gpu* h) {
@@ -564,10 +383,6 @@ extern "C" void bft_gpu_free(bft_gpu* h) {
     h->free_ev.clear();
     for (auto& e : h->ext) (void)hipEventDestroy(e.ev);
     h->ext.clear();
-    if (h->qc_ev) { (void)hipEventDestroy(h->qc_ev); h->qc_ev = nullptr; }
-    if (h->pm_ev) { (void)hipEventDestroy(h->pm_ev); h->pm_ev = nullptr; }
-    if (h->sp_ev) { (void)hipEventDestroy(h->sp_ev); h->sp_ev = nullptr; }
-    if (h->cc_ev) { (void)hipEventDestroy(h->cc_ev); h->cc_ev = nullptr; }
     const hipStream_t s = h->stream;
     if (s) (void)hipStreamSynchronize(s);
     if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); h->stream2 = nullptr; }
@@ -678,7 +493,7 @@ static int insert_dev(bft_gpu* h, const void* d_kmers, uint64_t n, uint32_t id_g
     case 3: CK(launch_pack<3>(h, p, n, id_genome, run)); break;
     default: CK(launch_pack<4>(h, p, n, id_genome, run)); break;
     }
-    if (ordered) CK(note_foreign_stream(h, s));
+    if (ordered) CK(bft_note_foreign_stream(h, s));
     else if (!own_async) HIPCK(hipStreamSynchronize(h->stream));
     if (h->log_n > 0 && id_genome < h->log_last_gid) h->log_g_sorted = false;
     h->log_last_gid = id_genome;
@@ -737,10 +552,8 @@ static int bits_for(uint64_t v) {
     return b;
 }
 
-// Stable LSD sort of `total` entries by (keys word 0..W-1 as one big integer, then g).
-// keys: SoA with stride `stride`.  Result in okeys (stride ostride) / og.
-static int sort_pairs(bft_gpu* h, const uint64_t* keys, uint64_t stride, const uint32_t* g, uint64_t total, uint64_t* okeys,
-                      uint64_t ostride, uint32_t* og, bool g_already_ordered, bool is_log = false) {
+int bft_sort_pairs(bft_gpu* h, const uint64_t* keys, uint64_t stride, const uint32_t* g, uint64_t total, uint64_t* okeys, uint64_t ostride, uint32_t* og,
+                   bool g_already_ordered, bool is_log) {
     const int W = h->W;
     if (W == 1) {
         // one-word keys: sort the (key, genome) pairs themselves; the radix sort is stable, so a genome-id pass
@@ -994,30 +807,6 @@ static void derive_node_hash(bft_gpu* h) {
     h->im.nph_no_uc = st[2] == 0 ? 1u : 0u;
 }
 
-// The build of the k-mer hash for a table (tk, tcol) that is complete on the device, started on the handle's second stream: the build
-// assembles the containers on `stream` meanwhile.  The build sorts and gathers and starves what runs beside it of memory bandwidth and
-// latency (k_prefix_flags over the whole table: 0.2 ms alone, 2.8 ms beside it; the root's single-workgroup k_assign_cc: 0.8 -> 3.5 ms),
-// so it starts behind those (`after`: an event of the assembly stream) and overlaps the chain of small kernels and read-back counts that
-// follows.  kh_finish waits for it.  Any failure just leaves the image without the table.
-struct KhFill {
-    DevBuf buf, status, ovf_k, ovf_v;
-    BftKhScratch scratch;
-    BftKhGeo geo;
-    uint64_t lines_cap = 0, lines_used = 0;
-    uint32_t ovf_n = 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr, ew = nullptr;
-    hipStream_t s2 = nullptr;
-    bool started = false, prepared = false;
-    std::thread prep;  // kh_prepare_async
-    KhFill() { memset(&geo, 0, sizeof(geo)); }
-    ~KhFill() {  // (a build that fails half-way: the fill must be over before its buffers go back to the cache)
-        if (prep.joinable()) prep.join();
-        if (started && s2) (void)hipStreamSynchronize(s2);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        if (ew) (void)hipEventDestroy(ew);
-    }
-};
 static bool kh_wanted(const bft_gpu* h, uint64_t nk) { return h->opt_kmer_hash && nk > 0 && nk < (1ull << 31); }
 static bool kh_geo_ok(const bft_gpu* h, const BftKhGeo& g) { return bft_kh_has_kernels(h->W, g.S) && g.nl + BFT_KH_TAIL_LINES < (1ull << 32); }
 // the host side of the build that needs no table yet: the second stream, the table's memory, the events (a millisecond of driver
@@ -1190,7 +979,7 @@ static void drop_table(bft_gpu* h) {
     h->im.tcol = nullptr;
     h->info[12] = image_bytes(h);
 }
-static int ensure_table(bft_gpu* h) {
+int bft_ensure_table(bft_gpu* h) {
     if (!h->table_dropped) return 0;
     CK(wait_foreign_stream(h));
     const uint64_t n = h->n_kmers;
@@ -1211,7 +1000,7 @@ static int ensure_table(bft_gpu* h) {
     } else {  // two-word keys: the build's permutation sort (words apart, as the dump wrote them), then rows of two words
         DevBuf sorted;
         CK(sorted.alloc(n * W * 8));
-        CK(sort_pairs(h, keys.as<uint64_t>(), n, vals.as<uint32_t>(), n, sorted.as<uint64_t>(), n, tcol.as<uint32_t>(), true));
+        CK(bft_sort_pairs(h, keys.as<uint64_t>(), n, vals.as<uint32_t>(), n, sorted.as<uint64_t>(), n, tcol.as<uint32_t>(), true));
         hipLaunchKernelGGL(k_rows_from_words, dim3(grid_for((n + 255) / 256)), dim3(256), 0, h->stream, sorted.as<uint64_t>(), n, W, tk.as<uint64_t>());
         HIPCK(hipGetLastError());
     }
@@ -1452,42 +1241,34 @@ static int split_dedupe_w1(bft_gpu* h, const uint64_t* src_k, const uint32_t* sr
     return 0;
 }
 
-// "build_stages": the marks of one bft_gpu_build (bft_stage) become the handle's stage table when the build returns, however it returns
-struct StageScope {
-    bft_gpu* h;
-    explicit StageScope(bft_gpu* hh, hipStream_t s = nullptr) : h(hh) {  // (s: the stream the first stage runs on, when not the handle's)
-        t_stages_on = h->opt_build_stages;
-        t_stage_marks.clear();
-        if (t_stages_on) bft_stage("start", 0, s ? s : h->stream);
+StageScope::StageScope(bft_gpu* hh, hipStream_t s) : h(hh) {
+    t_stages_on = h->opt_build_stages;
+    t_stage_marks.clear();
+    if (t_stages_on) bft_stage("start", 0, s ? s : h->stream);
+}
+StageScope::~StageScope() {
+    if (!t_stages_on) return;
+    t_stages_on = false;
+    h->stages.clear();
+    (void)hipStreamSynchronize(h->stream);
+    if (h->stream2) (void)hipStreamSynchronize(h->stream2);
+    for (size_t i = 0; i < t_stage_marks.size(); i++) {
+        float ms = 0;
+        // a mark on the second stream ("+name": work that runs beside the main chain) is timed from the build's start
+        const bool side = !t_stage_marks[i].name.empty() && t_stage_marks[i].name[0] == '+';
+        size_t prev = 0;
+        if (!side) for (size_t j = i; j-- > 0;) if (t_stage_marks[j].name[0] != '+') { prev = j; break; }
+        if (i > 0 && hipEventSynchronize(t_stage_marks[i].ev) == hipSuccess &&
+            hipEventElapsedTime(&ms, t_stage_marks[prev].ev, t_stage_marks[i].ev) == hipSuccess)
+            h->stages.push_back({t_stage_marks[i].name, (double)ms, t_stage_marks[i].bytes});
+        (void)hipGetLastError();
     }
-    ~StageScope() {
-        if (!t_stages_on) return;
-        t_stages_on = false;
-        h->stages.clear();
-        (void)hipStreamSynchronize(h->stream);
-        if (h->stream2) (void)hipStreamSynchronize(h->stream2);
-        for (size_t i = 0; i < t_stage_marks.size(); i++) {
-            float ms = 0;
-            // a mark on the second stream ("+name": work that runs beside the main chain) is timed from the build's start
-            const bool side = !t_stage_marks[i].name.empty() && t_stage_marks[i].name[0] == '+';
-            size_t prev = 0;
-            if (!side) for (size_t j = i; j-- > 0;) if (t_stage_marks[j].name[0] != '+') { prev = j; break; }
-            if (i > 0 && hipEventSynchronize(t_stage_marks[i].ev) == hipSuccess &&
-                hipEventElapsedTime(&ms, t_stage_marks[prev].ev, t_stage_marks[i].ev) == hipSuccess)
-                h->stages.push_back({t_stage_marks[i].name, (double)ms, t_stage_marks[i].bytes});
-            (void)hipGetLastError();
-        }
-        for (auto& m : t_stage_marks) t_stage_pool.push_back(m.ev);
-        t_stage_marks.clear();
-    }
-};
+    for (auto& m : t_stage_marks) t_stage_pool.push_back(m.ev);
+    t_stage_marks.clear();
+}
 
-// Steps 5-7 of a build, from the point where the sorted table tk (nk rows), the colour set per row n_tcol and the dictionary n_cs_off / n_cs_ids
-// (32-bit ids) are final: containers, flat forms, k-mer hash (on the second stream), narrowing, commit into h, root tables.  Shared by
-// bft_gpu_build and bft_gpu_subgraph.  khf: the k-mer hash fill (prepared or not); tail / seg_off / npg: the interning's deferred tail and
-// its input (a default tail -- nothing pending -- where there was no interning); t0 / t1: start and end of the sort (bft_gpu_build_time).
-static int commit_image(bft_gpu* h, DevBuf& tk, DevBuf& n_tcol, DevBuf& n_cs_off, DevBuf& n_cs_ids, uint64_t nk, uint64_t n_sets, uint64_t n_ids, uint64_t np,
-                        KhFill& khf, BftInternTail& tail, DevBuf& seg_off, DevBuf& npg, double t0, double t1) {
+int bft_commit_image(bft_gpu* h, DevBuf& tk, DevBuf& n_tcol, DevBuf& n_cs_off, DevBuf& n_cs_ids, uint64_t nk, uint64_t n_sets, uint64_t n_ids, uint64_t np,
+                     KhFill& khf, BftInternTail& tail, DevBuf& seg_off, DevBuf& npg, double t0, double t1) {
     const int W = h->W;
     struct KhStart {  // (from here on tk, n_tcol and the number of colour sets are final)
         bft_gpu* h; const uint64_t* tk; const uint32_t* tcol; uint64_t nk, n_sets; KhFill* f;
@@ -1497,7 +1278,7 @@ static int commit_image(bft_gpu* h, DevBuf& tk, DevBuf& n_tcol, DevBuf& n_cs_off
     // (and earlier still -- behind the root's prefix scans, or before them: 15.7 ms each way, round 5: the build is bound by the device's total work,
     // not by either stream's chain)
     const BftAssembleHook hook{tk.p ? &KhStart::run : nullptr, &khs};
-    const double t2 = now_ms();
+    const double t2 = bft_now_ms();
 
     // 5. containers, level by level, on the GPU
     if (!tk.p) CK(tk.alloc(8));
@@ -1505,7 +1286,7 @@ static int commit_image(bft_gpu* h, DevBuf& tk, DevBuf& n_tcol, DevBuf& n_cs_off
     CK(bft_assemble_gpu(tk.as<uint64_t>(), nk, h->k, h->d_hashmod.as<uint32_t>(), h->stream, idx, &hook));
     bft_trace_mark("containers assembled");
     bft_stage("containers: concatenation", 0, h->stream);
-    double t3 = now_ms();
+    double t3 = bft_now_ms();
     DevBuf n_ccx, n_f18buf, n_fentbuf;
     uint64_t n_f18 = 0, n_fent = 0;
     CK(bft_flatten_gpu(idx.ccs.as<BftCC>(), idx.n_ccs, idx.f2w.as<uint64_t>(), idx.clus.as<uint64_t>(), idx.child.as<uint64_t>(), h->opt_flat_min, h->stream,
@@ -1632,7 +1413,7 @@ static int commit_image(bft_gpu* h, DevBuf& tk, DevBuf& n_tcol, DevBuf& n_cs_off
         fprintf(stderr, "[bft_gpu build] cache of released blocks: %zu blocks, %.1f MB; this process so far: %llu hipMalloc (%.2f ms), %llu hipFree on release (%.2f ms)\n", g_pool.size(),
                 g_pool_bytes / 1048576.0, (unsigned long long)g_malloc_calls, g_malloc_ms, (unsigned long long)g_free_calls, g_free_ms);
     }
-    h->build_ms[4] = now_ms() - t3;
+    h->build_ms[4] = bft_now_ms() - t3;
     return BFT_GPU_OK;
 }
 
@@ -1642,10 +1423,10 @@ extern "C" int bft_gpu_build(bft_gpu* h) {
     if (h->built && h->log_n == 0) return BFT_GPU_OK;
     CK(wait_foreign_stream(h));  // batches still being packed into the log on a caller's stream (bft_gpu_insert_kmers_dev_async)
     if (h->log_comp && (!h->log_g_sorted || h->opt_no_composite)) CK(log_decompose(h));  // (only the composite path below takes a log of composites)
-    if (h->built) CK(ensure_table(h));  // ("compact_table": the merge reads the index's sorted table)
+    if (h->built) CK(bft_ensure_table(h));  // ("compact_table": the merge reads the index's sorted table)
     const int W = h->W;
     const uint64_t total = h->log_n;  // the run: what was inserted since the last build
-    double t0 = now_ms();
+    double t0 = bft_now_ms();
     bft_trace_mark(nullptr);
     StageScope stage_scope(h);
 
@@ -1774,7 +1555,7 @@ extern "C" int bft_gpu_build(bft_gpu* h) {
         // 2. sort by (T, genome)
         CK(sk.alloc(total * W * 8));
         CK(sg.alloc(total * 4));
-        CK(sort_pairs(h, src_k, src_stride, src_g, total, sk.as<uint64_t>(), total, sg.as<uint32_t>(), h->log_g_sorted, true));
+        CK(bft_sort_pairs(h, src_k, src_stride, src_g, total, sk.as<uint64_t>(), total, sg.as<uint32_t>(), h->log_g_sorted, true));
         ck.release();
         cg.release();
         // (the insertion log stays until the new image is committed below: a failed build loses nothing)
@@ -1817,7 +1598,7 @@ extern "C" int bft_gpu_build(bft_gpu* h) {
     }
     bft_trace_mark("sort + dedupe done");
     bft_stage("sort + dedupe (rest)", 0, h->stream);
-    double t1 = now_ms();
+    double t1 = bft_now_ms();
 
     // 4. colour sets: signature sort + exact run detection + verification, all on the GPU
     uint64_t n_sets = 0, n_ids = 0;
@@ -1872,14 +1653,12 @@ extern "C" int bft_gpu_build(bft_gpu* h) {
     np = total_pairs;
     bft_trace_mark("merge / bookkeeping");
     bft_stage("merge into the index", 0, h->stream);
-    return commit_image(h, tk, n_tcol, n_cs_off, n_cs_ids, nk, n_sets, n_ids, np, khf, tail, seg_off, npg, t0, t1);
+    return bft_commit_image(h, tk, n_tcol, n_cs_off, n_cs_ids, nk, n_sets, n_ids, np, khf, tail, seg_off, npg, t0, t1);
 }
 
-static int ensure_table(bft_gpu* h);
-// need_table = false: the caller is answered by the k-mer hash alone ("compact_table": the sorted table may be away)
-static int ensure_built(bft_gpu* h, bool need_table = true) {
+int bft_ensure_built(bft_gpu* h, bool need_table) {
     if (!h->built || h->log_n) CK(bft_gpu_build(h));
-    if (need_table) CK(ensure_table(h));
+    if (need_table) CK(bft_ensure_table(h));
     return 0;
 }
 
@@ -1946,7 +1725,7 @@ static int launch_query_walk(bft_gpu* h, const uint8_t* d_kmers, uint64_t n, uin
     if (n == 0) return 0;
     const int rec = rec_bytes ? rec_bytes : h->B;
     hipEvent_t e0, e1;
-    CK(timing_begin(h, s, &e0, &e1));
+    CK(bft_timing_begin(h, s, &e0, &e1));
     const uint32_t keep = h->im.walk_kh;
     if (!through_kh) h->im.walk_kh = 0;
     int rc = 0;
@@ -1959,7 +1738,7 @@ static int launch_query_walk(bft_gpu* h, const uint8_t* d_kmers, uint64_t n, uin
     h->im.walk_kh = keep;
     CK(rc);
     claims_launched(h, s);
-    CK(timing_end(h, s, e0, e1));
+    CK(bft_timing_end(h, s, e0, e1));
     return 0;
 }
 
@@ -2033,23 +1812,23 @@ static void claims_launched(bft_gpu* h, hipStream_t s) {
 // Presence (and, with im.emit_cs, the colour set of every found k-mer into d_out32) through the k-mer hash.
 static int launch_query_kh(bft_gpu* h, const uint8_t* d_kmers, uint64_t n, uint64_t* d_bits64, uint32_t* d_out32, hipStream_t s, int rec) {
     hipEvent_t e0, e1;
-    CK(timing_begin(h, s, &e0, &e1));
+    CK(bft_timing_begin(h, s, &e0, &e1));
     CK(bft_kh_query(h->im, h->opt_grid_mult, d_kmers, n, rec, d_bits64, d_out32, claim_counters(h, s, n, (n + 255) / 256), h->opt_query_chunk, s));
     HIPCK(hipGetLastError());
     claims_launched(h, s);
-    CK(timing_end(h, s, e0, e1));
+    CK(bft_timing_end(h, s, e0, e1));
     return 0;
 }
 
 // Which kernel a batch takes: the k-mer hash answers presence and colour sets (one cache line per k-mer); rows -- positions in the
 // sorted table, what the reference keeps in resultPresence -- come from the container walk, as does everything on an image
 // without the k-mer hash ("kmer_hash" 0, a table that could not be allocated or whose overflow list ran full: kh_wanted, kh_finish).  Same answers either way (tests/test_gpu_parity.py).
-static int launch_query(bft_gpu* h, const uint8_t* d_kmers, uint64_t n, uint64_t* d_bits64, uint32_t* d_rows, hipStream_t s, int rec_bytes = 0) {
+int bft_launch_query(bft_gpu* h, const uint8_t* d_kmers, uint64_t n, uint64_t* d_bits64, uint32_t* d_rows, hipStream_t s, int rec_bytes) {
     if (n == 0) return 0;
     const int rec = rec_bytes ? rec_bytes : h->B;
     const bool no_rows = d_rows == nullptr || h->im.emit_cs;  // presence or colour sets: what the k-mer hash holds
     if (h->im.kh_lines != nullptr && no_rows && !h->opt_walk_hash) return launch_query_kh(h, d_kmers, n, d_bits64, d_rows, s, rec);
-    CK(ensure_table(h));
+    CK(bft_ensure_table(h));
     // the walk looks plain root groups up in the k-mer hash when no row is asked for ("walk_hash")
     return launch_query_walk(h, d_kmers, n, d_bits64, d_rows, s, rec, no_rows && h->opt_walk_hash);
 }
@@ -2208,11 +1987,11 @@ static int launch_branching(bft_gpu* h, const uint8_t* d_kmers, uint64_t n, uint
     if (n == 0) return 0;
     const bool staged = h->root_ncc >= 1 && h->root_ncc <= BFT_LDS_ROOT_MAX_CC;
     hipEvent_t e0, e1;
-    CK(timing_begin(h, s, &e0, &e1));
+    CK(bft_timing_begin(h, s, &e0, &e1));
     if (h->im.kh_lines != nullptr) {  // eight candidates per k-mer, each one cache line of the k-mer hash, four in flight at a time
         CK(bft_kh_branching(h->im, d_kmers, n, h->B, d_bits64, d_counts, claim_counters(h, s, n * 8, (n + 255) / 256), h->opt_query_chunk, s));
         claims_launched(h, s);
-        CK(timing_end(h, s, e0, e1));
+        CK(bft_timing_end(h, s, e0, e1));
         return 0;
     }
 #define BR(WW, PP) (staged ? launch_branching_k<WW, true, PP>(h, d_kmers, n, d_bits64, d_counts, s) : launch_branching_k<WW, false, PP>(h, d_kmers, n, d_bits64, d_counts, s))
@@ -2223,23 +2002,23 @@ static int launch_branching(bft_gpu* h, const uint8_t* d_kmers, uint64_t n, uint
     default: CK(BR(4, 0)); break;
     }
 #undef BR
-    CK(timing_end(h, s, e0, e1));
+    CK(bft_timing_end(h, s, e0, e1));
     return 0;
 }
 
 extern "C" int bft_gpu_query_branching_dev(bft_gpu* h, const void* d_kmers, uint64_t n, void* d_branching_bits, void* d_counts, void* hip_stream) {
     if (!h || ((!d_kmers || !d_branching_bits) && n)) return fail(BFT_GPU_E_ARG, "NULL argument");
     ENTER(h);
-    CK(ensure_built(h, false));  // (the k-mer hash answers; the walk fetches the table itself)
+    CK(bft_ensure_built(h, false));  // (the k-mer hash answers; the walk fetches the table itself)
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
     CK(launch_branching(h, (const uint8_t*)d_kmers, n, (uint64_t*)d_branching_bits, (uint8_t*)d_counts, s));
-    return note_foreign_stream(h, s);
+    return bft_note_foreign_stream(h, s);
 }
 
 extern "C" int bft_gpu_query_branching(bft_gpu* h, const uint8_t* kmers, uint64_t n, uint8_t* branching_bits, uint8_t* counts) {
     if (!h || ((!kmers || !branching_bits) && n)) return fail(BFT_GPU_E_ARG, "NULL argument");
     ENTER(h);
-    CK(ensure_built(h, false));  // (the k-mer hash answers; the walk fetches the table itself)
+    CK(bft_ensure_built(h, false));  // (the k-mer hash answers; the walk fetches the table itself)
     const uint64_t chunk = 1ull << 26;
     const uint64_t mc = std::min(n, chunk);
     DevBuf dk, db, dc;
@@ -2260,10 +2039,10 @@ extern "C" int bft_gpu_query_branching(bft_gpu* h, const uint8_t* kmers, uint64_
 extern "C" int bft_gpu_query_presence_dev(bft_gpu* h, const void* d_kmers, uint64_t n, void* d_present_bits, void* hip_stream) {
     if (!h || ((!d_kmers || !d_present_bits) && n)) return fail(BFT_GPU_E_ARG, "NULL argument");
     ENTER(h);
-    CK(ensure_built(h, false));  // (the k-mer hash answers; the walk fetches the table itself)
+    CK(bft_ensure_built(h, false));  // (the k-mer hash answers; the walk fetches the table itself)
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
-    CK(launch_query(h, (const uint8_t*)d_kmers, n, (uint64_t*)d_present_bits, nullptr, s));
-    return note_foreign_stream(h, s);
+    CK(bft_launch_query(h, (const uint8_t*)d_kmers, n, (uint64_t*)d_present_bits, nullptr, s));
+    return bft_note_foreign_stream(h, s);
 }
 
 // ---- small host batches through the pinned block -------------------------------------------------------------------------
@@ -2290,7 +2069,7 @@ static int query_small(bft_gpu* h, const uint8_t* kmers, uint64_t n, uint8_t* pr
     uint32_t* prow = (uint32_t*)(pin + BFT_PIN_ROWS_OFF);
     uint32_t* pset = (uint32_t*)(pin + BFT_PIN_SETS_OFF);
     const bool want_rows = rows || colorsets;
-    CK(launch_query(h, pin, n, (uint64_t*)(pin + BFT_PIN_BITS_OFF), want_rows ? prow : nullptr, h->stream));
+    CK(bft_launch_query(h, pin, n, (uint64_t*)(pin + BFT_PIN_BITS_OFF), want_rows ? prow : nullptr, h->stream));
     if (colorsets) {
         hipLaunchKernelGGL(k_row_colorsets, dim3(grid_for((n + 255) / 256)), dim3(256), 0, h->stream, prow, h->im.tcol, n, pset);
         HIPCK(hipGetLastError());
@@ -2305,7 +2084,7 @@ static int query_small(bft_gpu* h, const uint8_t* kmers, uint64_t n, uint8_t* pr
 extern "C" int bft_gpu_query_presence(bft_gpu* h, const uint8_t* kmers, uint64_t n, uint8_t* present_bits) {
     if (!h || ((!kmers || !present_bits) && n)) return fail(BFT_GPU_E_ARG, "NULL argument");
     ENTER(h);
-    CK(ensure_built(h, false));  // (the k-mer hash answers; the walk fetches the table itself)
+    CK(bft_ensure_built(h, false));  // (the k-mer hash answers; the walk fetches the table itself)
     if (n && n <= BFT_PIN_MAX_N) return query_small(h, kmers, n, present_bits, nullptr, nullptr);
     const uint64_t chunk = 1ull << 26;  // multiple of 64: chunks are byte aligned in the bitmap
     DevBuf dk, db;
@@ -2314,7 +2093,7 @@ extern "C" int bft_gpu_query_presence(bft_gpu* h, const uint8_t* kmers, uint64_t
     for (uint64_t a = 0; a < n; a += chunk) {
         const uint64_t m = std::min(chunk, n - a);
         HIPCK(hipMemcpyAsync(dk.p, kmers + a * h->B, m * h->B, hipMemcpyHostToDevice, h->stream));
-        CK(launch_query(h, dk.as<uint8_t>(), m, db.as<uint64_t>(), nullptr, h->stream));
+        CK(bft_launch_query(h, dk.as<uint8_t>(), m, db.as<uint64_t>(), nullptr, h->stream));
         HIPCK(hipMemcpyAsync(present_bits + a / 8, db.p, (m + 7) / 8, hipMemcpyDeviceToHost, h->stream));
         HIPCK(hipStreamSynchronize(h->stream));
     }
@@ -2324,7 +2103,7 @@ extern "C" int bft_gpu_query_presence(bft_gpu* h, const uint8_t* kmers, uint64_t
 // shared front half of the colour queries: rows + presence bits for one chunk
 static int query_rows(bft_gpu* h, const uint8_t* kmers, uint64_t m, DevBuf& dk, DevBuf& db, DevBuf& dr, uint8_t* present_bits) {
     HIPCK(hipMemcpyAsync(dk.p, kmers, m * h->B, hipMemcpyHostToDevice, h->stream));
-    CK(launch_query(h, dk.as<uint8_t>(), m, db.as<uint64_t>(), dr.as<uint32_t>(), h->stream));
+    CK(bft_launch_query(h, dk.as<uint8_t>(), m, db.as<uint64_t>(), dr.as<uint32_t>(), h->stream));
     if (present_bits) HIPCK(hipMemcpyAsync(present_bits, db.p, (m + 7) / 8, hipMemcpyDeviceToHost, h->stream));
     return 0;
 }
@@ -2334,52 +2113,36 @@ static int query_rows(bft_gpu* h, const uint8_t* kmers, uint64_t m, DevBuf& dk, 
 // from the dictionary, and the wavefronts stream the ids out.  No row, no sorted table ("compact_table" stays), no host round trip.
 static int colors_core(bft_gpu* h, const uint8_t* d_kmers, uint64_t n, uint64_t* d_bits64, uint64_t* d_offsets, uint32_t* d_ids, uint64_t ids_cap, uint64_t* d_needed,
                        hipStream_t s, bool fill) {
-    if (h->qc_used && h->qc_stream != s) {  // (the scratch belongs to the handle: one stream at a time -- behind an event of the handle's own, not the other stream)
-        const hipError_t e = h->qc_ev ? hipEventSynchronize(h->qc_ev) : hipDeviceSynchronize();
-        h->qc_stream = s;
-        HIPCK(e);
-    }
+    CK(h->qc.acquire(s, bft_stream_capturing(s)));
     if (fill && h->im.kh_lines != nullptr && !h->opt_walk_hash && bft_kh_has_kernels(h->W, h->im.kh.S) && h->im.nb_genomes < 65536u) {  // (k_colors_kh keeps list lengths in 16 bits)
         // through the k-mer hash: lookup, offsets and ids in ONE launch (k_colors_kh; the host entry point counts first and fills per chunk: the three steps below)
         // (a block of its own: the kernel writes its counter and states raw, which a block of bft_scan's -- qc_tmp -- must never see)
         const size_t sb = bft_kh_colors_scratch_bytes(n);
-        if (h->qc_kh.bytes < sb) {
-            if (h->qc_used) HIPCK(hipStreamSynchronize(s));
-            CK(h->qc_kh.alloc(sb + sb / 2));
-        }
-        h->qc_used = true;
-        h->qc_stream = s;
-        CK(timed_launch(h, s, [&] { return bft_kh_colors(h->im, d_kmers, n, h->B, d_bits64, d_offsets, d_ids, d_ids ? ids_cap : 0, d_needed, h->qc_kh.p, s); }));
-        if (!h->qc_ev && hipEventCreateWithFlags(&h->qc_ev, hipEventDisableTiming) != hipSuccess) { h->qc_ev = nullptr; (void)hipGetLastError(); }
-        if (h->qc_ev && hipEventRecord(h->qc_ev, s) != hipSuccess) (void)hipGetLastError();
+        CK(h->qc.grow(h->qc_kh, sb, sb / 2));
+        CK(bft_timed_launch(h, s, [&] { return bft_kh_colors(h->im, d_kmers, n, h->B, d_bits64, d_offsets, d_ids, d_ids ? ids_cap : 0, d_needed, h->qc_kh.p, s); }));
+        h->qc.release();
         return 0;
     }
     const size_t tb = bft_scan::scratch_bytes(n + 1);  // (the scan's tile states)
-    if (h->qc_cs.bytes < n * 4 || h->qc_tmp.bytes < tb) {
-        if (h->qc_used) HIPCK(hipStreamSynchronize(s));
-        if (h->qc_cs.bytes < n * 4) CK(h->qc_cs.alloc(n * 4 + n / 2));
-        if (h->qc_tmp.bytes < tb) CK(h->qc_tmp.alloc(tb + tb / 2));
-    }
-    h->qc_used = true;
-    h->qc_stream = s;
+    CK(h->qc.grow(h->qc_cs, n * 4, n / 2));
+    CK(h->qc.grow(h->qc_tmp, tb, tb / 2));
     uint32_t* d_cs = h->qc_cs.as<uint32_t>();
     {   // (the k-mer hash has the colour set in the line that answers presence; the walk, on an image without the table, takes it from tcol[row])
         h->im.emit_cs = 1;
-        const int rc = launch_query(h, d_kmers, n, d_bits64, d_cs, s);
+        const int rc = bft_launch_query(h, d_kmers, n, d_bits64, d_cs, s);
         h->im.emit_cs = 0;
         CK(rc);
     }
     const BftCsLen len{d_cs, h->im.cs_off, n};
     CK((bft_scan::exclusive_sum<uint64_t>(len, d_offsets, n + 1, s, h->qc_tmp)));
     if (fill) {
-        CK(timed_launch(h, s, [&] {
+        CK(bft_timed_launch(h, s, [&] {
             hipLaunchKernelGGL(k_color_fill_cs, dim3(grid_for((n + 255) / 256)), dim3(256), 0, s, d_cs, h->im.cs_off, h->im.cs_ids, h->im.cs_w, d_offsets, n, ids_cap, d_ids, d_needed);
             HIPCK(hipGetLastError());
             return 0;
         }));
     }
-    if (!h->qc_ev && hipEventCreateWithFlags(&h->qc_ev, hipEventDisableTiming) != hipSuccess) { h->qc_ev = nullptr; (void)hipGetLastError(); }
-    if (h->qc_ev && hipEventRecord(h->qc_ev, s) != hipSuccess) (void)hipGetLastError();
+    h->qc.release();
     return 0;
 }
 
@@ -2387,15 +2150,15 @@ extern "C" int bft_gpu_query_colors_dev(bft_gpu* h, const void* d_kmers, uint64_
                                         void* d_ids_needed, void* hip_stream) {
     if (!h || !d_offsets || ((!d_kmers || !d_present_bits) && n)) return fail(BFT_GPU_E_ARG, "NULL argument");
     ENTER(h);
-    CK(ensure_built(h, false));
+    CK(bft_ensure_built(h, false));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
     if (n == 0) {
         CK(bft_zero_async(d_offsets, 8, s));  // (kernels, not memsets, wherever a caller may be capturing: bft_dev.h)
         if (d_ids_needed) CK(bft_zero_async(d_ids_needed, 8, s));
-        return note_foreign_stream(h, s);
+        return bft_note_foreign_stream(h, s);
     }
     CK(colors_core(h, (const uint8_t*)d_kmers, n, (uint64_t*)d_present_bits, (uint64_t*)d_offsets, (uint32_t*)d_ids, ids_cap, (uint64_t*)d_ids_needed, s, true));
-    return note_foreign_stream(h, s);
+    return bft_note_foreign_stream(h, s);
 }
 
 // The host-buffer form: the resident one on staged chunks.
@@ -2403,7 +2166,7 @@ extern "C" int bft_gpu_query_colors(bft_gpu* h, const uint8_t* kmers, uint64_t n
                                     uint32_t* ids, uint64_t ids_cap, uint64_t* ids_needed) {
     if (!h || !offsets || ((!kmers) && n)) return fail(BFT_GPU_E_ARG, "NULL argument");
     ENTER(h);
-    CK(ensure_built(h, false));
+    CK(bft_ensure_built(h, false));
     const uint64_t chunk = 1ull << 24;
     const uint64_t mc = std::min(n, chunk);
     DevBuf dk, db, doff, dids;
@@ -2425,7 +2188,7 @@ extern "C" int bft_gpu_query_colors(bft_gpu* h, const uint8_t* kmers, uint64_t n
         if (!overflow && ids && total + cnt <= ids_cap) {
             if (cnt) {
                 CK(dids.alloc(cnt * 4));
-                CK(timed_launch(h, h->stream, [&] {
+                CK(bft_timed_launch(h, h->stream, [&] {
                     hipLaunchKernelGGL(k_color_fill_cs, dim3(grid_for((m + 255) / 256)), dim3(256), 0, h->stream, h->qc_cs.as<uint32_t>(), h->im.cs_off, h->im.cs_ids, h->im.cs_w,
                                        doff.as<uint64_t>(), m, cnt, dids.as<uint32_t>(), (uint64_t*)nullptr);
                     HIPCK(hipGetLastError());
@@ -2468,7 +2231,7 @@ static int ensure_cs_bitmaps(bft_gpu* h) {
 static int launch_color_rows(bft_gpu* h, uint32_t* d_rowidx, uint64_t n, uint32_t rowbytes, uint8_t* d_out, hipStream_t s, bool are_colorsets = false) {
     CK(ensure_cs_bitmaps(h));
     hipEvent_t e0, e1;
-    CK(timing_begin(h, s, &e0, &e1));
+    CK(bft_timing_begin(h, s, &e0, &e1));
     if (h->has_cs_bm) {
         if (!are_colorsets)
             hipLaunchKernelGGL(k_row_colorsets, dim3(grid_for((n + 255) / 256)), dim3(256), 0, s, d_rowidx, h->im.tcol, n, d_rowidx);  // row -> colour set, in place
@@ -2526,7 +2289,7 @@ static int launch_color_rows(bft_gpu* h, uint32_t* d_rowidx, uint64_t n, uint32_
     else
         hipLaunchKernelGGL(k_color_rows, dim3(grid_for((n + 255) / 256)), dim3(256), 0, s, d_rowidx, h->im.tcol, h->im.cs_off, h->im.cs_ids, h->im.cs_w, n, rowbytes, d_out);
     HIPCK(hipGetLastError());
-    return timing_end(h, s, e0, e1);
+    return bft_timing_end(h, s, e0, e1);
 }
 
 // device-resident colour rows: presence bits + CEIL(nb_genomes/8)-byte bitmap row per k-mer, no synchronisation
@@ -2534,7 +2297,7 @@ extern "C" int bft_gpu_query_color_rows_dev(bft_gpu* h, const void* d_kmers, uin
                                             void* hip_stream) {
     if (!h || ((!d_kmers || !d_present_bits || !d_rows || !d_scratch_rows_u32) && n)) return fail(BFT_GPU_E_ARG, "NULL argument");
     ENTER(h);
-    CK(ensure_built(h, false));
+    CK(bft_ensure_built(h, false));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
     const uint32_t rowbytes = (h->im.nb_genomes + 7) / 8;
     if (n == 0 || rowbytes == 0) return BFT_GPU_OK;
@@ -2544,25 +2307,25 @@ extern "C" int bft_gpu_query_color_rows_dev(bft_gpu* h, const void* d_kmers, uin
     const bool direct = h->has_cs_bm;
     // rows of 16 bytes and up through the k-mer hash: lookup and rows in one launch (the scratch array stays unused)
     if (direct && rowbytes >= 16 && ((uintptr_t)d_rows & 15u) == 0 && h->im.kh_lines != nullptr && !h->opt_walk_hash && bft_kh_has_kernels(h->W, h->im.kh.S)) {
-        CK(timed_launch(h, s, [&] {
+        CK(bft_timed_launch(h, s, [&] {
             return bft_kh_color_rows(h->im, (const uint8_t*)d_kmers, n, h->B, (uint64_t*)d_present_bits, h->d_cs_bm.as<uint8_t>() + CS_BM_SLACK, (rowbytes + 3) & ~3u, rowbytes,
                                      (uint8_t*)d_rows, h->device, s);
         }));
-        return note_foreign_stream(h, s);
+        return bft_note_foreign_stream(h, s);
     }
-    if (!direct) CK(ensure_table(h));
+    if (!direct) CK(bft_ensure_table(h));
     if (direct) h->im.emit_cs = 1;
-    const int rc = launch_query(h, (const uint8_t*)d_kmers, n, (uint64_t*)d_present_bits, (uint32_t*)d_scratch_rows_u32, s);
+    const int rc = bft_launch_query(h, (const uint8_t*)d_kmers, n, (uint64_t*)d_present_bits, (uint32_t*)d_scratch_rows_u32, s);
     h->im.emit_cs = 0;
     CK(rc);
     CK(launch_color_rows(h, (uint32_t*)d_scratch_rows_u32, n, rowbytes, (uint8_t*)d_rows, s, direct));
-    return note_foreign_stream(h, s);
+    return bft_note_foreign_stream(h, s);
 }
 
 extern "C" int bft_gpu_query_color_rows(bft_gpu* h, const uint8_t* kmers, uint64_t n, uint8_t* present_bits, uint8_t* rows) {
     if (!h || !rows || (!kmers && n)) return fail(BFT_GPU_E_ARG, "NULL argument");
     ENTER(h);
-    CK(ensure_built(h));
+    CK(bft_ensure_built(h));
     const uint32_t rowbytes = (h->im.nb_genomes + 7) / 8;
     if (rowbytes == 0) return BFT_GPU_OK;
     const uint64_t chunk = 1ull << 22;
@@ -2626,12 +2389,8 @@ static int query_sequences_core(bft_gpu* h, const char* d_seqs, const uint64_t* 
                                 int canonical, uint8_t* d_rows, hipStream_t s) {
     const uint32_t G = h->im.nb_genomes, rowbytes = (G + 7) / 8;
     if (rowbytes == 0 || n_seqs == 0) return 0;
-    if (h->sq_used && h->sq_stream != s) HIPCK(hipStreamSynchronize(h->sq_stream));
-    auto need = [&](DevBuf& b, size_t bytes) -> int {
-        if (b.bytes >= bytes) return 0;
-        if (h->sq_used) HIPCK(hipStreamSynchronize(s));  // the block being replaced may still be read by the previous call
-        return b.alloc(bytes + bytes / 8);
-    };
+    CK(h->sq.acquire(s, bft_stream_capturing(s)));
+    auto need = [&](DevBuf& b, size_t bytes) { return h->sq.grow(b, bytes, bytes / 8); };
     // sequences per chunk: 32-bit sequence numbers
     const uint64_t chunk = 1ull << 30;
     const uint64_t cmax = std::min(chunk, n_seqs);
@@ -2644,13 +2403,11 @@ static int query_sequences_core(bft_gpu* h, const char* d_seqs, const uint64_t* 
     CK(need(h->sq_tmp, scan_bytes));
     CK(need(h->sq_tile, (total_chars / 64 + 2) * 4));
     CK(need(h->sq_cs, (total_chars + 64) * 4));  // colour set of every k-mer position of a chunk (positions <= characters)
-    h->sq_used = true;
-    h->sq_stream = s;
     // (the slack words behind the codes are read by windows at the very end of the blob: keep them defined)
     CK(bft_zero_async(h->sq_codes.as<uint64_t>() + n_cw, (BFT_MAX_W + 2) * 8, s));
     CK(bft_zero_async(h->sq_bad.as<uint32_t>() + n_cw, (BFT_MAX_W + 2) * 4, s));
     if (n_cw)
-        CK(timed_launch(h, s, [&] {
+        CK(bft_timed_launch(h, s, [&] {
             hipLaunchKernelGGL(k_seq_encode, dim3(grid_for((n_cw + 255) / 256)), dim3(256), 0, s, d_seqs, total_chars, n_cw, h->sq_codes.as<uint64_t>(),
                                h->sq_bad.as<uint32_t>());
             HIPCK(hipGetLastError());
@@ -2659,7 +2416,7 @@ static int query_sequences_core(bft_gpu* h, const char* d_seqs, const uint64_t* 
     for (uint64_t a = 0; a < n_seqs; a += chunk) {
         const uint64_t ns = std::min(chunk, n_seqs - a);
         const uint64_t* soff = d_seq_off + a;
-        CK(timed_launch(h, s, [&] {  // (the plan: positions per read, their offsets, the tile table)
+        CK(bft_timed_launch(h, s, [&] {  // (the plan: positions per read, their offsets, the tile table)
             hipLaunchKernelGGL(k_seq_plan, dim3(grid_for((ns + 256) / 256)), dim3(256), 0, s, soff, ns, h->k, h->sq_npos.as<uint64_t>());
             CK(bft_scan::exclusive_sum_ptr<uint64_t>(h->sq_npos.as<uint64_t>(), h->sq_poff.as<uint64_t>(), ns + 1, s, h->sq_tmp));
             hipLaunchKernelGGL(k_seq_tiles, dim3(256 * 4), dim3(256), 0, s, h->sq_poff.as<uint64_t>(), (uint32_t)ns, h->sq_tile.as<uint32_t>());
@@ -2667,7 +2424,7 @@ static int query_sequences_core(bft_gpu* h, const char* d_seqs, const uint64_t* 
             return 0;
         }));
         h->sq_units = total_chars / 256 + 2;  // (k-mer positions <= characters: the blocks the kernel can deal out)
-        CK(timed_launch(h, s, [&] {
+        CK(bft_timed_launch(h, s, [&] {
             switch (h->W) {
             case 1: return launch_seq_walk_w<1>(h, (uint32_t)ns, canonical, soff, s);
             case 2: return launch_seq_walk_w<2>(h, (uint32_t)ns, canonical, soff, s);
@@ -2677,7 +2434,7 @@ static int query_sequences_core(bft_gpu* h, const char* d_seqs, const uint64_t* 
         }));
         claims_launched(h, s);
         const uint32_t win = std::min<uint32_t>(SEQ_TALLY_G, (G + 63u) & ~63u);  // counters per wavefront: all genomes up to 2048
-        CK(timed_launch(h, s, [&] {
+        CK(bft_timed_launch(h, s, [&] {
             hipLaunchKernelGGL(k_seq_tally, dim3((unsigned)std::min<uint64_t>((ns + SEQ_TALLY_WAVES - 1) / SEQ_TALLY_WAVES, 256ull * 16)), dim3(64 * SEQ_TALLY_WAVES),
                                (size_t)SEQ_TALLY_WAVES * win * 4, s, h->sq_cs.as<uint32_t>(), h->sq_poff.as<uint64_t>(), (uint32_t)ns, h->im.cs_off, h->im.cs_ids, h->im.cs_w, G,
                                rowbytes, threshold, win, d_rows + a * rowbytes);
@@ -2685,6 +2442,7 @@ static int query_sequences_core(bft_gpu* h, const char* d_seqs, const uint64_t* 
             return 0;
         }));
     }
+    h->sq.release();
     return 0;
 }
 
@@ -2693,10 +2451,10 @@ extern "C" int bft_gpu_query_sequences_dev(bft_gpu* h, const void* d_seqs, const
     if (!h || ((!d_seqs || !d_seq_off || !d_rows) && n_seqs)) return fail(BFT_GPU_E_ARG, "NULL argument");
     if (!(threshold > 0) || threshold > 1) return fail(BFT_GPU_E_ARG, "the threshold must be in (0, 1] (reference src/bft.c:1246-1247)");
     ENTER(h);
-    CK(ensure_built(h, false));  // (the k-mer hash answers; the walk fetches the table itself)
+    CK(bft_ensure_built(h, false));  // (the k-mer hash answers; the walk fetches the table itself)
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
     CK(query_sequences_core(h, (const char*)d_seqs, (const uint64_t*)d_seq_off, n_seqs, total_chars, threshold, canonical, (uint8_t*)d_rows, s));
-    return note_foreign_stream(h, s);
+    return bft_note_foreign_stream(h, s);
 }
 
 extern "C" int bft_gpu_query_sequences(bft_gpu* h, const char* seqs, const uint64_t* seq_off, uint64_t n_seqs, double threshold, int canonical,
@@ -2704,7 +2462,7 @@ extern "C" int bft_gpu_query_sequences(bft_gpu* h, const char* seqs, const uint6
     if (!h || ((!seqs || !seq_off || !rows) && n_seqs)) return fail(BFT_GPU_E_ARG, "NULL argument");
     if (!(threshold > 0) || threshold > 1) return fail(BFT_GPU_E_ARG, "the threshold must be in (0, 1] (reference src/bft.c:1246-1247)");
     ENTER(h);
-    CK(ensure_built(h, false));  // (the k-mer hash answers; the walk fetches the table itself)
+    CK(bft_ensure_built(h, false));  // (the k-mer hash answers; the walk fetches the table itself)
     const uint32_t G = h->im.nb_genomes, rowbytes = (G + 7) / 8;
     if (rowbytes == 0 || n_seqs == 0) return BFT_GPU_OK;
     // host buffers: the blob and its offsets (rebased to the first sequence) go up in pieces of at most 2^30 characters
@@ -2736,7 +2494,7 @@ extern "C" int bft_gpu_load_bft(const char* path, int device, bft_gpu** out) {
     if (!path || !out) return fail(BFT_GPU_E_ARG, "NULL argument");
     *out = nullptr;
     DeviceScope ds_;
-    const double t_load0 = now_ms();
+    const double t_load0 = bft_now_ms();
     BftFileContent fc;
     std::string err;
     try {  // sizes come from an untrusted file: an allocation failure is an I/O error of this call, not the end of the process
@@ -2760,13 +2518,13 @@ extern "C" int bft_gpu_load_bft(const char* path, int device, bft_gpu** out) {
         }
     }
     static const bool io_trace = getenv("BFT_GPU_TRACE_IO") != nullptr;
-    const double t_io0 = now_ms();
+    const double t_io0 = bft_now_ms();
     if (io_trace) fprintf(stderr, "[bft_gpu io] %8.1f ms load: file decoded, handle created, log reserved\n", t_io0 - t_load0);
     for (size_t g = 0; g < fc.per_genome.size() && rc == 0; g++)
         if (!fc.per_genome[g].empty()) rc = bft_gpu_insert_kmers(h, fc.per_genome[g].data(), fc.per_genome[g].size() / B, (uint32_t)g);
-    if (io_trace) fprintf(stderr, "[bft_gpu io] %8.1f ms load: every genome's k-mers inserted (host batches)\n", now_ms() - t_io0);
+    if (io_trace) fprintf(stderr, "[bft_gpu io] %8.1f ms load: every genome's k-mers inserted (host batches)\n", bft_now_ms() - t_io0);
     if (rc == 0) rc = bft_gpu_build(h);
-    if (io_trace) fprintf(stderr, "[bft_gpu io] %8.1f ms load: index built\n", now_ms() - t_io0);
+    if (io_trace) fprintf(stderr, "[bft_gpu io] %8.1f ms load: index built\n", bft_now_ms() - t_io0);
     bft_dispose_async(fc);  // (the decoded k-mers of every genome)
     if (rc != 0) {
         const std::string keep = g_err;
@@ -2789,9 +2547,9 @@ extern "C" int bft_gpu_write_bft(bft_gpu* h, const char* path) {
     if (!bft_reference_k(h->k)) return fail(BFT_GPU_E_ARG, "the .bft format requires k % 9 == 0 (reference src/main.c:61-63)");
     ENTER(h);
     static const bool io_trace = getenv("BFT_GPU_TRACE_IO") != nullptr;
-    const double t_io0 = now_ms();
-    CK(ensure_built(h));
-    if (io_trace) fprintf(stderr, "[bft_gpu io] %8.1f ms write: index built, sorted table resident\n", now_ms() - t_io0);
+    const double t_io0 = bft_now_ms();
+    CK(bft_ensure_built(h));
+    if (io_trace) fprintf(stderr, "[bft_gpu io] %8.1f ms write: index built, sorted table resident\n", bft_now_ms() - t_io0);
     BftHostImage hi;
     hi.k = h->k;
     hi.r1 = h->r1;
@@ -2833,7 +2591,7 @@ extern "C" int bft_gpu_write_bft(bft_gpu* h, const char* path) {
             for (std::thread& x : th) x.join();
         }
     }
-    if (io_trace) fprintf(stderr, "[bft_gpu io] %8.1f ms write: image arrays on the host\n", now_ms() - t_io0);
+    if (io_trace) fprintf(stderr, "[bft_gpu io] %8.1f ms write: image arrays on the host\n", bft_now_ms() - t_io0);
     std::string err;
     try {
         if (!bft_file_write(path, hi, err)) return fail(BFT_GPU_E_IO, err);
@@ -2842,7 +2600,7 @@ extern "C" int bft_gpu_write_bft(bft_gpu* h, const char* path) {
     } catch (const std::exception& e) {
         return fail(BFT_GPU_E_IO, std::string("write_BFT: ") + e.what());
     }
-    if (io_trace) fprintf(stderr, "[bft_gpu io] %8.1f ms write: file written and closed\n", now_ms() - t_io0);
+    if (io_trace) fprintf(stderr, "[bft_gpu io] %8.1f ms write: file written and closed\n", bft_now_ms() - t_io0);
     bft_dispose_async(hi);  // (the host copy of the image: gigabytes of vectors)
     return BFT_GPU_OK;
 }
@@ -2893,7 +2651,7 @@ void plan_blob(bft_gpu* h, BlobPlan& p) {
 extern "C" int bft_gpu_image_size(bft_gpu* h, uint64_t* nbytes) {
     if (!h || !nbytes) return fail(BFT_GPU_E_ARG, "NULL argument");
     ENTER(h);
-    CK(ensure_built(h, false));
+    CK(bft_ensure_built(h, false));
     BlobPlan p;
     plan_blob(h, p);
     *nbytes = p.hdr[H_TOTAL];
@@ -2903,7 +2661,7 @@ extern "C" int bft_gpu_image_size(bft_gpu* h, uint64_t* nbytes) {
 extern "C" int bft_gpu_image_pack(bft_gpu* h, void* d_blob, uint64_t cap, void* hip_stream) {
     if (!h || !d_blob) return fail(BFT_GPU_E_ARG, "NULL argument");
     ENTER(h);
-    CK(ensure_built(h));
+    CK(bft_ensure_built(h));
     BlobPlan p;
     plan_blob(h, p);
     if (cap < p.hdr[H_TOTAL]) return fail(BFT_GPU_E_NOSPACE, "blob buffer too small");
@@ -2991,7 +2749,7 @@ extern "C" int bft_gpu_image_unpack(const void* d_blob, uint64_t nbytes, int dev
 extern "C" int bft_gpu_debug_get_array(bft_gpu* h, const char* name, void* out, uint64_t cap_bytes, uint64_t* nbytes) {
     if (!h || !name) return fail(BFT_GPU_E_ARG, "NULL argument");
     ENTER(h);
-    CK(ensure_built(h));
+    CK(bft_ensure_built(h));
     static const char* names[16] = {"nodes", "bfT", "ccs", "f2w", "clus", "child", "uck", "ucrow", "tk", "ccx", "f18", "fent", "kh", "tcol", "kh_ovf_k", "kh_ovf_v"};
     const DevBuf* bufs[16] = {&h->d_nodes, &h->d_bfT, &h->d_ccs, &h->d_f2w, &h->d_clus, &h->d_child, &h->d_uck, &h->d_ucrow, &h->d_tk,
                               &h->d_ccx, &h->d_f18, &h->d_fent, &h->d_kh, &h->d_tcol, &h->d_kh_ovf_k, &h->d_kh_ovf_v};
@@ -3247,7 +3005,7 @@ extern "C" int bft_gpu_set_option(bft_gpu* h, const char* name, int64_t value) {
             ENTER(h);
             CK(wait_foreign_stream(h));
             HIPCK(hipStreamSynchronize(h->stream));
-            CK(ensure_table(h));
+            CK(bft_ensure_table(h));
             derive_kmer_hash(h);
             sync_walk_kh(h);
             derive_node_hash(h);  // (by default the node prefix hash exists exactly when the container walk answers queries)
@@ -3270,7 +3028,7 @@ extern "C" int bft_gpu_set_option(bft_gpu* h, const char* name, int64_t value) {
             CK(wait_foreign_stream(h));
             HIPCK(hipStreamSynchronize(h->stream));
             if (h->opt_compact) drop_table(h);
-            else CK(ensure_table(h));
+            else CK(bft_ensure_table(h));
         }
     } else if (nm == "root_direct") {  // 2 (default): root level through the derived range + direct tables; 1: direct table only; 0: containers
         if (value < 0 || value > 3) return fail(BFT_GPU_E_ARG, "root_direct must be 0, 1, 2 or 3");
@@ -3279,7 +3037,7 @@ extern "C" int bft_gpu_set_option(bft_gpu* h, const char* name, int64_t value) {
             ENTER(h);
             CK(wait_foreign_stream(h));
             HIPCK(hipStreamSynchronize(h->stream));
-            CK(ensure_table(h));  // ("compact_table": k_root_ranges reads the sorted table)
+            CK(bft_ensure_table(h));  // ("compact_table": k_root_ranges reads the sorted table)
             derive_root_direct(h);
             sync_walk_kh(h);
             default_launch_shape(h);
@@ -3292,7 +3050,7 @@ extern "C" int bft_gpu_set_option(bft_gpu* h, const char* name, int64_t value) {
             ENTER(h);
             CK(wait_foreign_stream(h));
             HIPCK(hipStreamSynchronize(h->stream));
-            CK(ensure_table(h));
+            CK(bft_ensure_table(h));
             derive_root_direct(h);
             sync_walk_kh(h);
             default_launch_shape(h);
@@ -3304,7 +3062,7 @@ extern "C" int bft_gpu_set_option(bft_gpu* h, const char* name, int64_t value) {
             ENTER(h);
             CK(wait_foreign_stream(h));
             HIPCK(hipStreamSynchronize(h->stream));
-            CK(ensure_table(h));
+            CK(bft_ensure_table(h));
             CK(tune_residency(h));
         }
     } else if (nm == "query_dynamic") {  // 0: the k-mer hash kernels split their batch by workgroup number (what they did before the claims)
@@ -3353,7 +3111,7 @@ extern "C" int bft_gpu_set_option(bft_gpu* h, const char* name, int64_t value) {
             ENTER(h);
             CK(wait_foreign_stream(h));
             HIPCK(hipStreamSynchronize(h->stream));
-            CK(ensure_table(h));  // ("compact_table": the derived tables are rebuilt from the sorted table)
+            CK(bft_ensure_table(h));  // ("compact_table": the derived tables are rebuilt from the sorted table)
             CK(bind_image(h, h->im.nb_genomes));
             h->info[12] = image_bytes(h);
             drop_table(h);
@@ -3443,7 +3201,7 @@ __global__ void k_tform_to_packed(const uint64_t* __restrict__ tk, uint64_t n, i
 extern "C" int bft_gpu_extract(bft_gpu* h, uint8_t* kmers_out, uint32_t* colorset_out, uint64_t cap, uint64_t* n_out) {
     if (!h) return fail(BFT_GPU_E_ARG, "NULL handle");
     ENTER(h);
-    CK(ensure_built(h));
+    CK(bft_ensure_built(h));
     if (n_out) *n_out = h->n_kmers;
     if (!kmers_out && !colorset_out) return BFT_GPU_OK;
     if (cap < h->n_kmers) return fail(BFT_GPU_E_NOSPACE, "extract buffer too small");
@@ -3469,7 +3227,7 @@ extern "C" int bft_gpu_extract(bft_gpu* h, uint8_t* kmers_out, uint32_t* colorse
 extern "C" int bft_gpu_colorset(bft_gpu* h, uint32_t cs, uint32_t* ids, uint32_t cap, uint32_t* n_out) {
     if (!h) return fail(BFT_GPU_E_ARG, "NULL handle");
     ENTER(h);
-    CK(ensure_built(h, false));
+    CK(bft_ensure_built(h, false));
     CK(host_colorsets(h));
     if ((uint64_t)cs + 1 >= h->cs_off.size()) return fail(BFT_GPU_E_ARG, "unknown colour set");
     const uint32_t a = h->cs_off[cs], b = h->cs_off[cs + 1];
@@ -3486,7 +3244,7 @@ extern "C" int bft_gpu_colorset(bft_gpu* h, uint32_t cs, uint32_t* ids, uint32_t
 extern "C" int bft_gpu_query_rows(bft_gpu* h, const uint8_t* kmers, uint64_t n, uint8_t* present_bits, uint32_t* rows, uint32_t* colorsets) {
     if (!h || (!kmers && n)) return fail(BFT_GPU_E_ARG, "NULL argument");
     ENTER(h);
-    CK(ensure_built(h));
+    CK(bft_ensure_built(h));
     if (n && n <= BFT_PIN_MAX_N) return query_small(h, kmers, n, present_bits, rows, colorsets);
     const uint64_t chunk = 1ull << 24;
     const uint64_t mc = std::min(n, chunk);
@@ -3509,615 +3267,10 @@ extern "C" int bft_gpu_query_rows(bft_gpu* h, const uint8_t* kmers, uint64_t n, 
     return BFT_GPU_OK;
 }
 
-// ------------------------------------------------------------------------------------------------
-// prefix matching (prefix_matching, include/bft.h:135, src/bft.c:1087-1147): the kernels of bft_prefix.hip over the sorted table
-// ------------------------------------------------------------------------------------------------
-static bool stream_capturing(hipStream_t s) {
+bool bft_stream_capturing(hipStream_t s) {
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
     return st != hipStreamCaptureStatusNone;
-}
-static uint64_t pm_bytes(uint64_t m) {
-    auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
-    return 2 * al(m * 4) + 2 * al(m * 8) + al((m + 1) * 8) + al(BFT_PM_CHUNKS * 8ull) + al((BFT_PM_CHUNKS + 1) * 8ull);
-}
-// The handle's scratch for a batch of n prefixes on stream s.  It belongs to the handle, not to a stream: a call on another stream first waits for
-// the last use (an event of the handle's own); nothing is allocated or waited for while s is being captured.
-static int pm_scratch(bft_gpu* h, uint64_t n, hipStream_t s, bool capturing, BftPmScratch* p) {
-    if (h->pm_used && h->pm_stream != s) {
-        if (capturing) return fail(BFT_GPU_E_ARG, "prefix query recorded into a graph: the handle's prefix scratch is in use on another stream");
-        HIPCK(h->pm_ev ? hipEventSynchronize(h->pm_ev) : hipDeviceSynchronize());
-        h->pm_used = false;
-    }
-    const size_t tb = bft_scan::scratch_bytes(std::max<uint64_t>(n, BFT_PM_CHUNKS) + 1);
-    if (h->pm_n < n || h->pm_tmp.bytes < tb) {
-        if (capturing) return fail(BFT_GPU_E_ARG, "prefix query recorded into a graph: make one direct call of this size first (nothing may allocate in a capture)");
-        if (h->pm_used) HIPCK(hipStreamSynchronize(s));
-        if (h->pm_n < n) {
-            const uint64_t m = n + n / 2;
-            CK(h->pm_buf.alloc(pm_bytes(m)));
-            h->pm_n = m;
-        }
-        if (h->pm_tmp.bytes < tb) CK(h->pm_tmp.alloc(tb + tb / 2));
-    }
-    const uint64_t m = h->pm_n;
-    auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
-    uint8_t* q = h->pm_buf.as<uint8_t>();
-    p->a = (uint32_t*)q; q += al(m * 4);
-    p->filt = (uint32_t*)q; q += al(m * 4);
-    p->cand = (uint64_t*)q; q += al(m * 8);
-    p->kept = (uint64_t*)q; q += al(m * 8);
-    p->coff = (uint64_t*)q; q += al((m + 1) * 8);
-    p->chunk = (uint64_t*)q; q += al(BFT_PM_CHUNKS * 8ull);
-    p->chunk_off = (uint64_t*)q;
-    h->pm_used = true;
-    h->pm_stream = s;
-    return 0;
-}
-static void pm_release(bft_gpu* h, hipStream_t s) {
-    if (!h->pm_ev && hipEventCreateWithFlags(&h->pm_ev, hipEventDisableTiming) != hipSuccess) { h->pm_ev = nullptr; (void)hipGetLastError(); }
-    if (h->pm_ev && hipEventRecord(h->pm_ev, s) != hipSuccess) (void)hipGetLastError();
-}
-// intervals, candidate offsets, matches per prefix -> d_offsets (n + 1; d_offsets[n] = total, also written to d_needed when it is not NULL) and
-// the chunk offsets the emit reads; every launch is timed ("timing")
-static int pm_count(bft_gpu* h, const uint8_t* d_pref, const uint8_t* d_len, uint64_t n, uint64_t* d_offsets, uint64_t* d_needed, hipStream_t s,
-                    const BftPmScratch& p) {
-    const uint64_t* tk = h->d_tk.as<uint64_t>();
-    CK(timed_launch(h, s, [&] { return bft_pm_bounds(h->W, d_pref, d_len, n, h->k, h->B, tk, h->n_kmers, p, s); }));
-    CK(timed_launch(h, s, [&] { return bft_scan::exclusive_sum_ptr<uint64_t>(p.cand, p.coff, n, s, h->pm_tmp, nullptr, true); }));
-    CK(timed_launch(h, s, [&] { return bft_pm_count(h->W, n, tk, p, s); }));
-    CK(timed_launch(h, s, [&] { return bft_scan::exclusive_sum_ptr<uint64_t>(p.kept, d_offsets, n, s, h->pm_tmp, (unsigned long long*)d_needed, true); }));
-    CK(timed_launch(h, s, [&] { return bft_scan::exclusive_sum_ptr<uint64_t>(p.chunk, p.chunk_off, BFT_PM_CHUNKS, s, h->pm_tmp, nullptr, true); }));
-    return 0;
-}
-static int pm_emit(bft_gpu* h, uint64_t n, const BftPmScratch& p, uint64_t cap, uint8_t* d_kmers, uint32_t* d_rows, uint32_t* d_cs, hipStream_t s) {
-    if (cap == 0 || (!d_kmers && !d_rows && !d_cs)) return 0;
-    return timed_launch(h, s, [&] { return bft_pm_emit(h->W, n, h->k, h->B, h->d_tk.as<uint64_t>(), h->d_tcol.as<uint32_t>(), p, cap, d_kmers, d_rows, d_cs, s); });
-}
-
-extern "C" int bft_gpu_query_prefixes_dev(bft_gpu* h, const void* d_prefixes, const void* d_lengths, uint64_t n, void* d_offsets, void* d_kmers_out,
-                                          void* d_rows_out, void* d_colorsets_out, uint64_t cap, void* d_needed, void* hip_stream) {
-    if (!h || !d_offsets || ((!d_prefixes || !d_lengths) && n)) return fail(BFT_GPU_E_ARG, "NULL argument");
-    ENTER(h);
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
-    const bool capturing = stream_capturing(s);
-    CK(ensure_built(h, false));
-    if (h->table_dropped) {  // ("compact_table": the rows come from the sorted table; bringing it back synchronises)
-        if (capturing) return fail(BFT_GPU_E_ARG, "prefix query recorded into a graph: the sorted table is not resident (compact_table); make one direct call first");
-        CK(ensure_table(h));
-    }
-    if (n == 0) {
-        CK(bft_zero_async(d_offsets, 8, s));  // (kernels, not memsets, wherever a caller may be capturing: bft_dev.h)
-        if (d_needed) CK(bft_zero_async(d_needed, 8, s));
-        return note_foreign_stream(h, s);
-    }
-    BftPmScratch p;
-    CK(pm_scratch(h, n, s, capturing, &p));
-    CK(pm_count(h, (const uint8_t*)d_prefixes, (const uint8_t*)d_lengths, n, (uint64_t*)d_offsets, (uint64_t*)d_needed, s, p));
-    CK(pm_emit(h, n, p, cap, (uint8_t*)d_kmers_out, (uint32_t*)d_rows_out, (uint32_t*)d_colorsets_out, s));
-    pm_release(h, s);
-    return note_foreign_stream(h, s);
-}
-
-// The host-buffer form: lengths are checked first, the matches counted on the device, and the outputs filled only when cap holds them all.
-extern "C" int bft_gpu_query_prefixes(bft_gpu* h, const uint8_t* prefixes, const uint8_t* lengths, uint64_t n, uint64_t* offsets, uint8_t* kmers_out,
-                                      uint32_t* rows_out, uint32_t* colorsets_out, uint64_t cap, uint64_t* needed) {
-    if (!h || !offsets || ((!prefixes || !lengths) && n)) return fail(BFT_GPU_E_ARG, "NULL argument");
-    for (uint64_t i = 0; i < n; i++)
-        if (lengths[i] < 1 || lengths[i] > h->k) return fail(BFT_GPU_E_ARG, "prefix length outside [1, k]");
-    ENTER(h);
-    CK(ensure_built(h));
-    if (n == 0) {
-        offsets[0] = 0;
-        if (needed) *needed = 0;
-        return BFT_GPU_OK;
-    }
-    const hipStream_t s = h->stream;
-    DevBuf dp, dl, doff, dneed;
-    CK(dp.alloc(n * h->B));
-    CK(dl.alloc(n));
-    CK(doff.alloc((n + 1) * 8));
-    CK(dneed.alloc(8));
-    HIPCK(hipMemcpyAsync(dp.p, prefixes, n * h->B, hipMemcpyHostToDevice, s));
-    HIPCK(hipMemcpyAsync(dl.p, lengths, n, hipMemcpyHostToDevice, s));
-    BftPmScratch p;
-    CK(pm_scratch(h, n, s, false, &p));
-    CK(pm_count(h, dp.as<uint8_t>(), dl.as<uint8_t>(), n, doff.as<uint64_t>(), dneed.as<uint64_t>(), s, p));
-    uint64_t total = 0;
-    HIPCK(hipMemcpyAsync(&total, dneed.p, 8, hipMemcpyDeviceToHost, s));
-    HIPCK(hipStreamSynchronize(s));
-    if (needed) *needed = total;
-    const bool want = kmers_out || rows_out || colorsets_out;
-    if (want && total > cap) {
-        pm_release(h, s);
-        return fail(BFT_GPU_E_NOSPACE, "prefix match buffers too small");
-    }
-    if (want && total) {
-        DevBuf dk, dr, dc;
-        if (kmers_out) CK(dk.alloc(total * h->B));
-        if (rows_out) CK(dr.alloc(total * 4));
-        if (colorsets_out) CK(dc.alloc(total * 4));
-        CK(pm_emit(h, n, p, total, dk.as<uint8_t>(), dr.as<uint32_t>(), dc.as<uint32_t>(), s));
-        if (kmers_out) HIPCK(hipMemcpyAsync(kmers_out, dk.p, total * h->B, hipMemcpyDeviceToHost, s));
-        if (rows_out) HIPCK(hipMemcpyAsync(rows_out, dr.p, total * 4, hipMemcpyDeviceToHost, s));
-        if (colorsets_out) HIPCK(hipMemcpyAsync(colorsets_out, dc.p, total * 4, hipMemcpyDeviceToHost, s));
-    }
-    HIPCK(hipMemcpyAsync(offsets, doff.p, (n + 1) * 8, hipMemcpyDeviceToHost, s));
-    HIPCK(hipStreamSynchronize(s));
-    pm_release(h, s);
-    return BFT_GPU_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// simple paths (extract_simple_paths_to_disk / extract_simple_core_paths_to_disk, reference snippets.h, src/snippets.c:115-603): degrees,
-// links, pointer jumping and spelling over the sorted table (bft_paths.hip)
-// ------------------------------------------------------------------------------------------------
-static uint64_t sp_bytes(uint64_t m, int sb) {
-    auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
-    return al(((1ull << sb) + 1) * 4) + 3 * al(m * 4) + al(m) + 2 * al(m * 16) + al(m * 8);
-}
-// The handle's scratch for an index of n rows on stream s: its own block, shared with no other query; a call on another stream first waits for
-// the last use (an event of the handle's own).
-static int sp_scratch(bft_gpu* h, uint64_t n, hipStream_t s, BftSpScratch* p) {
-    if (h->sp_used && h->sp_stream != s) {
-        HIPCK(h->sp_ev ? hipEventSynchronize(h->sp_ev) : hipDeviceSynchronize());
-        h->sp_used = false;
-    }
-    const int sb = bft_sp_bucket_bits(h->k);
-    const size_t tb = bft_scan::scratch_bytes(n + 1);
-    if (h->sp_m < n || h->sp_buf.bytes < sp_bytes(h->sp_m, sb) || h->sp_tmp.bytes < tb) {
-        if (h->sp_used) HIPCK(hipStreamSynchronize(s));
-        if (h->sp_m < n || h->sp_buf.bytes < sp_bytes(h->sp_m, sb)) {
-            const uint64_t m = std::max(n, h->sp_m);
-            CK(h->sp_buf.alloc(sp_bytes(m, sb)));
-            h->sp_m = m;
-        }
-        if (h->sp_tmp.bytes < tb) CK(h->sp_tmp.alloc(tb));
-    }
-    const uint64_t m = h->sp_m;
-    auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
-    uint8_t* q = h->sp_buf.as<uint8_t>();
-    p->sb = sb;
-    p->start = (uint32_t*)q; q += al(((1ull << sb) + 1) * 4);
-    p->succ = (uint32_t*)q; q += al(m * 4);
-    p->indeg = (uint32_t*)q; q += al(m * 4);
-    p->pred = (uint32_t*)q; q += al(m * 4);
-    p->flags = q; q += al(m);
-    p->st[0] = (uint4*)q; q += al(m * 16);
-    p->st[1] = (uint4*)q; q += al(m * 16);
-    p->choff = (uint64_t*)q;
-    h->sp_used = true;
-    h->sp_stream = s;
-    return 0;
-}
-static void sp_release(bft_gpu* h, hipStream_t s) {
-    if (!h->sp_ev && hipEventCreateWithFlags(&h->sp_ev, hipEventDisableTiming) != hipSuccess) { h->sp_ev = nullptr; (void)hipGetLastError(); }
-    if (h->sp_ev && hipEventRecord(h->sp_ev, s) != hipSuccess) (void)hipGetLastError();
-}
-// Degrees, links, ranks, lengths and both scans on stream s: d_counts = {n_paths, n_chars, longest} (24 bytes, device); *fin: the jumps' last buffer.
-// With "build_stages" on, every step is a stage (bft_gpu_build_stages), its bytes those its algorithm reads and writes.
-static int sp_count(bft_gpu* h, uint32_t t, hipStream_t s, unsigned long long* d_counts, const BftSpScratch& p, int* fin) {
-    const uint64_t n = h->n_kmers;
-    const int W = h->W, k = h->k;
-    const uint64_t* tk = h->d_tk.as<uint64_t>();
-    const double nd = (double)n, rowb = 8.0 * W;
-    CK(bft_zero_async(d_counts, 24, s));
-    CK(bft_zero_async(p.indeg, n * 4, s));
-    CK(timed_launch(h, s, [&] { return bft_sp_buckets(W, tk, n, k, p, s); }));
-    bft_stage("simple paths: buckets of the table", (double)((1ull << p.sb) + 1) * 4, s);
-    CK(timed_launch(h, s, [&] { return bft_sp_degrees(W, tk, n, k, p, s); }));
-    bft_stage("simple paths: degrees and successors", nd * (2 * rowb + 4 + 4 + 12), s);
-    CK(timed_launch(h, s, [&] { return bft_sp_links(n, t, h->d_tcol.as<uint32_t>(), h->d_cs_off.as<uint32_t>(), h->d_cs_ids.p, h->cs_w, p, s); }));
-    bft_stage("simple paths: nodes and edges", nd * (12 + 8 + (t ? 8 : 0) + 1 + 16), s);
-    int cur = 0, rounds = 0;  // (ceil(log2(n + 1)) of them: no chain is longer than n, nothing is read back)
-    for (uint64_t span = 1; span < n + 1; span <<= 1, cur ^= 1, rounds++) CK(timed_launch(h, s, [&] { return bft_sp_jump(n, p, cur, s); }));
-    *fin = cur;
-    bft_stage("simple paths: pointer jumping", nd * 48 * rounds, s);
-    CK(timed_launch(h, s, [&] { return bft_sp_ends(n, k, p, cur, d_counts + 2, s); }));
-    bft_stage("simple paths: heads, tails, lengths", nd * (16 + 1 + 4 + 8 + 4), s);
-    const uint2* hd = bft_sp_hd(p, cur);
-    CK(timed_launch(h, s, [&] { return bft_scan::exclusive_sum<uint32_t>(BftSpHead{hd, n}, p.pred, n, s, h->sp_tmp, d_counts, false); }));
-    CK(timed_launch(h, s, [&] { return bft_scan::exclusive_sum<uint64_t>(BftSpHeadLen{hd, p.indeg, n}, p.choff, n, s, h->sp_tmp, d_counts + 1, false); }));
-    bft_stage("simple paths: two scans (paths, characters)", nd * (8 + 4 + 8 + 4 + 8), s);
-    return 0;
-}
-// offsets (paths_cap + 1 entries at most) and characters (chars_cap at most) of the paths sp_count counted
-static int sp_emit(bft_gpu* h, const BftSpScratch& p, int fin, uint64_t* d_offsets, uint64_t paths_cap, char* d_seqs, uint64_t chars_cap,
-                   const unsigned long long* d_counts, hipStream_t s) {
-    const uint64_t n = h->n_kmers;
-    if (d_offsets) CK(timed_launch(h, s, [&] { return bft_sp_offsets(n, p, fin, d_offsets, paths_cap, d_counts, s); }));
-    bft_stage("simple paths: offsets", (double)n * 8, s);
-    if (d_seqs) CK(timed_launch(h, s, [&] { return bft_sp_spell(h->W, h->d_tk.as<uint64_t>(), n, h->k, p, fin, d_seqs, chars_cap, s); }));
-    bft_stage("simple paths: spelling", (double)n * (8.0 * h->W + 8 + 8 + 1), s);
-    return 0;
-}
-static int sp_prepare(bft_gpu* h) {
-    CK(ensure_built(h));  // ("compact_table": the sorted table comes back, as for rows and prefixes)
-    if (h->n_kmers >= (1ull << 31)) return fail(BFT_GPU_E_LIMIT, "simple paths: at most 2^31 - 1 k-mers");
-    return 0;
-}
-
-extern "C" int bft_gpu_simple_paths_dev(bft_gpu* h, uint32_t min_shared, void* d_offsets, void* d_seqs, uint64_t paths_cap, uint64_t chars_cap, void* d_counts,
-                                        void* hip_stream) {
-    if (!h || !d_counts) return fail(BFT_GPU_E_ARG, "NULL argument");
-    ENTER(h);
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
-    if (stream_capturing(s)) return fail(BFT_GPU_E_ARG, "simple paths recorded into a graph: not supported (the table may have to come back, scratch may grow)");
-    CK(sp_prepare(h));
-    if (h->n_kmers == 0) {
-        CK(bft_zero_async(d_counts, 24, s));
-        if (d_offsets) CK(bft_zero_async(d_offsets, 8, s));
-        return note_foreign_stream(h, s);
-    }
-    BftSpScratch p;
-    CK(sp_scratch(h, h->n_kmers, s, &p));
-    {
-        StageScope stage_scope(h, s);
-        int fin = 0;
-        CK(sp_count(h, min_shared, s, (unsigned long long*)d_counts, p, &fin));
-        CK(sp_emit(h, p, fin, (uint64_t*)d_offsets, paths_cap, (char*)d_seqs, chars_cap, (const unsigned long long*)d_counts, s));
-    }
-    sp_release(h, s);
-    return note_foreign_stream(h, s);
-}
-
-// The host-buffer form: the paths are counted on the device, and the outputs filled only when the caps hold them all.
-extern "C" int bft_gpu_simple_paths(bft_gpu* h, uint32_t min_shared, uint64_t* offsets, char* seqs, uint64_t paths_cap, uint64_t chars_cap, uint64_t* n_paths,
-                                    uint64_t* n_chars) {
-    if (!h || !n_paths || !n_chars) return fail(BFT_GPU_E_ARG, "NULL argument");
-    ENTER(h);
-    CK(sp_prepare(h));
-    *n_paths = *n_chars = 0;
-    if (h->n_kmers == 0) {
-        if (offsets) offsets[0] = 0;
-        return BFT_GPU_OK;
-    }
-    const hipStream_t s = h->stream;
-    DevBuf dcnt;
-    CK(dcnt.alloc(24));
-    BftSpScratch p;
-    CK(sp_scratch(h, h->n_kmers, s, &p));
-    StageScope stage_scope(h);
-    int fin = 0;
-    CK(sp_count(h, min_shared, s, dcnt.as<unsigned long long>(), p, &fin));
-    unsigned long long cnt[3] = {0, 0, 0};
-    HIPCK(hipMemcpyAsync(cnt, dcnt.p, 24, hipMemcpyDeviceToHost, s));
-    HIPCK(hipStreamSynchronize(s));
-    *n_paths = cnt[0];
-    *n_chars = cnt[1];
-    if ((offsets && cnt[0] > paths_cap) || (seqs && cnt[1] > chars_cap)) {
-        sp_release(h, s);
-        return fail(BFT_GPU_E_NOSPACE, "simple path buffers too small");
-    }
-    if (offsets || seqs) {
-        DevBuf doff, dseq;
-        if (offsets) CK(doff.alloc((cnt[0] + 1) * 8));
-        if (seqs && cnt[1]) CK(dseq.alloc(cnt[1]));
-        CK(sp_emit(h, p, fin, offsets ? doff.as<uint64_t>() : nullptr, cnt[0], seqs ? dseq.as<char>() : nullptr, cnt[1], dcnt.as<unsigned long long>(), s));
-        if (offsets) HIPCK(hipMemcpyAsync(offsets, doff.p, (cnt[0] + 1) * 8, hipMemcpyDeviceToHost, s));
-        if (seqs && cnt[1]) HIPCK(hipMemcpyAsync(seqs, dseq.p, cnt[1], hipMemcpyDeviceToHost, s));
-        HIPCK(hipStreamSynchronize(s));
-    }
-    sp_release(h, s);
-    return BFT_GPU_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// connected components (get_nb_connected_component with BFS / DFS / BFS_subgraph / DFS_subgraph, reference snippets.h, src/snippets.c:605-960):
-// membership, a lock-free union-find over the successor edges, numbering and sizes over the sorted table (bft_components.hip)
-// ------------------------------------------------------------------------------------------------
-static uint64_t cc_bytes(uint64_t m, uint64_t sets, int sb) {
-    auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
-    return al(((1ull << sb) + 1) * 4) + 2 * al(m * 4) + al(sets);
-}
-// The handle's scratch for an index of n rows and n_sets colour sets on stream s: its own block, shared with no other query; a call on another
-// stream first waits for the last use (an event of the handle's own).
-static int cc_scratch(bft_gpu* h, uint64_t n, uint64_t n_sets, hipStream_t s, BftCcScratch* p) {
-    if (h->cc_used && h->cc_stream != s) {
-        HIPCK(h->cc_ev ? hipEventSynchronize(h->cc_ev) : hipDeviceSynchronize());
-        h->cc_used = false;
-    }
-    const int sb = bft_sp_bucket_bits(h->k);
-    const size_t tb = bft_scan::scratch_bytes(n + 1);
-    if (h->cc_m < n || h->cc_sets < n_sets || h->cc_buf.bytes < cc_bytes(h->cc_m, h->cc_sets, sb) || h->cc_tmp.bytes < tb) {
-        if (h->cc_used) HIPCK(hipStreamSynchronize(s));
-        if (h->cc_m < n || h->cc_sets < n_sets || h->cc_buf.bytes < cc_bytes(h->cc_m, h->cc_sets, sb)) {
-            const uint64_t m = std::max(n, h->cc_m), ns = std::max(n_sets, h->cc_sets);
-            CK(h->cc_buf.alloc(cc_bytes(m, ns, sb)));
-            h->cc_m = m;
-            h->cc_sets = ns;
-        }
-        if (h->cc_tmp.bytes < tb) CK(h->cc_tmp.alloc(tb));
-    }
-    auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
-    uint8_t* q = h->cc_buf.as<uint8_t>();
-    p->sp = BftSpScratch{};
-    p->sp.sb = sb;
-    p->sp.start = (uint32_t*)q; q += al(((1ull << sb) + 1) * 4);
-    p->parent = (uint32_t*)q; q += al(h->cc_m * 4);
-    p->num = (uint32_t*)q; q += al(h->cc_m * 4);
-    p->member = q;
-    h->cc_used = true;
-    h->cc_stream = s;
-    return 0;
-}
-static void cc_release(bft_gpu* h, hipStream_t s) {
-    if (!h->cc_ev && hipEventCreateWithFlags(&h->cc_ev, hipEventDisableTiming) != hipSuccess) { h->cc_ev = nullptr; (void)hipGetLastError(); }
-    if (h->cc_ev && hipEventRecord(h->cc_ev, s) != hipSuccess) (void)hipGetLastError();
-}
-// Membership, forest, numbering, labels and sizes on stream s: d_counts = {n_components, n_members, largest} (24 bytes, device); the labels stay in
-// p.num, the sizes in p.parent.  d_labels / d_sizes (may be NULL): the labels, the sizes below sizes_cap.  The number of launches depends on nb alone.
-// With "build_stages" on, every step is a stage (bft_gpu_build_stages), its bytes those its algorithm reads and writes.
-static int cc_run(bft_gpu* h, const uint32_t* ids, uint32_t nb, hipStream_t s, unsigned long long* d_counts, const BftCcScratch& p, uint32_t* d_labels,
-                  uint64_t* d_sizes, uint64_t sizes_cap) {
-    const uint64_t n = h->n_kmers, ns = h->n_sets;
-    const int W = h->W, k = h->k;
-    const uint64_t* tk = h->d_tk.as<uint64_t>();
-    const double nd = (double)n, rowb = 8.0 * W;
-    CK(bft_zero_async(d_counts, 24, s));
-    for (uint32_t j = 0; j < nb; j += BFT_CC_IDS)
-        CK(timed_launch(h, s, [&] { return bft_cc_sets(ns, h->d_cs_off.as<uint32_t>(), h->d_cs_ids.p, h->cs_w, ids + j, nb - j, j == 0, p, s); }));
-    if (nb) bft_stage("components: members among the colour sets", (double)ns * 9 + (double)h->n_ids * h->cs_w, s);
-    CK(timed_launch(h, s, [&] { return bft_cc_init(n, nb ? h->d_tcol.as<uint32_t>() : nullptr, p, s); }));
-    bft_stage("components: members", nd * (4 + (nb ? 5 : 0)), s);
-    CK(timed_launch(h, s, [&] { return bft_sp_buckets(W, tk, n, k, p.sp, s); }));
-    bft_stage("components: buckets of the table", (double)((1ull << p.sp.sb) + 1) * 4, s);
-    CK(timed_launch(h, s, [&] { return bft_cc_hook(W, tk, n, k, p, s); }));
-    bft_stage("components: successors and hooking", nd * (2 * rowb + 4 + 4 + 8), s);
-    CK(timed_launch(h, s, [&] { return bft_cc_flatten(n, p, s); }));
-    bft_stage("components: roots", nd * 12, s);
-    CK(timed_launch(h, s, [&] { return bft_scan::exclusive_sum<uint32_t>(BftCcMember{p.parent}, p.num, n, s, h->cc_tmp, d_counts + 1, false); }));
-    CK(timed_launch(h, s, [&] { return bft_scan::exclusive_sum<uint32_t>(BftCcRoot{p.parent}, p.num, n, s, h->cc_tmp, d_counts, false); }));
-    bft_stage("components: two scans (members, components)", nd * 16, s);
-    CK(timed_launch(h, s, [&] { return bft_cc_label(n, p, d_labels, s); }));
-    bft_stage("components: labels", nd * (4 + 4 + 4 + 4 + (d_labels ? 4 : 0)), s);
-    CK(timed_launch(h, s, [&] { return bft_cc_count(n, p, s); }));
-    bft_stage("components: sizes", nd * 4, s);
-    CK(timed_launch(h, s, [&] { return bft_cc_sizes(n, p, d_sizes, sizes_cap, d_counts, s); }));
-    bft_stage("components: sizes out, largest", 0.0, s);  // (n_components entries: not known on the host without a read-back)
-    return 0;
-}
-static int cc_prepare(bft_gpu* h) {
-    CK(ensure_built(h));  // ("compact_table": the sorted table comes back, as for rows, prefixes and simple paths)
-    if (h->n_kmers >= (1ull << 31)) return fail(BFT_GPU_E_LIMIT, "components: at most 2^31 - 1 k-mers");
-    return 0;
-}
-
-extern "C" int bft_gpu_components_dev(bft_gpu* h, const uint32_t* genome_ids, uint32_t nb_ids, void* d_labels, void* d_sizes, uint64_t sizes_cap, void* d_counts,
-                                      void* hip_stream) {
-    if (!h || !d_counts || (nb_ids && !genome_ids)) return fail(BFT_GPU_E_ARG, "NULL argument");
-    for (uint32_t j = 1; j < nb_ids; j++)
-        if (genome_ids[j] <= genome_ids[j - 1]) return fail(BFT_GPU_E_ARG, "components: genome ids must be strictly increasing");
-    ENTER(h);
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
-    if (stream_capturing(s)) return fail(BFT_GPU_E_ARG, "components recorded into a graph: not supported (the table may have to come back, scratch may grow)");
-    CK(cc_prepare(h));
-    if (h->n_kmers == 0) {
-        CK(bft_zero_async(d_counts, 24, s));
-        return note_foreign_stream(h, s);
-    }
-    BftCcScratch p;
-    CK(cc_scratch(h, h->n_kmers, h->n_sets, s, &p));
-    {
-        StageScope stage_scope(h, s);
-        CK(cc_run(h, genome_ids, nb_ids, s, (unsigned long long*)d_counts, p, (uint32_t*)d_labels, (uint64_t*)d_sizes, sizes_cap));
-    }
-    cc_release(h, s);
-    return note_foreign_stream(h, s);
-}
-
-// The host-buffer form: the components are counted on the device, and the outputs filled only when the caps hold them all.
-extern "C" int bft_gpu_components(bft_gpu* h, const uint32_t* genome_ids, uint32_t nb_ids, uint32_t* labels, uint64_t labels_cap, uint64_t* sizes,
-                                  uint64_t sizes_cap, uint64_t* counts) {
-    if (!h || !counts || (nb_ids && !genome_ids)) return fail(BFT_GPU_E_ARG, "NULL argument");
-    for (uint32_t j = 1; j < nb_ids; j++)
-        if (genome_ids[j] <= genome_ids[j - 1]) return fail(BFT_GPU_E_ARG, "components: genome ids must be strictly increasing");
-    ENTER(h);
-    CK(cc_prepare(h));
-    counts[0] = counts[1] = counts[2] = 0;
-    const uint64_t n = h->n_kmers;
-    if (n == 0) return BFT_GPU_OK;
-    const hipStream_t s = h->stream;
-    DevBuf dcnt;
-    CK(dcnt.alloc(24));
-    BftCcScratch p;
-    CK(cc_scratch(h, n, h->n_sets, s, &p));
-    StageScope stage_scope(h);
-    CK(cc_run(h, genome_ids, nb_ids, s, dcnt.as<unsigned long long>(), p, nullptr, nullptr, 0));
-    unsigned long long cnt[3] = {0, 0, 0};
-    HIPCK(hipMemcpyAsync(cnt, dcnt.p, 24, hipMemcpyDeviceToHost, s));
-    HIPCK(hipStreamSynchronize(s));
-    for (int i = 0; i < 3; i++) counts[i] = cnt[i];
-    if ((labels && labels_cap < n) || (sizes && sizes_cap < cnt[0])) {
-        cc_release(h, s);
-        return fail(BFT_GPU_E_NOSPACE, "component buffers too small");
-    }
-    DevBuf dsz;
-    if (sizes && cnt[0]) {  // (the counters are 32-bit in the scratch: widened by a second pass of the last kernel)
-        CK(dsz.alloc(cnt[0] * 8));
-        CK(timed_launch(h, s, [&] { return bft_cc_sizes(n, p, dsz.as<uint64_t>(), cnt[0], dcnt.as<unsigned long long>(), s); }));
-        HIPCK(hipMemcpyAsync(sizes, dsz.p, cnt[0] * 8, hipMemcpyDeviceToHost, s));
-    }
-    if (labels) HIPCK(hipMemcpyAsync(labels, p.num, n * 4, hipMemcpyDeviceToHost, s));
-    if (labels || sizes) HIPCK(hipStreamSynchronize(s));
-    cc_release(h, s);
-    return BFT_GPU_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// sub-graphs (create_cdbg_from_bft_kmers, include/bft.h:179, src/bft.c:1353-1464): the batch looked up in the source, the found k-mers
-// sorted and de-duplicated, the used part of the dictionary renumbered (bft_subgraph.hip), then the common tail of a build (commit_image)
-// ------------------------------------------------------------------------------------------------
-struct SgEvent {
-    hipEvent_t e = nullptr;
-    ~SgEvent() { if (e) (void)hipEventDestroy(e); }
-};
-// d: a fresh handle with src's k and seeds.  The lookup runs on s (the caller's stream: d_kmers is read in its order), everything after it on
-// d's stream; the new launches are timed on src ("timing"), the stages recorded on d when src records them ("build_stages").
-static int subgraph_fill(bft_gpu* src, bft_gpu* d, const uint8_t* d_kmers, uint64_t n, bool colors, uint64_t* n_absent, hipStream_t s) {
-    const int W = src->W;
-    if (colors) {
-        d->genomes = src->genomes;
-        d->max_gid_seen = src->max_gid_seen;
-        d->any_insert = src->any_insert;
-    } else {  // (one genome, named after the source's genome 0)
-        if (!src->genomes.empty()) d->genomes.push_back(src->genomes[0]);
-        d->any_insert = true;
-    }
-    d->opt_build_stages = src->opt_build_stages;
-    CK(set_device(d));  // (from here on the cache hands out blocks for d's stream)
-    const hipStream_t ds = d->stream;
-    StageScope stage_scope(d);
-    const double t0 = now_ms();
-    SgEvent ev;
-    HIPCK(hipEventCreateWithFlags(&ev.e, hipEventDisableTiming));
-
-    // 1. lookup: the colour-set id of every found k-mer, from the k-mer hash or -- an image without one -- the walk's tcol[row]
-    DevBuf bits, cs, cnt, keys, vals;
-    CK(bits.alloc(((n + 63) / 64) * 8));
-    CK(cs.alloc(n * 4));
-    CK(cnt.alloc_zero(8, ds));
-    unsigned long long m = 0;
-    if (n) {
-        HIPCK(hipEventRecord(ev.e, ds));  // (the blocks above may still be in use on d's stream)
-        HIPCK(hipStreamWaitEvent(s, ev.e, 0));
-        src->im.emit_cs = 1;
-        const int rc = launch_query(src, d_kmers, n, bits.as<uint64_t>(), cs.as<uint32_t>(), s);
-        src->im.emit_cs = 0;
-        CK(rc);
-        CK(note_foreign_stream(src, s));
-        HIPCK(hipEventRecord(ev.e, s));
-        HIPCK(hipStreamWaitEvent(ds, ev.e, 0));
-        bft_stage("sub-graph: lookup in the source", (double)n * (src->B + 4) + (double)n / 8, ds);
-        // 2. the found ones as (T-form key, colour-set id) records
-        CK(keys.alloc(n * W * 8));
-        CK(vals.alloc(n * 4));
-        CK(timed_launch(src, ds, [&] {
-            return bft_sg_compact(W, d_kmers, n, src->k, src->B, bits.as<uint64_t>(), cs.as<uint32_t>(), keys.as<uint64_t>(), n, vals.as<uint32_t>(),
-                                  cnt.as<unsigned long long>(), ds);
-        }));
-        HIPCK(hipMemcpyAsync(&m, cnt.p, 8, hipMemcpyDeviceToHost, ds));
-        HIPCK(hipStreamSynchronize(ds));
-        bft_stage("sub-graph: found k-mers compacted", (double)n * (src->B + 4) + (double)m * (8 * W + 4), ds);
-    }
-    bits.release();
-    cs.release();
-    if (n_absent) *n_absent = n - m;
-
-    // 3. order (the library's sort, keys only: equal keys carry equal ids) and de-duplication (first record of every run: one scan)
-    DevBuf tk, tcol;
-    uint64_t nk = 0;
-    if (m) {
-        DevBuf sk, sg, pos, tmp;
-        CK(sk.alloc(m * W * 8));
-        CK(sg.alloc(m * 4));
-        CK(timed_launch(src, ds, [&] { return sort_pairs(d, keys.as<uint64_t>(), n, vals.as<uint32_t>(), m, sk.as<uint64_t>(), m, sg.as<uint32_t>(), true); }));
-        keys.release();
-        vals.release();
-        CK(pos.alloc((m + 1) * 4));
-        const BftSgHeads heads{sk.as<uint64_t>(), m, m, W};
-        CK(timed_launch(src, ds, [&] { return bft_scan::exclusive_sum<uint32_t>(heads, pos.as<uint32_t>(), m, ds, tmp, nullptr, true); }));
-        uint32_t nk32 = 0;
-        HIPCK(hipMemcpyAsync(&nk32, pos.as<uint32_t>() + m, 4, hipMemcpyDeviceToHost, ds));
-        HIPCK(hipStreamSynchronize(ds));
-        nk = nk32;
-        CK(tk.alloc(nk * W * 8));
-        CK(tcol.alloc(nk * 4));
-        CK(timed_launch(src, ds, [&] { return bft_sg_scatter(W, sk.as<uint64_t>(), m, sg.as<uint32_t>(), m, pos.as<uint32_t>(), tk.as<uint64_t>(), tcol.as<uint32_t>(), ds); }));
-        HIPCK(hipStreamSynchronize(ds));
-    } else {
-        CK(tcol.alloc(4));
-    }
-    bft_stage("sub-graph: sort + dedupe", (double)m * (8 * W + 4) * 6 + (double)nk * (8 * W + 4), ds);
-
-    // 4. the dictionary: the used sets of the source in their old order (colours), or the one set {0}
-    DevBuf cs_off, cs_ids;
-    uint64_t n_sets = 0, n_ids = 0, np = 0;
-    if (nk && colors) {
-        const uint64_t S = src->n_sets;
-        DevBuf used, new_id, id_pos, tmp;
-        CK(used.alloc_zero(S * 4, ds));
-        CK(new_id.alloc((S + 1) * 4));
-        CK(id_pos.alloc((S + 1) * 4));
-        const uint32_t* old_off = src->d_cs_off.as<uint32_t>();
-        CK(timed_launch(src, ds, [&] { return bft_sg_mark(tcol.as<uint32_t>(), nk, used.as<uint32_t>(), ds); }));
-        CK(timed_launch(src, ds, [&] { return bft_scan::exclusive_sum_ptr<uint32_t>(used.as<uint32_t>(), new_id.as<uint32_t>(), S, ds, tmp, nullptr, true); }));
-        const BftSgUsedLen lens{used.as<uint32_t>(), old_off, S};
-        CK(timed_launch(src, ds, [&] { return bft_scan::exclusive_sum<uint32_t>(lens, id_pos.as<uint32_t>(), S, ds, tmp, nullptr, true); }));
-        uint32_t tot[2] = {0, 0};
-        HIPCK(hipMemcpyAsync(&tot[0], new_id.as<uint32_t>() + S, 4, hipMemcpyDeviceToHost, ds));
-        HIPCK(hipMemcpyAsync(&tot[1], id_pos.as<uint32_t>() + S, 4, hipMemcpyDeviceToHost, ds));
-        HIPCK(hipStreamSynchronize(ds));
-        n_sets = tot[0];
-        n_ids = tot[1];
-        CK(cs_off.alloc((n_sets + 1) * 4));
-        CK(cs_ids.alloc(n_ids * 4));
-        CK(timed_launch(src, ds, [&] { return bft_sg_remap(tcol.as<uint32_t>(), nk, new_id.as<uint32_t>(), ds); }));
-        CK(timed_launch(src, ds, [&] {
-            return bft_sg_dict(used.as<uint32_t>(), new_id.as<uint32_t>(), id_pos.as<uint32_t>(), old_off, src->d_cs_ids.p, src->cs_w, S, cs_off.as<uint32_t>(),
-                               cs_ids.as<uint32_t>(), ds);
-        }));
-        CK(bft_count_pairs(tcol.as<uint32_t>(), nk, cs_off.as<uint32_t>(), ds, &np));
-        bft_stage("sub-graph: used part of the dictionary", (double)nk * 12 + (double)S * 16 + (double)n_ids * (src->cs_w + 4), ds);
-    } else if (nk) {
-        static const uint32_t one_set[3] = {0, 1, 0};  // cs_off = {0, 1}, cs_ids = {0}
-        CK(cs_off.alloc(8));
-        CK(cs_ids.alloc(4));
-        HIPCK(hipMemsetAsync(tcol.p, 0, nk * 4, ds));
-        HIPCK(hipMemcpyAsync(cs_off.p, one_set, 8, hipMemcpyHostToDevice, ds));
-        HIPCK(hipMemcpyAsync(cs_ids.p, one_set + 2, 4, hipMemcpyHostToDevice, ds));
-        n_sets = 1;
-        n_ids = 1;
-        np = nk;
-    } else {
-        CK(cs_off.alloc_zero(4, ds));
-        CK(cs_ids.alloc(4));
-    }
-    HIPCK(hipStreamSynchronize(ds));
-    const double t1 = now_ms();
-
-    // 5-7. containers, flat forms, k-mer hash, root tables, commit: the build's own tail
-    KhFill khf;
-    BftInternTail tail;  // (nothing deferred: no interning here)
-    DevBuf seg_off, npg;
-    return commit_image(d, tk, tcol, cs_off, cs_ids, nk, n_sets, n_ids, np, khf, tail, seg_off, npg, t0, t1);
-}
-
-static int subgraph_new(bft_gpu* src, const uint8_t* d_kmers, uint64_t n, int colors, uint64_t* n_absent, bft_gpu** out, hipStream_t s) {
-    if (n >= (1ull << 31)) return fail(BFT_GPU_E_LIMIT, "sub-graph batch of 2^31 k-mers or more");
-    if (stream_capturing(s)) return fail(BFT_GPU_E_ARG, "sub-graph recorded into a graph: it allocates and synchronises");
-    CK(ensure_built(src, false));
-    if (!(src->im.kh_lines != nullptr && !src->opt_walk_hash)) CK(ensure_table(src));  // (the walk answers: launch_query would bring the table back itself)
-    HIPCK(hipStreamSynchronize(src->stream));
-    bft_gpu* d = nullptr;
-    CK(bft_gpu_create_seeded(src->k, src->device, src->r1, src->r2, &d));
-    const int rc = subgraph_fill(src, d, d_kmers, n, colors != 0, n_absent, s);
-    if (rc) {
-        const std::string err = g_err;
-        bft_gpu_free(d);
-        return fail(rc, err);
-    }
-    *out = d;
-    return BFT_GPU_OK;
-}
-
-extern "C" int bft_gpu_subgraph_dev(bft_gpu* src, const void* d_kmers, uint64_t nb_kmers, int colors, uint64_t* n_absent, bft_gpu** out, void* hip_stream) {
-    if (!src || !out || (!d_kmers && nb_kmers)) return fail(BFT_GPU_E_ARG, "NULL argument");
-    *out = nullptr;
-    ENTER(src);
-    return subgraph_new(src, (const uint8_t*)d_kmers, nb_kmers, colors, n_absent, out, hip_stream ? (hipStream_t)hip_stream : src->stream);
-}
-
-extern "C" int bft_gpu_subgraph(bft_gpu* src, const uint8_t* kmers, uint64_t nb_kmers, int colors, uint64_t* n_absent, bft_gpu** out) {
-    if (!src || !out || (!kmers && nb_kmers)) return fail(BFT_GPU_E_ARG, "NULL argument");
-    *out = nullptr;
-    ENTER(src);
-    DevBuf dk;
-    if (nb_kmers) {
-        CK(dk.alloc(nb_kmers * src->B));
-        HIPCK(hipMemcpy(dk.p, kmers, nb_kmers * src->B, hipMemcpyHostToDevice));
-    }
-    return subgraph_new(src, dk.as<uint8_t>(), nb_kmers, colors, n_absent, out, src->stream);
 }
 
 // The colour set `cs` in the reference's annotation bytes (smallest of modes 0/1/2, compute_best_mode,
@@ -4125,7 +3278,7 @@ extern "C" int bft_gpu_subgraph(bft_gpu* src, const uint8_t* kmers, uint64_t nb_
 extern "C" int bft_gpu_colorset_annot(bft_gpu* h, uint32_t cs, uint8_t* annot, uint32_t cap, uint32_t* n_out) {
     if (!h) return fail(BFT_GPU_E_ARG, "NULL handle");
     ENTER(h);
-    CK(ensure_built(h, false));
+    CK(bft_ensure_built(h, false));
     CK(host_colorsets(h));
     if ((uint64_t)cs + 1 >= h->cs_off.size()) return fail(BFT_GPU_E_ARG, "unknown colour set");
     const uint32_t a = h->cs_off[cs], b = h->cs_off[cs + 1];

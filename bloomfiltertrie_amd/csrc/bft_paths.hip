@@ -21,7 +21,9 @@
 #include <type_traits>
 
 #include "bft_dev.h"
+#include "bft_handle.h"
 #include "bft_paths.h"
+#include "bft_scan.h"
 #include "bft_succ.h"
 
 namespace {
@@ -245,4 +247,138 @@ int bft_sp_spell(int W, const uint64_t* d_tk, uint64_t n, int k, const BftSpScra
     return sp_dispatch(W, [&](auto KW) {
         hipLaunchKernelGGL((k_sp_spell<KW>), sp_grid(n), dim3(SP_THREADS), 0, s, d_tk, (uint32_t)n, k, bft_sp_hd(p, fin), p.choff, d_seqs, chars_cap);
     });
+}
+
+// ------------------------------------------------------------------------------------------------
+// the C-ABI entry points: the handle's scratch, the chain of launches, the host-buffer form
+// ------------------------------------------------------------------------------------------------
+// the arrays of a block with room for m rows (p->sb set), from `base` on; returns the block's size
+static size_t sp_carve(uint64_t m, uint8_t* base, BftSpScratch* p) {
+    Carver c{base};
+    c.take(p->start, ((1ull << p->sb) + 1) * 4);
+    c.take(p->succ, m * 4);
+    c.take(p->indeg, m * 4);
+    c.take(p->pred, m * 4);
+    c.take(p->flags, m);
+    c.take(p->st[0], m * 16);
+    c.take(p->st[1], m * 16);
+    c.take(p->choff, m * 8);
+    return c.off;
+}
+// The handle's scratch (h->sp: HandleScratch, bft_handle.h) for an index of n rows on stream s: its own block, shared with no other query, sized exactly.
+static int sp_scratch(bft_gpu* h, uint64_t n, hipStream_t s, BftSpScratch* p) {
+    CK(h->sp.acquire(s, false));  // (the entry points refuse a capturing stream)
+    p->sb = bft_sp_bucket_bits(h->k);
+    h->sp_m = std::max(n, h->sp_m);
+    CK(h->sp.grow(h->sp_buf, sp_carve(h->sp_m, nullptr, p), 0));
+    CK(h->sp.grow(h->sp_tmp, bft_scan::scratch_bytes(n + 1), 0));
+    sp_carve(h->sp_m, h->sp_buf.as<uint8_t>(), p);
+    return 0;
+}
+// Degrees, links, ranks, lengths and both scans on stream s: d_counts = {n_paths, n_chars, longest} (24 bytes, device); *fin: the jumps' last buffer.
+// With "build_stages" on, every step is a stage (bft_gpu_build_stages), its bytes those its algorithm reads and writes.
+static int sp_count(bft_gpu* h, uint32_t t, hipStream_t s, unsigned long long* d_counts, const BftSpScratch& p, int* fin) {
+    const uint64_t n = h->n_kmers;
+    const int W = h->W, k = h->k;
+    const uint64_t* tk = h->d_tk.as<uint64_t>();
+    const double nd = (double)n, rowb = 8.0 * W;
+    CK(bft_zero_async(d_counts, 24, s));
+    CK(bft_zero_async(p.indeg, n * 4, s));
+    CK(bft_timed_launch(h, s, [&] { return bft_sp_buckets(W, tk, n, k, p, s); }));
+    bft_stage("simple paths: buckets of the table", (double)((1ull << p.sb) + 1) * 4, s);
+    CK(bft_timed_launch(h, s, [&] { return bft_sp_degrees(W, tk, n, k, p, s); }));
+    bft_stage("simple paths: degrees and successors", nd * (2 * rowb + 4 + 4 + 12), s);
+    CK(bft_timed_launch(h, s, [&] { return bft_sp_links(n, t, h->d_tcol.as<uint32_t>(), h->d_cs_off.as<uint32_t>(), h->d_cs_ids.p, h->cs_w, p, s); }));
+    bft_stage("simple paths: nodes and edges", nd * (12 + 8 + (t ? 8 : 0) + 1 + 16), s);
+    int cur = 0, rounds = 0;  // (ceil(log2(n + 1)) of them: no chain is longer than n, nothing is read back)
+    for (uint64_t span = 1; span < n + 1; span <<= 1, cur ^= 1, rounds++) CK(bft_timed_launch(h, s, [&] { return bft_sp_jump(n, p, cur, s); }));
+    *fin = cur;
+    bft_stage("simple paths: pointer jumping", nd * 48 * rounds, s);
+    CK(bft_timed_launch(h, s, [&] { return bft_sp_ends(n, k, p, cur, d_counts + 2, s); }));
+    bft_stage("simple paths: heads, tails, lengths", nd * (16 + 1 + 4 + 8 + 4), s);
+    const uint2* hd = bft_sp_hd(p, cur);
+    CK(bft_timed_launch(h, s, [&] { return bft_scan::exclusive_sum<uint32_t>(BftSpHead{hd, n}, p.pred, n, s, h->sp_tmp, d_counts, false); }));
+    CK(bft_timed_launch(h, s, [&] { return bft_scan::exclusive_sum<uint64_t>(BftSpHeadLen{hd, p.indeg, n}, p.choff, n, s, h->sp_tmp, d_counts + 1, false); }));
+    bft_stage("simple paths: two scans (paths, characters)", nd * (8 + 4 + 8 + 4 + 8), s);
+    return 0;
+}
+// offsets (paths_cap + 1 entries at most) and characters (chars_cap at most) of the paths sp_count counted
+static int sp_emit(bft_gpu* h, const BftSpScratch& p, int fin, uint64_t* d_offsets, uint64_t paths_cap, char* d_seqs, uint64_t chars_cap,
+                   const unsigned long long* d_counts, hipStream_t s) {
+    const uint64_t n = h->n_kmers;
+    if (d_offsets) CK(bft_timed_launch(h, s, [&] { return bft_sp_offsets(n, p, fin, d_offsets, paths_cap, d_counts, s); }));
+    bft_stage("simple paths: offsets", (double)n * 8, s);
+    if (d_seqs) CK(bft_timed_launch(h, s, [&] { return bft_sp_spell(h->W, h->d_tk.as<uint64_t>(), n, h->k, p, fin, d_seqs, chars_cap, s); }));
+    bft_stage("simple paths: spelling", (double)n * (8.0 * h->W + 8 + 8 + 1), s);
+    return 0;
+}
+static int sp_prepare(bft_gpu* h) {
+    CK(bft_ensure_built(h));  // ("compact_table": the sorted table comes back, as for rows and prefixes)
+    if (h->n_kmers >= (1ull << 31)) return bft_fail(BFT_GPU_E_LIMIT, "simple paths: at most 2^31 - 1 k-mers");
+    return 0;
+}
+
+extern "C" int bft_gpu_simple_paths_dev(bft_gpu* h, uint32_t min_shared, void* d_offsets, void* d_seqs, uint64_t paths_cap, uint64_t chars_cap, void* d_counts,
+                                        void* hip_stream) {
+    if (!h || !d_counts) return bft_fail(BFT_GPU_E_ARG, "NULL argument");
+    ENTER(h);
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
+    if (bft_stream_capturing(s)) return bft_fail(BFT_GPU_E_ARG, "simple paths recorded into a graph: not supported (the table may have to come back, scratch may grow)");
+    CK(sp_prepare(h));
+    if (h->n_kmers == 0) {
+        CK(bft_zero_async(d_counts, 24, s));
+        if (d_offsets) CK(bft_zero_async(d_offsets, 8, s));
+        return bft_note_foreign_stream(h, s);
+    }
+    BftSpScratch p;
+    CK(sp_scratch(h, h->n_kmers, s, &p));
+    {
+        StageScope stage_scope(h, s);
+        int fin = 0;
+        CK(sp_count(h, min_shared, s, (unsigned long long*)d_counts, p, &fin));
+        CK(sp_emit(h, p, fin, (uint64_t*)d_offsets, paths_cap, (char*)d_seqs, chars_cap, (const unsigned long long*)d_counts, s));
+    }
+    h->sp.release();
+    return bft_note_foreign_stream(h, s);
+}
+
+// The host-buffer form: the paths are counted on the device, and the outputs filled only when the caps hold them all.
+extern "C" int bft_gpu_simple_paths(bft_gpu* h, uint32_t min_shared, uint64_t* offsets, char* seqs, uint64_t paths_cap, uint64_t chars_cap, uint64_t* n_paths,
+                                    uint64_t* n_chars) {
+    if (!h || !n_paths || !n_chars) return bft_fail(BFT_GPU_E_ARG, "NULL argument");
+    ENTER(h);
+    CK(sp_prepare(h));
+    *n_paths = *n_chars = 0;
+    if (h->n_kmers == 0) {
+        if (offsets) offsets[0] = 0;
+        return BFT_GPU_OK;
+    }
+    const hipStream_t s = h->stream;
+    DevBuf dcnt;
+    CK(dcnt.alloc(24));
+    BftSpScratch p;
+    CK(sp_scratch(h, h->n_kmers, s, &p));
+    StageScope stage_scope(h);
+    int fin = 0;
+    CK(sp_count(h, min_shared, s, dcnt.as<unsigned long long>(), p, &fin));
+    unsigned long long cnt[3] = {0, 0, 0};
+    HIPCK(hipMemcpyAsync(cnt, dcnt.p, 24, hipMemcpyDeviceToHost, s));
+    HIPCK(hipStreamSynchronize(s));
+    *n_paths = cnt[0];
+    *n_chars = cnt[1];
+    if ((offsets && cnt[0] > paths_cap) || (seqs && cnt[1] > chars_cap)) {
+        h->sp.release();
+        return bft_fail(BFT_GPU_E_NOSPACE, "simple path buffers too small");
+    }
+    if (offsets || seqs) {
+        DevBuf doff, dseq;
+        if (offsets) CK(doff.alloc((cnt[0] + 1) * 8));
+        if (seqs && cnt[1]) CK(dseq.alloc(cnt[1]));
+        CK(sp_emit(h, p, fin, offsets ? doff.as<uint64_t>() : nullptr, cnt[0], seqs ? dseq.as<char>() : nullptr, cnt[1], dcnt.as<unsigned long long>(), s));
+        if (offsets) HIPCK(hipMemcpyAsync(offsets, doff.p, (cnt[0] + 1) * 8, hipMemcpyDeviceToHost, s));
+        if (seqs && cnt[1]) HIPCK(hipMemcpyAsync(seqs, dseq.p, cnt[1], hipMemcpyDeviceToHost, s));
+        HIPCK(hipStreamSynchronize(s));
+    }
+    h->sp.release();
+    return BFT_GPU_OK;
 }

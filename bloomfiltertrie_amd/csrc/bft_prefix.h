@@ -1,4 +1,4 @@
-// bft_prefix.h -- batched prefix matching (bft_prefix.hip): the launchers bft_gpu.hip chains with its scans.
+// bft_prefix.h -- batched prefix matching (bft_prefix.hip): the launchers the entry points there chain with the library's scans.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -15,9 +15,11 @@
 // Nothing here depends on the number of candidates on the host: the chunk size is derived on the device from the last candidate offset,
 // so a *_dev call does not synchronise.
 #include "bft_dev.h"
+#include "bft_handle.h"
 #include "bft_image.h"
 #include "bft_kernels_load.h"
 #include "bft_prefix.h"
+#include "bft_scan.h"
 #include "bft_walk.h"
 
 namespace {
@@ -245,4 +247,119 @@ int bft_pm_emit(int W, uint64_t n, int k, int B, const uint64_t* d_tk, const uin
     }
     HIPCK(hipGetLastError());
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the C-ABI entry points: the handle's scratch, the chain of launches, the host-buffer form
+// ------------------------------------------------------------------------------------------------
+// the arrays of a block with room for m prefixes, from `base` on; returns the block's size
+static size_t pm_carve(uint64_t m, uint8_t* base, BftPmScratch* p) {
+    Carver c{base};
+    c.take(p->a, m * 4);
+    c.take(p->filt, m * 4);
+    c.take(p->cand, m * 8);
+    c.take(p->kept, m * 8);
+    c.take(p->coff, (m + 1) * 8);
+    c.take(p->chunk, BFT_PM_CHUNKS * 8ull);
+    c.take(p->chunk_off, (BFT_PM_CHUNKS + 1) * 8ull);
+    return c.off;
+}
+// The handle's scratch (h->pm: HandleScratch, bft_handle.h) for a batch of n prefixes on stream s; a new block has room for half as many again.
+static int pm_scratch(bft_gpu* h, uint64_t n, hipStream_t s, bool capturing, BftPmScratch* p) {
+    CK(h->pm.acquire(s, capturing));
+    const size_t tb = bft_scan::scratch_bytes(std::max<uint64_t>(n, BFT_PM_CHUNKS) + 1);
+    if (h->pm_n < n) h->pm_n = n + n / 2;
+    CK(h->pm.grow(h->pm_buf, pm_carve(h->pm_n, nullptr, p), 0));
+    CK(h->pm.grow(h->pm_tmp, tb, tb / 2));
+    pm_carve(h->pm_n, h->pm_buf.as<uint8_t>(), p);
+    return 0;
+}
+// intervals, candidate offsets, matches per prefix -> d_offsets (n + 1; d_offsets[n] = total, also written to d_needed when it is not NULL) and
+// the chunk offsets the emit reads; every launch is timed ("timing")
+static int pm_count(bft_gpu* h, const uint8_t* d_pref, const uint8_t* d_len, uint64_t n, uint64_t* d_offsets, uint64_t* d_needed, hipStream_t s,
+                    const BftPmScratch& p) {
+    const uint64_t* tk = h->d_tk.as<uint64_t>();
+    CK(bft_timed_launch(h, s, [&] { return bft_pm_bounds(h->W, d_pref, d_len, n, h->k, h->B, tk, h->n_kmers, p, s); }));
+    CK(bft_timed_launch(h, s, [&] { return bft_scan::exclusive_sum_ptr<uint64_t>(p.cand, p.coff, n, s, h->pm_tmp, nullptr, true); }));
+    CK(bft_timed_launch(h, s, [&] { return bft_pm_count(h->W, n, tk, p, s); }));
+    CK(bft_timed_launch(h, s, [&] { return bft_scan::exclusive_sum_ptr<uint64_t>(p.kept, d_offsets, n, s, h->pm_tmp, (unsigned long long*)d_needed, true); }));
+    CK(bft_timed_launch(h, s, [&] { return bft_scan::exclusive_sum_ptr<uint64_t>(p.chunk, p.chunk_off, BFT_PM_CHUNKS, s, h->pm_tmp, nullptr, true); }));
+    return 0;
+}
+static int pm_emit(bft_gpu* h, uint64_t n, const BftPmScratch& p, uint64_t cap, uint8_t* d_kmers, uint32_t* d_rows, uint32_t* d_cs, hipStream_t s) {
+    if (cap == 0 || (!d_kmers && !d_rows && !d_cs)) return 0;
+    return bft_timed_launch(h, s, [&] { return bft_pm_emit(h->W, n, h->k, h->B, h->d_tk.as<uint64_t>(), h->d_tcol.as<uint32_t>(), p, cap, d_kmers, d_rows, d_cs, s); });
+}
+
+extern "C" int bft_gpu_query_prefixes_dev(bft_gpu* h, const void* d_prefixes, const void* d_lengths, uint64_t n, void* d_offsets, void* d_kmers_out,
+                                          void* d_rows_out, void* d_colorsets_out, uint64_t cap, void* d_needed, void* hip_stream) {
+    if (!h || !d_offsets || ((!d_prefixes || !d_lengths) && n)) return bft_fail(BFT_GPU_E_ARG, "NULL argument");
+    ENTER(h);
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
+    const bool capturing = bft_stream_capturing(s);
+    CK(bft_ensure_built(h, false));
+    if (h->table_dropped) {  // ("compact_table": the rows come from the sorted table; bringing it back synchronises)
+        if (capturing) return bft_fail(BFT_GPU_E_ARG, "prefix query recorded into a graph: the sorted table is not resident (compact_table); make one direct call first");
+        CK(bft_ensure_table(h));
+    }
+    if (n == 0) {
+        CK(bft_zero_async(d_offsets, 8, s));  // (kernels, not memsets, wherever a caller may be capturing: bft_dev.h)
+        if (d_needed) CK(bft_zero_async(d_needed, 8, s));
+        return bft_note_foreign_stream(h, s);
+    }
+    BftPmScratch p;
+    CK(pm_scratch(h, n, s, capturing, &p));
+    CK(pm_count(h, (const uint8_t*)d_prefixes, (const uint8_t*)d_lengths, n, (uint64_t*)d_offsets, (uint64_t*)d_needed, s, p));
+    CK(pm_emit(h, n, p, cap, (uint8_t*)d_kmers_out, (uint32_t*)d_rows_out, (uint32_t*)d_colorsets_out, s));
+    h->pm.release();
+    return bft_note_foreign_stream(h, s);
+}
+
+// The host-buffer form: lengths are checked first, the matches counted on the device, and the outputs filled only when cap holds them all.
+extern "C" int bft_gpu_query_prefixes(bft_gpu* h, const uint8_t* prefixes, const uint8_t* lengths, uint64_t n, uint64_t* offsets, uint8_t* kmers_out,
+                                      uint32_t* rows_out, uint32_t* colorsets_out, uint64_t cap, uint64_t* needed) {
+    if (!h || !offsets || ((!prefixes || !lengths) && n)) return bft_fail(BFT_GPU_E_ARG, "NULL argument");
+    for (uint64_t i = 0; i < n; i++)
+        if (lengths[i] < 1 || lengths[i] > h->k) return bft_fail(BFT_GPU_E_ARG, "prefix length outside [1, k]");
+    ENTER(h);
+    CK(bft_ensure_built(h));
+    if (n == 0) {
+        offsets[0] = 0;
+        if (needed) *needed = 0;
+        return BFT_GPU_OK;
+    }
+    const hipStream_t s = h->stream;
+    DevBuf dp, dl, doff, dneed;
+    CK(dp.alloc(n * h->B));
+    CK(dl.alloc(n));
+    CK(doff.alloc((n + 1) * 8));
+    CK(dneed.alloc(8));
+    HIPCK(hipMemcpyAsync(dp.p, prefixes, n * h->B, hipMemcpyHostToDevice, s));
+    HIPCK(hipMemcpyAsync(dl.p, lengths, n, hipMemcpyHostToDevice, s));
+    BftPmScratch p;
+    CK(pm_scratch(h, n, s, false, &p));
+    CK(pm_count(h, dp.as<uint8_t>(), dl.as<uint8_t>(), n, doff.as<uint64_t>(), dneed.as<uint64_t>(), s, p));
+    uint64_t total = 0;
+    HIPCK(hipMemcpyAsync(&total, dneed.p, 8, hipMemcpyDeviceToHost, s));
+    HIPCK(hipStreamSynchronize(s));
+    if (needed) *needed = total;
+    const bool want = kmers_out || rows_out || colorsets_out;
+    if (want && total > cap) {
+        h->pm.release();
+        return bft_fail(BFT_GPU_E_NOSPACE, "prefix match buffers too small");
+    }
+    if (want && total) {
+        DevBuf dk, dr, dc;
+        if (kmers_out) CK(dk.alloc(total * h->B));
+        if (rows_out) CK(dr.alloc(total * 4));
+        if (colorsets_out) CK(dc.alloc(total * 4));
+        CK(pm_emit(h, n, p, total, dk.as<uint8_t>(), dr.as<uint32_t>(), dc.as<uint32_t>(), s));
+        if (kmers_out) HIPCK(hipMemcpyAsync(kmers_out, dk.p, total * h->B, hipMemcpyDeviceToHost, s));
+        if (rows_out) HIPCK(hipMemcpyAsync(rows_out, dr.p, total * 4, hipMemcpyDeviceToHost, s));
+        if (colorsets_out) HIPCK(hipMemcpyAsync(colorsets_out, dc.p, total * 4, hipMemcpyDeviceToHost, s));
+    }
+    HIPCK(hipMemcpyAsync(offsets, doff.p, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIPCK(hipStreamSynchronize(s));
+    h->pm.release();
+    return BFT_GPU_OK;
 }

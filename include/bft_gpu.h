@@ -191,7 +191,9 @@ int bft_gpu_footprint(bft_gpu* h, uint64_t* out, int n_out);
  *   start is a kernel argument, which a replay cannot move (tests/test_gpu_parity.py::test_captured_queries_replay).  The id-list, colour-row and
  *   sequence calls may be recorded too, after one direct call of the same size (which sizes the handle's scratch: nothing may allocate while a stream
  *   is captured); what they zero they zero with kernels of the library's own -- a captured hipMemsetAsync replays correctly only once on ROCm 7.0.2
- *   (test_captured_colour_queries_replay, test_captured_sequence_queries_replay; tools/probe_graph_memset.py).
+ *   (test_captured_colour_queries_replay, test_captured_sequence_queries_replay; tools/probe_graph_memset.py).  A recorded call that would have to
+ *   grow that scratch, or to wait for its use on another stream, returns BFT_GPU_E_ARG and records nothing; replays of a recorded call are not
+ *   ordered against calls on other streams (the handle's scratch is one per query family: the caller keeps them apart).
  * The container walk (k_query*): "query_wgs_per_cu" (how it sits on a CU: 1 = one 1024-thread workgroup, 4 wavefronts per SIMD; 2 = two of them, 8 per
  *   SIMD with 64 VGPRs each; 3 = two 768-thread workgroups, 6 per SIMD with 84 VGPRs each; 0, default = by rule: 3), "query_probe" (rows per probe of the
  *   suffix-group search: 4 = adjacent 32-byte blocks, 8 = 64-byte blocks with a re-interpolated guess, 0 = by rule from the mean group size),

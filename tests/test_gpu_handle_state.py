@@ -587,3 +587,178 @@ def test_kernel_time_counts_every_query_entry_point(form):
         ms, launches = t.kernel_time(reset=True)
         assert launches >= at_least and ms > 0, (form, name, launches, ms)
     t.close()
+
+
+# ---- 2e: the scratch owner's policy (HandleScratch, bft_handle.h) ------------------------------------------------------------------------
+def _hip_runtime():
+    """the HIP runtime this process already has loaded (torch's): raw streams, which can be destroyed"""
+    for line in open("/proc/self/maps"):
+        if "libamdhip64" in line:
+            return C.CDLL(line.split()[-1])
+    raise RuntimeError("no libamdhip64 mapped")
+
+
+def test_sequence_queries_after_their_last_stream_is_destroyed():
+    """Sequence queries on a stream made with hipStreamCreate, used once, synchronised and DESTROYED; then on another stream and on the handle's own.
+    The scratch's last user is gone by the second call: the handle waits on an event of its own, never on that stream.  Every call returns
+    BFT_GPU_OK (the wrapper raises otherwise) and every answer equals ground truth."""
+    import torch
+    hip = _hip_runtime()
+    k, ngen, n, thr = 27, 130, 3000, 0.5
+    t, gt, anc = _index(k, ngen)
+    genomes = [S.mutate(anc, 0.002, 1000 + k + 10 + g) if g else anc for g in range(4)]
+    rb = (gt.genomes + 7) // 8
+
+    def ask(stream, seed):
+        rng = np.random.default_rng(seed)
+        reads = [genomes[s][a:a + m] for s, a, m in zip(rng.integers(0, 4, n), rng.integers(0, GENOME_LEN - 200, n), rng.integers(k, k + 40, n))]
+        enc = [bytes(S._ASCII[r]) for r in reads]
+        off = np.zeros(n + 1, np.int64)
+        off[1:] = np.cumsum([len(e) for e in enc])
+        d_blob = torch.from_numpy(np.frombuffer(b"".join(enc), dtype=np.uint8).copy()).cuda()
+        d_off = torch.from_numpy(off).cuda()
+        d_rows = torch.full((n, rb), 0xAB, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        t.query_sequences_dev(d_blob.data_ptr(), d_off.data_ptr(), n, int(off[-1]), thr, d_rows.data_ptr(), False, stream)
+        return reads, d_rows
+
+    def check(reads, d_rows, what):
+        unp = np.unpackbits(d_rows.cpu().numpy(), axis=1, bitorder="little")
+        assert not unp[:, gt.genomes:].any(), what
+        assert [np.flatnonzero(r).tolist() for r in unp[:, :gt.genomes]] == gt.sequences(reads, thr), what
+
+    st = C.c_void_p()
+    assert hip.hipStreamCreate(C.byref(st)) == 0
+    reads, d_rows = ask(st.value, 1)
+    assert hip.hipStreamSynchronize(st) == 0
+    assert hip.hipStreamDestroy(st) == 0
+    check(reads, d_rows, "on the stream that was destroyed afterwards")
+    s2 = torch.cuda.Stream()
+    with torch.cuda.stream(s2):
+        reads, d_rows = ask(s2.cuda_stream, 2)
+    s2.synchronize()
+    check(reads, d_rows, "on a second stream")
+    reads, d_rows = ask(None, 3)
+    _sync()
+    check(reads, d_rows, "on the handle's stream")
+    t.close()
+
+
+def _replay_between_streams(call, read, want):
+    """call(stream) direct on stream A, captured on A, replayed twice, eager on stream B, replayed again: read() after each of the four equals
+    want (checked for the direct call too).  A recorded call leaves no event of the handle's inside the graph, so the eager call on B neither
+    fails nor waits on one."""
+    import torch
+    sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
+    with torch.cuda.stream(sa):
+        call(sa.cuda_stream)
+    sa.synchronize()
+    want(read(), "direct")
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=sa):
+        call(torch.cuda.current_stream().cuda_stream)
+    for what in ("replay 1", "replay 2", "eager on another stream", "replay 3"):
+        read(clear=True)
+        torch.cuda.synchronize()
+        if what.startswith("replay"):
+            g.replay()
+        else:
+            with torch.cuda.stream(sb):
+                call(sb.cuda_stream)
+        torch.cuda.synchronize()
+        want(read(), what)
+    del g
+
+
+def test_recorded_id_lists_and_prefixes_between_eager_calls_on_another_stream():
+    """An id-list call recorded on stream A after one direct call of that size, replayed twice, the same call eager on stream B, a replay again;
+    the same for the prefix call.  All against ground truth (id lists) / brute force over extract() (prefixes)."""
+    import torch
+    k, ngen, n = 27, 130, 20000
+    t, gt, _ = _index(k, ngen)
+    q = _queries(gt, n, 61)
+    eb, eoff, eids = gt.colors(q)
+    cap = len(eids) + 16
+    dq = torch.from_numpy(q).cuda()
+    bits = torch.zeros((n + 63) // 64 * 8, dtype=torch.uint8, device="cuda")
+    offs = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+    ids = torch.zeros(cap, dtype=torch.int32, device="cuda")
+    need = torch.zeros(1, dtype=torch.int64, device="cuda")
+
+    def read(clear=False):
+        if clear:
+            bits.zero_(); offs.zero_(); ids.zero_(); need.zero_()
+            return None
+        return bits.cpu().numpy(), offs.cpu().numpy().view(np.uint64), ids.cpu().numpy().view(np.uint32), int(need.item())
+
+    def want(got, what):
+        b, off, idl, nd = got
+        assert (b[: len(eb)] == eb).all() and (off == eoff).all(), what
+        assert nd == len(eids) and (idl[: len(eids)] == eids).all(), what
+
+    _replay_between_streams(lambda s: t.query_colors_dev(dq.data_ptr(), n, bits.data_ptr(), offs.data_ptr(), ids.data_ptr(), cap, need.data_ptr(), s), read, want)
+
+    ex = _Extract(t, gt)
+    plen = np.random.default_rng(62).integers(10, 28, n).astype(np.uint8)
+    poff, prow = ex.prefixes(S.unpack_codes(q, k), plen)
+    m = int(poff[-1])
+    d_l = torch.from_numpy(plen).cuda()
+    d_k = torch.zeros((m + 1, q.shape[1]), dtype=torch.uint8, device="cuda")
+    d_r = torch.zeros(m + 1, dtype=torch.int32, device="cuda")
+    d_c = torch.zeros(m + 1, dtype=torch.int32, device="cuda")
+
+    def pread(clear=False):
+        if clear:
+            offs.zero_(); d_k.zero_(); d_r.zero_(); d_c.zero_(); need.zero_()
+            return None
+        return offs.cpu().numpy().view(np.uint64), d_k.cpu().numpy()[:m], d_r.cpu().numpy().view(np.uint32)[:m], d_c.cpu().numpy().view(np.uint32)[:m], int(need.item())
+
+    def pwant(got, what):
+        off, km, rows, sets, nd = got
+        assert nd == m and (off == poff).all() and (rows.astype(np.int64) == prow).all(), what
+        assert (km == ex.kmers[prow]).all() and (sets == ex.cs[prow]).all(), what
+
+    _replay_between_streams(lambda s: t.query_prefixes_dev(dq.data_ptr(), d_l.data_ptr(), n, offs.data_ptr(), d_k.data_ptr(), d_r.data_ptr(), d_c.data_ptr(),
+                                                           m + 1, need.data_ptr(), s), pread, pwant)
+    t.close()
+
+
+def test_recorded_id_list_call_that_would_grow_the_scratch_is_refused():
+    """An id-list call LARGER than any direct call before it, made while its stream is being captured, returns BFT_GPU_E_ARG (nothing may allocate in
+    a capture) and records nothing; the test ends the capture itself and replays nothing from it.  A direct call of that size is then answered
+    correctly."""
+    import torch
+    k, ngen, n_small, n_big = 27, 130, 5000, 60000
+    t, gt, _ = _index(k, ngen)
+    q = _queries(gt, n_big, 63)
+    eb, eoff, eids = gt.colors(q)
+    cap = len(eids) + 16
+    dq = torch.from_numpy(q).cuda()
+    bits = torch.zeros((n_big + 63) // 64 * 8, dtype=torch.uint8, device="cuda")
+    offs = torch.zeros(n_big + 1, dtype=torch.int64, device="cuda")
+    ids = torch.zeros(cap, dtype=torch.int32, device="cuda")
+    need = torch.zeros(1, dtype=torch.int64, device="cuda")
+    s = torch.cuda.Stream()
+
+    def raw(n, stream):
+        return t._lib.bft_gpu_query_colors_dev(t._h, C.c_void_p(dq.data_ptr()), n, C.c_void_p(bits.data_ptr()), C.c_void_p(offs.data_ptr()),
+                                               C.c_void_p(ids.data_ptr()), cap, C.c_void_p(need.data_ptr()), C.c_void_p(stream))
+
+    with torch.cuda.stream(s):
+        assert raw(n_small, s.cuda_stream) == 0
+    s.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=s):
+        need.zero_()  # (the recorded graph is not empty)
+        rc = raw(n_big, torch.cuda.current_stream().cuda_stream)
+        msg = t._lib.bft_gpu_last_error()
+    del g  # (never replayed)
+    assert rc == -1, rc  # BFT_GPU_E_ARG
+    assert b"make one direct call of this size first" in msg, msg
+    torch.cuda.synchronize()
+    with torch.cuda.stream(s):
+        assert raw(n_big, s.cuda_stream) == 0
+    s.synchronize()
+    assert (bits.cpu().numpy()[: len(eb)] == eb).all() and (offs.cpu().numpy().view(np.uint64) == eoff).all()
+    assert int(need.item()) == len(eids) and (ids.cpu().numpy().view(np.uint32)[: len(eids)] == eids).all()
+    t.close()
