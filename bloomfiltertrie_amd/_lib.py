@@ -60,6 +60,10 @@ SIGNATURES = {
     "bft_gpu_simple_paths_dev": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_uint64, C.c_uint64, _P, _P]),
     "bft_gpu_components": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64, _P, C.c_uint64, _P]),
     "bft_gpu_components_dev": (C.c_int, [_P, _P, C.c_uint32, _P, _P, C.c_uint64, _P, _P]),
+    "bft_gpu_kmers_by_count": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "bft_gpu_kmers_by_count_dev": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_uint64, _P, _P]),
+    "bft_gpu_pangenome_stats": (C.c_int, [_P, _P, _P, _P, C.c_uint32]),
+    "bft_gpu_pangenome_stats_dev": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P]),
     "bft_gpu_image_size": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "bft_gpu_image_pack": (C.c_int, [_P, _P, C.c_uint64, _P]),
     "bft_gpu_image_unpack": (C.c_int, [_P, C.c_uint64, C.c_int, C.POINTER(_P)]),

@@ -45,6 +45,7 @@ class BFT:
         self.k = k
         self.nb = kmer_bytes(k)
         self.device = device
+        self._named = 0  # genomes named through add_genome (the image's count covers those of a loaded or unpacked handle)
         _LIVE.add(self)
 
     @classmethod
@@ -111,6 +112,7 @@ class BFT:
         """add_genomes_BFT_Root (include/CC.h:307-338)."""
         gid = C.c_uint32()
         _lib.check(self._lib.bft_gpu_add_genome(self._h, name.encode(), C.byref(gid)))
+        self._named = max(self._named, gid.value + 1)
         return gid.value
 
     def insert_kmers(self, kmers, id_genome):
@@ -409,6 +411,49 @@ class BFT:
         ids = np.ascontiguousarray(genome_ids, dtype=np.uint32)
         _lib.check(self._lib.bft_gpu_components_dev(self._h, ids.ctypes.data if len(ids) else None, len(ids), C.c_void_p(d_labels_ptr or 0),
                                                     C.c_void_p(d_sizes_ptr or 0), sizes_cap, C.c_void_p(d_counts_ptr), C.c_void_p(stream or 0)))
+
+    def kmers_by_count(self, min_count, max_count, ascii=False):
+        """extract_core_kmers / extract_dispensable_kmers / extract_singleton_kmers (reference snippets.h, src/snippets.c:10-106) on the GPU: the
+        stored k-mers carried by min_count .. max_count genomes, in ascending row order (the order of extract()).  Core: both = the number of
+        genomes; dispensable: 0 .. genomes - 1; singleton: 1 .. 1.  Returns (kmers, rows): kmers packed uint8 [n, nb], or with ascii=True a list
+        of strings; rows uint32 [n]."""
+        lo, hi = int(min_count), int(max_count)
+        n = C.c_uint64()
+        _lib.check(self._lib.bft_gpu_kmers_by_count(self._h, lo, hi, None, None, None, 0, C.byref(n)))
+        m = int(n.value)
+        rows = np.zeros(m, dtype=np.uint32)
+        if ascii:
+            out = np.zeros((m, self.k + 1), dtype=np.uint8)
+            _lib.check(self._lib.bft_gpu_kmers_by_count(self._h, lo, hi, None, out.ctypes.data, rows.ctypes.data, m, C.byref(n)))
+            if m and out[:, self.k].any():
+                raise _lib.BFTError("bft_gpu_kmers_by_count: an ASCII k-mer is not NUL-terminated")
+            return [r.tobytes().decode() for r in out[:, :self.k]], rows
+        out = np.zeros((m, self.nb), dtype=np.uint8)
+        _lib.check(self._lib.bft_gpu_kmers_by_count(self._h, lo, hi, out.ctypes.data, None, rows.ctypes.data, m, C.byref(n)))
+        return out, rows
+
+    def kmers_by_count_dev(self, min_count, max_count, d_kmers_ptr, d_ascii_ptr, d_rows_ptr, cap, d_count_ptr, stream=None):
+        """Device-resident k-mer classes (bft_gpu_kmers_by_count_dev): the number of selected k-mers (uint64) at d_count_ptr always, the first `cap`
+        of them into the buffers that are not 0 (packed nb bytes each; ASCII k + 1 bytes each, NUL included; rows uint32); no synchronisation."""
+        _lib.check(self._lib.bft_gpu_kmers_by_count_dev(self._h, int(min_count), int(max_count), C.c_void_p(d_kmers_ptr or 0), C.c_void_p(d_ascii_ptr or 0),
+                                                        C.c_void_p(d_rows_ptr or 0), cap, C.c_void_p(d_count_ptr), C.c_void_p(stream or 0)))
+
+    def pangenome_stats(self):
+        """(spectrum, genome_total, genome_private), uint64 (bft_gpu_pangenome_stats): spectrum[c] = stored k-mers carried by exactly c genomes
+        (c = 0 .. genomes), genome_total[g] = k-mers whose colour set holds g, genome_private[g] = k-mers whose colour set is {g}."""
+        self.build()  # the genome count is known once the image exists; a genome named since (add_genome without k-mers) counts too
+        g = max(int(self.info()["genomes"]), self._named)
+        spectrum = np.zeros(g + 1, dtype=np.uint64)
+        total = np.zeros(g, dtype=np.uint64)
+        private = np.zeros(g, dtype=np.uint64)
+        _lib.check(self._lib.bft_gpu_pangenome_stats(self._h, spectrum.ctypes.data, total.ctypes.data if g else None, private.ctypes.data if g else None, g + 1))
+        return spectrum, total, private
+
+    def pangenome_stats_dev(self, d_spectrum_ptr, d_genome_total_ptr, d_genome_private_ptr, cap, stream=None):
+        """Device-resident statistics (bft_gpu_pangenome_stats_dev): uint64 counters, genomes + 1 / genomes / genomes entries, into the buffers
+        that are not 0; cap = entries of room in the spectrum; no synchronisation."""
+        _lib.check(self._lib.bft_gpu_pangenome_stats_dev(self._h, C.c_void_p(d_spectrum_ptr or 0), C.c_void_p(d_genome_total_ptr or 0),
+                                                         C.c_void_p(d_genome_private_ptr or 0), cap, C.c_void_p(stream or 0)))
 
     def genome_name(self, id_genome):
         """The name of genome id_genome (the reference's filenames[id_genome]; "genome_<id>" for an id that was never named)."""

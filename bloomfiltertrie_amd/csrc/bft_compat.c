@@ -817,3 +817,59 @@ void get_nb_connected_component(BFT* graph, ...) {
     va_end(args);
     *nb += (int)counts[0];
 }
+
+/* ---------------------------------------------------------------- pan-genome k-mer classes (<bft/snippets.h>) */
+
+/* src/snippets.c:10-75: the callback's arguments are a FILE* and an int*; a k-mer whose genome count is in the class is written with its NUL
+ * (strlen + 1 bytes) and counted.  The annotation is fetched as the reference fetches it, and freed (the reference leaks it). */
+static size_t class_callback(BFT_kmer* kmer, BFT* graph, va_list args, int which, const char* where) {
+    NOT_NULL(kmer, where);
+    NOT_NULL(graph, where);
+    FILE* file = va_arg(args, FILE*);
+    int* nb_kmers = va_arg(args, int*);
+    BFT_annotation* annot = get_annotation(kmer);
+    const uint32_t count = get_count_id_genomes(annot, graph);
+    free_BFT_annotation(annot);
+    const uint32_t nb_genomes = (uint32_t)graph->nb_genomes;
+    if (which == 0 ? count == nb_genomes : which == 1 ? count < nb_genomes : count == 1) {
+        fwrite(kmer->kmer, sizeof(char), strlen(kmer->kmer) + 1, file);
+        *nb_kmers += 1;
+    }
+    return true;
+}
+size_t extract_core_kmers(BFT_kmer* kmer, BFT* graph, va_list args) { return class_callback(kmer, graph, args, 0, "extract_core_kmers()"); }
+size_t extract_dispensable_kmers(BFT_kmer* kmer, BFT* graph, va_list args) { return class_callback(kmer, graph, args, 1, "extract_dispensable_kmers()"); }
+size_t extract_singleton_kmers(BFT_kmer* kmer, BFT* graph, va_list args) { return class_callback(kmer, graph, args, 2, "extract_singleton_kmers()"); }
+
+/* src/snippets.c:86-106.  The three callbacks above are told apart by their addresses (as get_nb_connected_component tells BFS from DFS) and become a
+ * range of genome counts: one bft_gpu_kmers_by_count call counts the class, a second one fetches it as ASCII with the NULs, and the file is one
+ * fwrite.  Any other f is handed every k-mer through iterate_over_kmers, as in the reference.  Both routes visit the k-mers in row order. */
+void extract_pangenome_kmers_to_disk(BFT* graph, char* filename_output, BFT_func_ptr f) {
+    NOT_NULL(graph, "extract_pangenome_kmers_to_disk()");
+    NOT_NULL(filename_output, "extract_pangenome_kmers_to_disk()");
+    FILE* file = fopen(filename_output, "w");
+    if (file == NULL) DIE("extract_pangenome_kmers_to_disk(): failed to create/open output file.\n");
+    int nb_kmers = 0;
+    if (f == extract_core_kmers || f == extract_dispensable_kmers || f == extract_singleton_kmers) {
+        const uint32_t nb_genomes = graph->nb_genomes > 0 ? (uint32_t)graph->nb_genomes : 0u;
+        uint32_t lo = 1, hi = 1;
+        if (f == extract_core_kmers) lo = hi = nb_genomes;
+        else if (f == extract_dispensable_kmers) { lo = 0; hi = nb_genomes - 1; }
+        uint64_t n = 0;
+        if (f != extract_dispensable_kmers || nb_genomes > 0) { /* (no genome: nothing is below 0, and 0 - 1 would wrap) */
+            ck(bft_gpu_kmers_by_count(graph->gpu, lo, hi, NULL, NULL, NULL, 0, &n), "extract_pangenome_kmers_to_disk()");
+            if (n) {
+                const size_t bytes = (size_t)n * ((size_t)graph->k + 1);
+                char* ascii = malloc(bytes);
+                if (ascii == NULL) DIE("extract_pangenome_kmers_to_disk(): out of memory\n");
+                ck(bft_gpu_kmers_by_count(graph->gpu, lo, hi, NULL, ascii, NULL, n, &n), "extract_pangenome_kmers_to_disk()");
+                if (fwrite(ascii, 1, bytes, file) != bytes) DIE("extract_pangenome_kmers_to_disk(): failed to write the output file.\n");
+                free(ascii);
+            }
+        }
+        nb_kmers = (int)n;
+    } else
+        iterate_over_kmers(graph, f, file, &nb_kmers);
+    if (fclose(file) != 0) DIE("extract_pangenome_kmers_to_disk(): failed to write the output file.\n");
+    printf("Number of extracted k-mers is %d.\n", nb_kmers);
+}

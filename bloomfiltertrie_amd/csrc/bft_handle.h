@@ -1,5 +1,6 @@
 // bft_handle.h -- the handle behind the C-ABI (struct bft_gpu) and the host helpers every entry point needs, for the translation units that hold
-// entry points: bft_gpu.hip (which defines the helpers) and the analysis families bft_prefix.hip, bft_paths.hip, bft_components.hip, bft_subgraph.hip.
+// entry points: bft_gpu.hip (which defines the helpers) and the analysis families bft_prefix.hip, bft_paths.hip, bft_components.hip, bft_pangenome.hip,
+// bft_subgraph.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -211,6 +212,9 @@ struct bft_gpu {
     HandleScratch cc{"components"};
     DevBuf cc_buf, cc_tmp;           // connected components (BftCcScratch, bft_components.h) and their scans' temporary
     uint64_t cc_m = 0, cc_sets = 0;  // rows and colour sets cc_buf has room for
+    HandleScratch pg{"k-mer classes"};
+    DevBuf pg_buf, pg_tmp;           // pan-genome k-mer classes (BftPgScratch, bft_pangenome.h) and their scan's temporary
+    uint64_t pg_m = 0, pg_sets = 0;  // rows and colour sets pg_buf has room for
 
     bool inject_build_failure = false;  // test hook: the next bft_gpu_build fails right before its commit point (one shot)
     bool opt_build_stages = false;      // "build_stages": the next builds record GPU time and bytes per stage (bft_gpu_build_stages)

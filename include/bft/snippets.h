@@ -1,7 +1,8 @@
 /*
- * <bft/snippets.h> -- the simple-path and connected-component snippets of GuillaumeHolley/BloomFilterTrie (reference include/snippets.h,
- * src/snippets.c), served by the MI355X library: one batched GPU pass over the whole index (bft_gpu_simple_paths, bft_gpu_components,
- * include/bft_gpu.h) instead of a walk that asks for the successors, predecessors and marks of one k-mer at a time.
+ * <bft/snippets.h> -- the simple-path, connected-component and pan-genome class snippets of GuillaumeHolley/BloomFilterTrie (reference
+ * include/snippets.h, src/snippets.c), served by the MI355X library: one batched GPU pass over the whole index (bft_gpu_simple_paths,
+ * bft_gpu_components, bft_gpu_kmers_by_count, include/bft_gpu.h) instead of a walk that asks for the successors, predecessors, marks or annotation
+ * of one k-mer at a time.
  *
  * The paths are those bft_gpu_simple_paths defines: maximal chains of k-mers with in- and out-degree <= 1 (degrees over the whole graph),
  * each spelled as its first k-mer plus the last nucleotide of every following one; a cycle is cut before its k-mer of smallest row.  They are
@@ -9,16 +10,18 @@
  * walk happens to reach them, and that order also decides where it starts a cycle (INTEGRATION.md lists every difference).
  *
  * The traversals BFS, DFS, BFS_subgraph, DFS_subgraph, the predicate is_in_subgraph and get_nb_connected_component are declared in
- * <bft/snippets_traversal.h>, which this header includes.
+ * <bft/snippets_traversal.h>; the k-mer class extractors extract_core_kmers / extract_dispensable_kmers / extract_singleton_kmers and
+ * extract_pangenome_kmers_to_disk in <bft/snippets_pangenome.h>.  This header includes both.
  *
- * Not provided: the per-k-mer callbacks extract_simple_paths and extract_core_simple_paths (they need marking), the k-mer class extractors
- * extract_core_kmers / extract_dispensable_kmers / extract_singleton_kmers / extract_pangenome_kmers_to_disk, cdbg_traversal and
- * nb_connected_components as a callback (they need marking too).
+ * Not provided: the per-k-mer callbacks extract_simple_paths and extract_core_simple_paths (they need marking), cdbg_traversal and
+ * nb_connected_components as a callback (they need marking too), and the annotation set operations intersection_annotations /
+ * union_annotations / sym_difference_annotations.
  */
 #ifndef BFT_GPU_COMPAT_SNIPPETS_H
 #define BFT_GPU_COMPAT_SNIPPETS_H
 
 #include "bft.h"
+#include "snippets_pangenome.h"
 #include "snippets_traversal.h"
 
 #ifdef __cplusplus

@@ -3,7 +3,8 @@
  * included by <bft/snippets.h>.  The number of connected components is one GPU pass over the whole index (bft_gpu_components, include/bft_gpu.h)
  * instead of a BFS or DFS that marks one k-mer at a time.  The count is the reference's: components do not depend on the order of a walk.
  *
- * Not provided: cdbg_traversal, and nb_connected_components as a callback of iterate_over_kmers (they need marking).
+ * Not provided: cdbg_traversal, and nb_connected_components as a callback of iterate_over_kmers (they need marking).  The k-mer class extractors
+ * (extract_core_kmers and its kin), which need none, are in <bft/snippets_pangenome.h>.
  */
 #ifndef BFT_GPU_COMPAT_SNIPPETS_TRAVERSAL_H
 #define BFT_GPU_COMPAT_SNIPPETS_TRAVERSAL_H

@@ -347,6 +347,36 @@ int bft_gpu_components(bft_gpu* h, const uint32_t* genome_ids, uint32_t nb_ids, 
 int bft_gpu_components_dev(bft_gpu* h, const uint32_t* genome_ids, uint32_t nb_ids, void* d_labels, void* d_sizes, uint64_t sizes_cap, void* d_counts,
                            void* hip_stream);
 
+/* The pan-genome k-mer classes: extract_core_kmers / extract_dispensable_kmers / extract_singleton_kmers through extract_pangenome_kmers_to_disk
+ * (reference snippets.h, src/snippets.c:10-106) without one annotation fetch per k-mer.  The genome count of a stored k-mer is the size of its colour
+ * set; bft_gpu_kmers_by_count selects the k-mers carried by min_count .. max_count genomes (core: both = the number of genomes; dispensable: 0 ..
+ * genomes - 1; singleton: 1 .. 1) and writes them in ascending row order (the bft_gpu_extract order, hence that of iterate_over_kmers here; the
+ * reference visits its containers in their own order: same set).  Outputs, each may be NULL: kmers_out, packed in the reference's layout (B =
+ * CEIL(2k/8) bytes each, as bft_gpu_extract); ascii_out, k + 1 bytes each: the k nucleotides and the terminating NUL (what the reference's callbacks
+ * fwrite, src/snippets.c:21); rows_out, the row of each in the stored k-mer table.  cap: entries of room in every output given.
+ * Host form: with every output NULL the call only counts; when cap < *n_out nothing is written and BFT_GPU_E_NOSPACE is returned, *n_out set.
+ * min_count > max_count, or a range no k-mer falls in, selects nothing (BFT_GPU_OK); max_count may exceed the number of genomes.  The number of
+ * genomes counts every genome added, one that received no k-mer included (then no k-mer is core), as graph->nb_genomes does in the reference.
+ * Pending insertions are built first; the handle's answers do not change ("compact_table": the sorted table comes back, as for rows, prefixes and
+ * simple paths).  Launches are counted in bft_gpu_kernel_time; with "build_stages" on, the call's steps become the stages bft_gpu_build_stages reports.
+ * At most 2^31 - 1 k-mers (BFT_GPU_E_LIMIT). */
+int bft_gpu_kmers_by_count(bft_gpu* h, uint32_t min_count, uint32_t max_count, uint8_t* kmers_out, char* ascii_out, uint32_t* rows_out, uint64_t cap,
+                           uint64_t* n_out);
+/* The same into device buffers on hip_stream (NULL = the handle's stream), without host synchronisation: d_count (uint64, required) always receives the
+ * number of selected k-mers; the outputs (any may be NULL) receive the first cap of them and nothing beyond -- pass NULL outputs and cap 0 first to
+ * learn the size.  Scratch (~4 bytes per stored k-mer) belongs to the handle and is shared with no other query family.  Not inside a graph capture
+ * (BFT_GPU_E_ARG). */
+int bft_gpu_kmers_by_count_dev(bft_gpu* h, uint32_t min_count, uint32_t max_count, void* d_kmers_out, void* d_ascii_out, void* d_rows_out, uint64_t cap,
+                               void* d_count, void* hip_stream);
+/* The whole index in one call: spectrum[c], c = 0 .. nb_genomes, the stored k-mers carried by exactly c genomes (spectrum[0] is 0 on every index this
+ * library builds: the entry is kept so that the index is the count; the entries sum to the number of stored k-mers); genome_total[g] the k-mers whose
+ * colour set holds genome g; genome_private[g] those whose colour set is {g} alone (they sum to spectrum[1]).  spectrum has nb_genomes + 1 entries, the
+ * other two nb_genomes; any may be NULL.  cap = entries of room in spectrum (the other two need cap - 1): cap < nb_genomes + 1 with an output given is
+ * BFT_GPU_E_NOSPACE.  An empty index gives zeros.  Work is one pass over the colour set of every row plus one over the dictionary. */
+int bft_gpu_pangenome_stats(bft_gpu* h, uint64_t* spectrum, uint64_t* genome_total, uint64_t* genome_private, uint32_t cap);
+/* The same into device buffers (uint64) on hip_stream (NULL = the handle's stream), without host synchronisation.  Not inside a graph capture. */
+int bft_gpu_pangenome_stats_dev(bft_gpu* h, void* d_spectrum, void* d_genome_total, void* d_genome_private, uint32_t cap, void* hip_stream);
+
 /* A colour set as the reference's annotation bytes -- BFT_annotation::annot as get_annotation returns it
  * (include/bft.h:97, src/bft.c:363-387): mode 0 (bitmap, genome g <-> bit g+2), 1 (ranges) or 2 (id list), chosen the way the
  * reference chooses it: compute_best_mode re-decides at every insertion of a genome id and keeps the current mode on a size tie
