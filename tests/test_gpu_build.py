@@ -236,7 +236,10 @@ def test_composite_sort_builds_the_same_image(k, ngen):
     from bloomfiltertrie_amd import BFT
     base = S.distinct(S.kmers_of(S.random_genome(30000, 5 + k), k))
     rng = np.random.default_rng(k + ngen)
-    parts = [np.ascontiguousarray(base[rng.random(len(base)) < 0.3]) for _ in range(ngen)]
+    masks = [rng.random(len(base)) < 0.3 for _ in range(ngen)]
+    parts = [np.ascontiguousarray(base[m]) for m in masks]
+    member = np.array(masks)  # ground truth from what `parts` hold: the ids of the genomes whose part holds the k-mer (the rows of base are distinct)
+    truth = {base[i].tobytes(): tuple(np.flatnonzero(member[:, i]).tolist()) for i in np.flatnonzero(member.any(axis=0)).tolist()}
     imgs = []
     for comp, msd, clog in ((1, 2, 1), (0, 0, 1), (1, 0, 1), (1, 2, 0)):
         t = BFT(k)
@@ -254,6 +257,11 @@ def test_composite_sort_builds_the_same_image(k, ngen):
         t.build()
         ek, ecs = t.extract()
         imgs.append(({name: t.debug_array(name) for name in ARRAYS}, ek, ecs, [t.colorset(c) for c in sorted(set(ecs.tolist()))[:200]]))
+        if not imgs[1:]:  # the merged lists (about ngen * 0.15 ids on each side) against the truth; the other variants against this one, below
+            got, n_sets = _colour_map(t)
+            assert got == truth
+            assert n_sets == len(set(truth.values())) == t.info()["colorsets"]
+            assert t.info()["pairs"] == sum(len(p) for p in parts) and t.info()["kmers"] == len(truth)
         t.close()
     a = imgs[0]
     for b in imgs[1:]:
