@@ -64,6 +64,24 @@ SIGNATURES = {
     "bft_gpu_kmers_by_count_dev": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_uint64, _P, _P]),
     "bft_gpu_pangenome_stats": (C.c_int, [_P, _P, _P, _P, C.c_uint32]),
     "bft_gpu_pangenome_stats_dev": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P]),
+    "bft_gpu_marks_begin": (C.c_int, [_P]),
+    "bft_gpu_marks_end": (C.c_int, [_P]),
+    "bft_gpu_marks_set": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint8, C.POINTER(C.c_uint64)]),
+    "bft_gpu_marks_set_dev": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint8, _P, _P]),
+    "bft_gpu_marks_get": (C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(C.c_uint64)]),
+    "bft_gpu_marks_get_dev": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P]),
+    "bft_gpu_marks_test_and_set": (C.c_int, [_P, _P, C.c_uint64, C.c_uint8, C.c_uint8, _P, C.POINTER(C.c_uint64)]),
+    "bft_gpu_marks_test_and_set_dev": (C.c_int, [_P, _P, C.c_uint64, C.c_uint8, C.c_uint8, _P, _P, _P]),
+    "bft_gpu_marks_fill": (C.c_int, [_P, C.c_uint8]),
+    "bft_gpu_marks_fill_dev": (C.c_int, [_P, C.c_uint8, _P]),
+    "bft_gpu_marks_counts": (C.c_int, [_P, _P]),
+    "bft_gpu_marks_counts_dev": (C.c_int, [_P, _P, _P]),
+    "bft_gpu_marks_select": (C.c_int, [_P, C.c_uint32, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "bft_gpu_marks_select_dev": (C.c_int, [_P, C.c_uint32, _P, _P, _P, C.c_uint64, _P, _P]),
+    "bft_gpu_marks_reach": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, C.c_uint8, C.c_uint8, C.c_int, _P, _P]),
+    "bft_gpu_marks_reach_dev": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, C.c_uint8, C.c_uint8, C.c_int, _P, _P, _P]),
+    "bft_gpu_marks_read": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "bft_gpu_marks_write": (C.c_int, [_P, _P, C.c_uint64]),
     "bft_gpu_image_size": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "bft_gpu_image_pack": (C.c_int, [_P, _P, C.c_uint64, _P]),
     "bft_gpu_image_unpack": (C.c_int, [_P, C.c_uint64, C.c_int, C.POINTER(_P)]),

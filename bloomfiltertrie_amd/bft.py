@@ -455,6 +455,131 @@ class BFT:
         _lib.check(self._lib.bft_gpu_pangenome_stats_dev(self._h, C.c_void_p(d_spectrum_ptr or 0), C.c_void_p(d_genome_total_ptr or 0),
                                                          C.c_void_p(d_genome_private_ptr or 0), cap, C.c_void_p(stream or 0)))
 
+    # -- vertex marking (bft_gpu_marks_*: set_marking / set_flag_kmer / get_flag_kmer and the traversals' marks) -------
+    def set_marking(self):
+        """set_marking (include/bft.h:143): the graph is locked (no insertion, no build) and every stored k-mer gets a flag, 0 at first; on a graph
+        that is already marking nothing changes."""
+        _lib.check(self._lib.bft_gpu_marks_begin(self._h))
+
+    def unset_marking(self):
+        """unset_marking (include/bft.h:144): the flags are released and the graph unlocked."""
+        _lib.check(self._lib.bft_gpu_marks_end(self._h))
+
+    @staticmethod
+    def _flag_args(flag_or_array, n):
+        """(flags array or None, single flag) of a set_flags call"""
+        if np.ndim(flag_or_array) == 0:
+            f = int(flag_or_array)
+            if not 0 <= f <= 255:
+                raise ValueError("a flag is 0, 1, 2 or 3")
+            return None, f
+        flags = np.ascontiguousarray(flag_or_array, dtype=np.uint8)
+        if flags.shape != (n,):
+            raise ValueError(f"expected one flag per k-mer ({n}), got {flags.shape}")
+        return flags, 0
+
+    def set_flags(self, kmers, flag_or_array):
+        """set_flag_kmer for a batch: one flag (0..3) for every k-mer, or an array with one flag per k-mer.  Returns the number of absent k-mers
+        (they are ignored)."""
+        kmers = self._chk(kmers)
+        flags, flag = self._flag_args(flag_or_array, len(kmers))
+        absent = C.c_uint64()
+        _lib.check(self._lib.bft_gpu_marks_set(self._h, kmers.ctypes.data, len(kmers), flags.ctypes.data if flags is not None else None, flag, C.byref(absent)))
+        return int(absent.value)
+
+    def set_flags_dev(self, d_kmers_ptr, n, flag=0, d_flags_ptr=None, d_absent_ptr=None, stream=None):
+        """Device-resident set (bft_gpu_marks_set_dev): one flag, or one byte per k-mer at d_flags_ptr; no synchronisation."""
+        _lib.check(self._lib.bft_gpu_marks_set_dev(self._h, C.c_void_p(d_kmers_ptr), n, C.c_void_p(d_flags_ptr or 0), int(flag), C.c_void_p(d_absent_ptr or 0),
+                                                   C.c_void_p(stream or 0)))
+
+    def get_flags(self, kmers):
+        """get_flag_kmer for a batch: uint8 per k-mer, 0..3, or 0xFF for an absent k-mer."""
+        kmers = self._chk(kmers)
+        out = np.zeros(len(kmers), dtype=np.uint8)
+        _lib.check(self._lib.bft_gpu_marks_get(self._h, kmers.ctypes.data, len(kmers), out.ctypes.data, None))
+        return out
+
+    def get_flags_dev(self, d_kmers_ptr, n, d_flags_out_ptr, d_absent_ptr=None, stream=None):
+        _lib.check(self._lib.bft_gpu_marks_get_dev(self._h, C.c_void_p(d_kmers_ptr), n, C.c_void_p(d_flags_out_ptr), C.c_void_p(d_absent_ptr or 0), C.c_void_p(stream or 0)))
+
+    def test_and_set(self, kmers, expect, flag):
+        """A k-mer moves to `flag` only if it holds `expect`; uint8 per batch entry: 1 for the one entry that moved its k-mer, 0 otherwise."""
+        kmers = self._chk(kmers)
+        won = np.zeros(len(kmers), dtype=np.uint8)
+        _lib.check(self._lib.bft_gpu_marks_test_and_set(self._h, kmers.ctypes.data, len(kmers), int(expect), int(flag), won.ctypes.data, None))
+        return won
+
+    def test_and_set_dev(self, d_kmers_ptr, n, expect, flag, d_won_ptr, d_absent_ptr=None, stream=None):
+        _lib.check(self._lib.bft_gpu_marks_test_and_set_dev(self._h, C.c_void_p(d_kmers_ptr), n, int(expect), int(flag), C.c_void_p(d_won_ptr),
+                                                            C.c_void_p(d_absent_ptr or 0), C.c_void_p(stream or 0)))
+
+    def fill_flags(self, flag):
+        """Every stored k-mer gets `flag`."""
+        _lib.check(self._lib.bft_gpu_marks_fill(self._h, int(flag)))
+
+    def fill_flags_dev(self, flag, stream=None):
+        _lib.check(self._lib.bft_gpu_marks_fill_dev(self._h, int(flag), C.c_void_p(stream or 0)))
+
+    def flag_counts(self):
+        """uint64[4]: stored k-mers per flag value."""
+        counts = np.zeros(4, dtype=np.uint64)
+        _lib.check(self._lib.bft_gpu_marks_counts(self._h, counts.ctypes.data))
+        return counts
+
+    def flag_counts_dev(self, d_counts_ptr, stream=None):
+        _lib.check(self._lib.bft_gpu_marks_counts_dev(self._h, C.c_void_p(d_counts_ptr), C.c_void_p(stream or 0)))
+
+    def select_flagged(self, mask, ascii=False):
+        """The k-mers whose flag is in the 4-bit mask (bit f: flag f), in ascending row order.  Returns (kmers, rows) as kmers_by_count."""
+        mask = int(mask)
+        n = C.c_uint64()
+        _lib.check(self._lib.bft_gpu_marks_select(self._h, mask, None, None, None, 0, C.byref(n)))
+        m = int(n.value)
+        rows = np.zeros(m, dtype=np.uint32)
+        if ascii:
+            out = np.zeros((m, self.k + 1), dtype=np.uint8)
+            _lib.check(self._lib.bft_gpu_marks_select(self._h, mask, None, out.ctypes.data, rows.ctypes.data, m, C.byref(n)))
+            if m and out[:, self.k].any():
+                raise _lib.BFTError("bft_gpu_marks_select: an ASCII k-mer is not NUL-terminated")
+            return [r.tobytes().decode() for r in out[:, :self.k]], rows
+        out = np.zeros((m, self.nb), dtype=np.uint8)
+        _lib.check(self._lib.bft_gpu_marks_select(self._h, mask, out.ctypes.data, None, rows.ctypes.data, m, C.byref(n)))
+        return out, rows
+
+    def select_flagged_dev(self, mask, d_kmers_ptr, d_ascii_ptr, d_rows_ptr, cap, d_count_ptr, stream=None):
+        _lib.check(self._lib.bft_gpu_marks_select_dev(self._h, int(mask), C.c_void_p(d_kmers_ptr or 0), C.c_void_p(d_ascii_ptr or 0), C.c_void_p(d_rows_ptr or 0), cap,
+                                                      C.c_void_p(d_count_ptr), C.c_void_p(stream or 0)))
+
+    def reach(self, seeds, genome_ids=(), through=0, to=1, boundary=False):
+        """Every eligible k-mer (flag `through`, colour set holding every id of genome_ids) connected to an eligible seed through eligible k-mers gets
+        the flag `to`; boundary=True also marks what BFS_subgraph / DFS_subgraph look at (bft_gpu_marks_reach).  Returns (seed_new: uint8 per seed,
+        1 for the lowest-index eligible seed of each component; counts: uint64 {eligible painted, boundary painted, seeds absent})."""
+        seeds = self._chk(seeds)
+        ids = np.ascontiguousarray(genome_ids, dtype=np.uint32)
+        seed_new = np.zeros(len(seeds), dtype=np.uint8)
+        counts = np.zeros(3, dtype=np.uint64)
+        _lib.check(self._lib.bft_gpu_marks_reach(self._h, seeds.ctypes.data, len(seeds), ids.ctypes.data if len(ids) else None, len(ids), int(through), int(to),
+                                                 1 if boundary else 0, seed_new.ctypes.data, counts.ctypes.data))
+        return seed_new, counts
+
+    def reach_dev(self, d_seeds_ptr, n_seeds, d_seed_new_ptr, d_counts_ptr, genome_ids=(), through=0, to=1, boundary=False, stream=None):
+        ids = np.ascontiguousarray(genome_ids, dtype=np.uint32)
+        _lib.check(self._lib.bft_gpu_marks_reach_dev(self._h, C.c_void_p(d_seeds_ptr), n_seeds, ids.ctypes.data if len(ids) else None, len(ids), int(through), int(to),
+                                                     1 if boundary else 0, C.c_void_p(d_seed_new_ptr or 0), C.c_void_p(d_counts_ptr), C.c_void_p(stream or 0)))
+
+    def read_flags(self):
+        """The packed flag array: uint8, 4 rows per byte, row r in bits 2 (r % 4) .. + 1 of byte r // 4 (rows in the order of extract())."""
+        n = C.c_uint64()
+        _lib.check(self._lib.bft_gpu_marks_read(self._h, None, 0, C.byref(n)))
+        out = np.zeros(int(n.value), dtype=np.uint8)
+        _lib.check(self._lib.bft_gpu_marks_read(self._h, out.ctypes.data if len(out) else None, len(out), C.byref(n)))
+        return out
+
+    def write_flags(self, packed):
+        """The whole packed flag array in (the layout of read_flags)."""
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        _lib.check(self._lib.bft_gpu_marks_write(self._h, packed.ctypes.data if len(packed) else None, len(packed)))
+
     def genome_name(self, id_genome):
         """The name of genome id_genome (the reference's filenames[id_genome]; "genome_<id>" for an id that was never named)."""
         buf = C.create_string_buffer(4096)

@@ -81,6 +81,7 @@ void free_cdbg(BFT* bft) {
     if (bft == NULL) return;
     for (int i = 0; i < bft->nb_genomes; i++) free(bft->filenames[i]);
     free(bft->filenames);
+    free(bft->marks);
     bft_gpu_free(bft->gpu);
     free(bft);
 }
@@ -745,16 +746,136 @@ void extract_simple_core_paths_to_disk(BFT* graph, double core_ratio, char* file
                          "extract_simple_core_paths_to_disk()");
 }
 
+/* ---------------------------------------------------------------- marking (include/bft.h:143-146, src/bft.c:686-765) */
+
+/* While the graph is marking, bft->marks is a host copy of the handle's packed flag array (4 rows per byte, bft_gpu_marks_read): set_flag_kmer and
+ * get_flag_kmer touch only the copy, by the row the k-mer's res already holds -- no GPU round trip per k-mer.  The copy goes to the GPU before a GPU
+ * operation if it changed (marks_push), and comes back after one that painted (marks_pull). */
+static void marks_push(BFT* bft, const char* where) {
+    if (!bft->marks_dirty) return;
+    ck(bft_gpu_marks_write(bft->gpu, bft->marks, bft->marks_bytes), where);
+    bft->marks_dirty = 0;
+}
+static void marks_pull(BFT* bft, const char* where) {
+    ck(bft_gpu_marks_read(bft->gpu, bft->marks, bft->marks_bytes, NULL), where);
+}
+
+void set_marking(BFT* bft) {
+    NOT_NULL(bft, "set_marking()");
+    if ((bft->marked & 0x1) == 0) {
+        ck(bft_gpu_marks_begin(bft->gpu), "set_marking()");
+        ck(bft_gpu_marks_read(bft->gpu, NULL, 0, &bft->marks_bytes), "set_marking()");
+        free(bft->marks);
+        bft->marks = calloc(bft->marks_bytes ? (size_t)bft->marks_bytes : 1, 1); /* (every flag is 0 after bft_gpu_marks_begin) */
+        NOT_NULL(bft->marks, "set_marking()");
+        bft->marks_dirty = 0;
+        bft->marked |= 0x1;
+    }
+}
+
+void unset_marking(BFT* bft) {
+    NOT_NULL(bft, "unset_marking()");
+    ck(bft_gpu_marks_end(bft->gpu), "unset_marking()");
+    free(bft->marks);
+    bft->marks = NULL;
+    bft->marks_bytes = 0;
+    bft->marks_dirty = 0;
+    bft->marked &= 0xfe;
+}
+
+void set_flag_kmer(uint8_t flag, BFT_kmer* bft_kmer, BFT* bft) {
+    NOT_NULL(bft_kmer, "set_flag_kmer()");
+    NOT_NULL(bft, "set_flag_kmer()");
+    if (flag > 3) DIE("set_flag_kmer(): a flag can only have as value 0, 1, 2 or 3.\n");
+    if ((bft->marked & 0x1) == 0) DIE("set_flag_kmer(): the graph is not initialized for marking.\n");
+    if (!is_kmer_in_cdbg(bft_kmer) || ((uint64_t)bft_kmer->res->row >> 2) >= bft->marks_bytes) DIE("set_flag_kmer(): k-mer is not present in the graph.\n");
+    const uint32_t row = bft_kmer->res->row, sh = 2 * (row & 3);
+    uint8_t* b = &bft->marks[row >> 2];
+    const uint8_t v = (uint8_t)((*b & ~(3u << sh)) | ((uint32_t)flag << sh));
+    if (v != *b) {
+        *b = v;
+        bft->marks_dirty = 1;
+    }
+}
+
+uint8_t get_flag_kmer(BFT_kmer* bft_kmer, BFT* bft) {
+    NOT_NULL(bft_kmer, "get_flag_kmer()");
+    NOT_NULL(bft, "get_flag_kmer()");
+    if ((bft->marked & 0x1) == 0) DIE("get_flag_kmer(): the graph is not initialized for marking.\n");
+    if (!is_kmer_in_cdbg(bft_kmer) || ((uint64_t)bft_kmer->res->row >> 2) >= bft->marks_bytes) DIE("get_flag_kmer(): k-mer is not present in the graph.\n");
+    const uint32_t row = bft_kmer->res->row;
+    return (uint8_t)((bft->marks[row >> 2] >> (2 * (row & 3))) & 3);
+}
+
 /* ---------------------------------------------------------------- connected components (<bft/snippets.h>) */
 
-/* BFS, DFS, BFS_subgraph and DFS_subgraph (src/snippets.c:605-822) walk from one k-mer and mark what they visit: this library has no vertex marks.
- * They exist so that a program can hand them to get_nb_connected_component, which tells them apart by their addresses; called in any other way
- * they stop the program. */
-#define NEEDS_MARKING(where) DIE("%s: vertex marking is not provided; pass it to get_nb_connected_component() to count components.\n", where)
-size_t BFS(BFT_kmer* kmer, BFT* graph, va_list args) { (void)kmer; (void)graph; (void)args; NEEDS_MARKING("BFS()"); }
-size_t BFS_subgraph(BFT_kmer* kmer, BFT* graph, va_list args) { (void)kmer; (void)graph; (void)args; NEEDS_MARKING("BFS_subgraph()"); }
-size_t DFS(BFT_kmer* kmer, BFT* graph, va_list args) { (void)kmer; (void)graph; (void)args; NEEDS_MARKING("DFS()"); }
-size_t DFS_subgraph(BFT_kmer* kmer, BFT* graph, va_list args) { (void)kmer; (void)graph; (void)args; NEEDS_MARKING("DFS_subgraph()"); }
+/* BFS, DFS, BFS_subgraph and DFS_subgraph (src/snippets.c:605-822) on a graph that is marking: a k-mer whose flag is not 0 gives 0; otherwise ONE
+ * bft_gpu_marks_reach from it (through 0, to 1) paints what the reference's walk would mark -- the _subgraph forms with the boundary rows and the ids
+ * read as the reference reads them -- and the result is what the reach says of the seed.  On a graph that is NOT marking they stop the program (the
+ * reference would, in get_flag_kmer); the message names get_nb_connected_component, which counts components without marks. */
+#define NEEDS_MARKING(where) DIE("%s: vertex marking is not set (set_marking()); pass it to get_nb_connected_component() to count components.\n", where)
+static size_t traverse(BFT_kmer* kmer, BFT* graph, va_list args, int sub, const char* where) {
+    NOT_NULL(kmer, where);
+    NOT_NULL(graph, where);
+    if ((graph->marked & 0x1) == 0) NEEDS_MARKING(where);
+    if (get_flag_kmer(kmer, graph) != 0) return 0;
+    uint32_t* ids = NULL;
+    int nb_ids = 0;
+    if (sub) {
+        va_list cpy;
+        va_copy(cpy, args);
+        nb_ids = va_arg(cpy, int);
+        bool in_order = nb_ids > 0;
+        if (nb_ids > 0) {
+            ids = malloc((size_t)nb_ids * sizeof(uint32_t));
+            NOT_NULL(ids, where);
+            for (int i = 0; i < nb_ids; i++) {
+                ids[i] = va_arg(cpy, uint32_t);
+                if (i && ids[i] <= ids[i - 1]) in_order = false;
+            }
+        }
+        va_end(cpy);
+        if (!in_order) { /* is_in_subgraph is false for every k-mer: the k-mer is marked visited and starts nothing (src/snippets.c:683-731) */
+            free(ids);
+            set_flag_kmer(1, kmer, graph);
+            return 0;
+        }
+    }
+    marks_push(graph, where);
+    uint8_t seed_new = 0;
+    uint64_t counts[3] = {0, 0, 0};
+    ck(bft_gpu_marks_reach(graph->gpu, kmer->kmer_comp, 1, ids, (uint32_t)nb_ids, 0, 1, sub, &seed_new, counts), where);
+    free(ids);
+    if (counts[0] + counts[1]) marks_pull(graph, where);
+    return seed_new;
+}
+size_t BFS(BFT_kmer* kmer, BFT* graph, va_list args) { return traverse(kmer, graph, args, 0, "BFS()"); }
+size_t BFS_subgraph(BFT_kmer* kmer, BFT* graph, va_list args) { return traverse(kmer, graph, args, 1, "BFS_subgraph()"); }
+size_t DFS(BFT_kmer* kmer, BFT* graph, va_list args) { return traverse(kmer, graph, args, 0, "DFS()"); }
+size_t DFS_subgraph(BFT_kmer* kmer, BFT* graph, va_list args) { return traverse(kmer, graph, args, 1, "DFS_subgraph()"); }
+
+/* src/snippets.c:883-906: marking on, f on every k-mer, marking off. */
+void cdbg_traversal(BFT* graph, BFT_func_ptr f, ...) {
+    NOT_NULL(graph, "cdbg_traversal()");
+    va_list args;
+    va_start(args, f);
+    set_neighbors_traversal(graph);
+    set_marking(graph);
+    v_iterate_over_kmers(graph, f, args);
+    unset_marking(graph);
+    unset_neighbors_traversal(graph);
+    va_end(args);
+}
+
+/* src/snippets.c:915-930: the callback of iterate_over_kmers on a marking graph -- args: int* nb, the traversal, the traversal's own arguments. */
+size_t nb_connected_components(BFT_kmer* kmer, BFT* graph, va_list args) {
+    int* nb_connected_comp = va_arg(args, int*);
+    BFT_func_ptr f = va_arg(args, BFT_func_ptr);
+    NOT_NULL(nb_connected_comp, "nb_connected_components()");
+    NOT_NULL(f, "nb_connected_components()");
+    *nb_connected_comp += f(kmer, graph, args) == true;
+    return 1;
+}
 
 /* src/snippets.c:824-881: the k-mer's sorted id list is walked against the requested ids in the order given, and the walk stops at the first list
  * id above the one looked for.  True only when nb_id_genomes > 0, the ids are strictly increasing and all of them are in the k-mer's set. */

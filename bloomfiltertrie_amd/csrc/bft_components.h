@@ -20,8 +20,9 @@ struct BftCcScratch {
 // strictly increasing); first = 0 ANDs into what an earlier launch wrote (more than BFT_CC_IDS ids)
 int bft_cc_sets(uint64_t n_sets, const uint32_t* d_cs_off, const void* d_cs_ids, uint32_t cs_w, const uint32_t* ids, uint32_t nb, bool first, const BftCcScratch& p,
                 hipStream_t s);
-// parent[u] = u for a member, BFT_CC_NONE otherwise (d_tcol NULL: every row is a member)
-int bft_cc_init(uint64_t n, const uint32_t* d_tcol, const BftCcScratch& p, hipStream_t s);
+// parent[u] = u for a member, BFT_CC_NONE otherwise (d_tcol NULL: every row is a member).  d_marks (bft_marking.h's flag words; NULL: no such
+// condition): a member must also hold the vertex flag `through`
+int bft_cc_init(uint64_t n, const uint32_t* d_tcol, const BftCcScratch& p, hipStream_t s, const uint32_t* d_marks = nullptr, uint32_t through = 0);
 // every member row joined with its member successors (lock-free union-find; start[] from bft_sp_buckets)
 int bft_cc_hook(int W, const uint64_t* d_tk, uint64_t n, int k, const BftCcScratch& p, hipStream_t s);
 // parent[u] = the root of u

@@ -2,7 +2,7 @@
 // snippets.h, src/snippets.c:605-960) over the sorted T-form table tk (one row per stored k-mer, rows in the bft_gpu_extract order):
 //   (bft_sp_buckets  first row of every bucket of the top bits of the T-form, as for the simple paths)
 //   k_cc_sets     one lane per colour set: does its sorted id list hold every requested id (a merge of the two sorted lists)
-//   k_cc_init     parent[u] = u for a member, BFT_CC_NONE for any other row
+//   k_cc_init     parent[u] = u for a member, BFT_CC_NONE for any other row (bft_marking.hip adds a condition on the row's vertex flag)
 //   k_cc_hook     one lane per member row u: its stored successors come from ONE lower bound (bft_for_each_successor, bft_succ.h), and u is joined
 //                 with every member successor v != u.  Predecessor edges are the same edges seen from the other end.  The union-find is lock-free:
 //                 the larger root is linked under the smaller (atomicCAS(&parent[hi], hi, lo), retried from the returned value), so a tree's root
@@ -49,10 +49,14 @@ __global__ __launch_bounds__(CC_THREADS) void k_cc_sets(uint32_t n_sets, const u
     }
 }
 
+// (marks: the two-bit vertex flags of bft_marking.h, 16 rows per word -- a member must also hold the flag `through`; NULL: no such condition)
 __global__ __launch_bounds__(CC_THREADS) void k_cc_init(uint32_t n, const uint32_t* __restrict__ tcol, const uint8_t* __restrict__ member,
-                                                        uint32_t* __restrict__ parent) {
-    for (uint64_t u = blockIdx.x * (uint64_t)CC_THREADS + threadIdx.x; u < n; u += (uint64_t)gridDim.x * CC_THREADS)
-        parent[u] = (tcol == nullptr || member[tcol[u]]) ? (uint32_t)u : BFT_CC_NONE;
+                                                        const uint32_t* __restrict__ marks, uint32_t through, uint32_t* __restrict__ parent) {
+    for (uint64_t u = blockIdx.x * (uint64_t)CC_THREADS + threadIdx.x; u < n; u += (uint64_t)gridDim.x * CC_THREADS) {
+        bool in = tcol == nullptr || member[tcol[u]];
+        if (in && marks != nullptr) in = ((marks[u >> 4] >> (2u * ((uint32_t)u & 15u))) & 3u) == through;
+        parent[u] = in ? (uint32_t)u : BFT_CC_NONE;
+    }
 }
 
 __device__ __forceinline__ uint32_t cc_load(uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -188,9 +192,9 @@ int bft_cc_sets(uint64_t n_sets, const uint32_t* d_cs_off, const void* d_cs_ids,
     return 0;
 }
 
-int bft_cc_init(uint64_t n, const uint32_t* d_tcol, const BftCcScratch& p, hipStream_t s) {
+int bft_cc_init(uint64_t n, const uint32_t* d_tcol, const BftCcScratch& p, hipStream_t s, const uint32_t* d_marks, uint32_t through) {
     if (n == 0) return 0;
-    hipLaunchKernelGGL(k_cc_init, cc_grid(n), dim3(CC_THREADS), 0, s, (uint32_t)n, d_tcol, (const uint8_t*)p.member, p.parent);
+    hipLaunchKernelGGL(k_cc_init, cc_grid(n), dim3(CC_THREADS), 0, s, (uint32_t)n, d_tcol, (const uint8_t*)p.member, d_marks, through, p.parent);
     HIPCK(hipGetLastError());
     return 0;
 }

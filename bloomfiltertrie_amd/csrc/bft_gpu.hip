@@ -402,6 +402,7 @@ extern "C" int bft_gpu_genome_name(bft_gpu* h, uint32_t id_genome, char* out, ui
 
 extern "C" int bft_gpu_add_genome(bft_gpu* h, const char* name, uint32_t* id_genome) {
     if (!h || !name) return fail(BFT_GPU_E_ARG, "NULL argument");
+    if (h->marking) return fail(BFT_GPU_E_STATE, "add_genome: the graph is locked for vertex marking (bft_gpu_marks_end unlocks it)");
     h->genomes.push_back(name);
     if (id_genome) *id_genome = (uint32_t)h->genomes.size() - 1;
     return BFT_GPU_OK;
@@ -473,6 +474,7 @@ static int launch_pack(bft_gpu* h, const uint8_t* d_packed, uint64_t n, uint32_t
 static int insert_dev(bft_gpu* h, const void* d_kmers, uint64_t n, uint32_t id_genome, hipStream_t s, bool ordered, bool own_async = false) {
     if (!h || (!d_kmers && n)) return fail(BFT_GPU_E_ARG, "NULL argument");
     if (id_genome >= BFT_MAX_GENOME_ID) return fail(BFT_GPU_E_ARG, "id_genome out of range (must be below 2^24)");
+    if (h->marking) return fail(BFT_GPU_E_STATE, "insert: the graph is locked for vertex marking (bft_gpu_marks_end unlocks it)");
     if (n == 0) return BFT_GPU_OK;
     ENTER(h);
     // No bound on the pairs an index holds (the reference has none, src/insertNode.c:18-36): a batch beyond what one sort takes is
@@ -512,6 +514,7 @@ extern "C" int bft_gpu_insert_kmers_dev_async(bft_gpu* h, const void* d_kmers, u
 extern "C" int bft_gpu_insert_kmers(bft_gpu* h, const uint8_t* kmers, uint64_t n, uint32_t id_genome) {
     if (!h || (!kmers && n)) return fail(BFT_GPU_E_ARG, "NULL argument");
     if (id_genome >= BFT_MAX_GENOME_ID) return fail(BFT_GPU_E_ARG, "id_genome out of range (must be below 2^24)");
+    if (h->marking) return fail(BFT_GPU_E_STATE, "insert: the graph is locked for vertex marking (bft_gpu_marks_end unlocks it)");
     if (n == 0) return BFT_GPU_OK;
     ENTER(h);
     if (n * (uint64_t)h->B <= bft_gpu::RING_SLOT) {  // through the pinned ring (see struct bft_gpu)
@@ -1419,6 +1422,7 @@ int bft_commit_image(bft_gpu* h, DevBuf& tk, DevBuf& n_tcol, DevBuf& n_cs_off, D
 
 extern "C" int bft_gpu_build(bft_gpu* h) {
     if (!h) return fail(BFT_GPU_E_ARG, "NULL handle");
+    if (h->marking) return fail(BFT_GPU_E_STATE, "build: the graph is locked for vertex marking (bft_gpu_marks_end unlocks it)");
     ENTER(h);
     if (h->built && h->log_n == 0) return BFT_GPU_OK;
     CK(wait_foreign_stream(h));  // batches still being packed into the log on a caller's stream (bft_gpu_insert_kmers_dev_async)

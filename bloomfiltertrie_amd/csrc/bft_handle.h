@@ -1,6 +1,6 @@
 // bft_handle.h -- the handle behind the C-ABI (struct bft_gpu) and the host helpers every entry point needs, for the translation units that hold
 // entry points: bft_gpu.hip (which defines the helpers) and the analysis families bft_prefix.hip, bft_paths.hip, bft_components.hip, bft_pangenome.hip,
-// bft_subgraph.hip.
+// bft_subgraph.hip, bft_marking.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -215,6 +215,17 @@ struct bft_gpu {
     HandleScratch pg{"k-mer classes"};
     DevBuf pg_buf, pg_tmp;           // pan-genome k-mer classes (BftPgScratch, bft_pangenome.h) and their scan's temporary
     uint64_t pg_m = 0, pg_sets = 0;  // rows and colour sets pg_buf has room for
+    // Vertex marks (bft_marking.hip): on between bft_gpu_marks_begin and bft_gpu_marks_end; insertions and builds are refused meanwhile, so the rows
+    // the flags are indexed by cannot move.
+    bool marking = false;
+    HandleScratch mk{"marks"};
+    DevBuf mk_flags;                 // two bits per stored k-mer, 16 rows per 32-bit word (bft_marking.h)
+    DevBuf mk_rows, mk_bits;         // a batch's rows in the table and its presence bits
+    DevBuf mk_slot, mk_tmp;          // select: the scan of the selection and its temporary
+    DevBuf mk_forest;                // reach: bucket starts, the flattened forest, members among the colour sets, the seed slot per root
+    bool mk_forest_ok = false;       // mk_forest holds the forest of the eligible rows for (mk_forest_through, mk_forest_ids)
+    uint32_t mk_forest_through = 0;
+    std::vector<uint32_t> mk_forest_ids;
 
     bool inject_build_failure = false;  // test hook: the next bft_gpu_build fails right before its commit point (one shot)
     bool opt_build_stages = false;      // "build_stages": the next builds record GPU time and bytes per stage (bft_gpu_build_stages)

@@ -17,7 +17,7 @@
  *     bft_gpu.h on bft_device_index(bft) -- that is the point of the GPU path;
  *   - insertions are collected on the GPU and the containers are rebuilt in bulk by the first query after them;
  *   - there is no CPU fallback: without a usable GPU every function reports the error and exits.
- * Not provided (outside the path): marking / flags, annotation set operations, prefix_matching_custom,
+ * Not provided (outside the path): annotation set operations, prefix_matching_custom,
  * colour compression (write_BFT ignores compress_annotations and writes uncompressed annotations, which the reference loads).
  */
 #ifndef BFT_GPU_COMPAT_BFT_H
@@ -63,8 +63,11 @@ typedef struct BFT_Root {
     int nb_genomes;
     int treshold_compression;
     uint8_t compressed; /* always 0, as the reference's CLI and create_cdbg set it */
-    uint8_t marked;     /* always 0 here (marking is not provided) */
+    uint8_t marked;     /* bit 0: the graph is locked for vertex marking (set_marking / unset_marking), as in the reference */
     bft_gpu* gpu;       /* the index, resident in HBM */
+    uint8_t* marks;     /* while marking: host copy of the packed flag array (4 rows per byte, bft_gpu_marks_read); NULL otherwise */
+    uint64_t marks_bytes;
+    uint8_t marks_dirty; /* the copy holds flags the GPU has not seen yet */
     Node node;          /* last member as in the reference (include/Node.h:121): the root vertex handed to isKmerPresent */
 } BFT_Root;
 
@@ -171,6 +174,17 @@ bool prefix_matching(BFT* bft, char* prefix, BFT_func_ptr f, ...);
  * not read. ---- */
 BFT* create_cdbg_from_bft_kmers(BFT_kmer** bft_kmers, uint32_t nb_bft_kmers, BFT* bft, bool add_colors);
 void add_id_genomes(BFT_kmer* bft_kmer, BFT_annotation* bft_annot, BFT* bft, uint32_t* list_id_genomes);
+
+/* ---- marking (include/bft.h:143-146, src/bft.c:686-765).  set_marking locks the graph (no insertion until unset_marking) and gives every k-mer
+ * the flag 0; on a graph that is already marking it changes nothing.  A flag is 0, 1, 2 or 3.  set_flag_kmer / get_flag_kmer take a k-mer obtained
+ * from this graph (get_kmer, get_neighbors, iterate_over_kmers, prefix_matching: its res holds its row) and work on a host copy of the flags: no
+ * GPU call per k-mer.  The reference's messages and exit(EXIT_FAILURE): a flag above 3, a graph that is not marking, a k-mer that is not in the
+ * graph.  Batches of k-mers: bft_gpu_marks_* of bft_gpu.h on bft_device_index(bft) -- not while flags set here are pending: the traversal snippets
+ * of <bft/snippets.h> are the calls that move the copy to the GPU and back. ---- */
+void set_marking(BFT* bft);
+void unset_marking(BFT* bft);
+void set_flag_kmer(uint8_t flag, BFT_kmer* bft_kmer, BFT* bft);
+uint8_t get_flag_kmer(BFT_kmer* bft_kmer, BFT* bft);
 
 /* ---- disk (include/bft.h:175-176, src/bft.c:1090-1110, src/write_to_disk.c) ---- */
 void write_BFT(BFT* bft, char* filename, bool compress_annotations);

@@ -9,12 +9,12 @@
  * written one per line in ascending row of their first k-mer (the order of iterate_over_kmers); the reference writes them in the order its
  * walk happens to reach them, and that order also decides where it starts a cycle (INTEGRATION.md lists every difference).
  *
- * The traversals BFS, DFS, BFS_subgraph, DFS_subgraph, the predicate is_in_subgraph and get_nb_connected_component are declared in
- * <bft/snippets_traversal.h>; the k-mer class extractors extract_core_kmers / extract_dispensable_kmers / extract_singleton_kmers and
+ * The traversals BFS, DFS, BFS_subgraph, DFS_subgraph, the predicate is_in_subgraph, get_nb_connected_component, cdbg_traversal and
+ * nb_connected_components are declared in <bft/snippets_traversal.h>; the k-mer class extractors extract_core_kmers / extract_dispensable_kmers / extract_singleton_kmers and
  * extract_pangenome_kmers_to_disk in <bft/snippets_pangenome.h>.  This header includes both.
  *
- * Not provided: the per-k-mer callbacks extract_simple_paths and extract_core_simple_paths (they need marking), cdbg_traversal and
- * nb_connected_components as a callback (they need marking too), and the annotation set operations intersection_annotations /
+ * Not provided: the per-k-mer callbacks extract_simple_paths and extract_core_simple_paths (vertex marking, which they need, is provided by
+ * <bft/bft.h>; their reference text has undefined behaviour), and the annotation set operations intersection_annotations /
  * union_annotations / sym_difference_annotations.
  */
 #ifndef BFT_GPU_COMPAT_SNIPPETS_H

@@ -377,6 +377,69 @@ int bft_gpu_pangenome_stats(bft_gpu* h, uint64_t* spectrum, uint64_t* genome_tot
 /* The same into device buffers (uint64) on hip_stream (NULL = the handle's stream), without host synchronisation.  Not inside a graph capture. */
 int bft_gpu_pangenome_stats_dev(bft_gpu* h, void* d_spectrum, void* d_genome_total, void* d_genome_private, uint32_t cap, void* hip_stream);
 
+/* Vertex marking: set_marking / unset_marking / set_flag_kmer / get_flag_kmer (reference include/bft.h:143-146, src/bft.c:686-765) for batches, and
+ * what the reference's traversals do with the marks (BFS / DFS / BFS_subgraph / DFS_subgraph, src/snippets.c:605-812) as ONE call, bft_gpu_marks_reach.
+ * A flag is 0, 1, 2 or 3 (anything above is BFT_GPU_E_ARG); every stored k-mer has one, 0 after bft_gpu_marks_begin.  The flags are an array in HBM that
+ * belongs to the handle: two bits per stored k-mer, indexed by its row in the stored k-mer table (the bft_gpu_extract order, what bft_gpu_query_rows
+ * reports); as bytes, 4 rows per byte, row r in bits 2 (r % 4) .. + 1 of byte r / 4 -- CEIL(n_kmers / 4) bytes, the bits behind the last row 0.
+ * bft_gpu_marks_begin (set_marking): pending insertions are built, the sorted table comes back ("compact_table") and the zeroed flags are allocated; on a
+ *   handle that is already marking it does nothing and the flags stay (src/bft.c:694).  Until bft_gpu_marks_end (unset_marking: the flags are released;
+ *   a no-op on a handle that is not marking), bft_gpu_insert_kmers*, bft_gpu_add_genome and bft_gpu_build return BFT_GPU_E_STATE -- "no insertion can
+ *   happen before unlocking" (src/bft.c:686); queries and the analysis calls are unaffected.  bft_gpu_free releases the marks with the handle.
+ * Every other call below returns BFT_GPU_E_STATE on a handle that is not marking.  The marks are not carried by bft_gpu_image_pack, .bft files,
+ * bft_gpu_subgraph or a device group: they belong to this handle alone.
+ * Batches are packed k-mers (the layout of every batch here); their rows come from the lookup of bft_gpu_query_rows.  Absent k-mers are ignored and
+ * counted in *n_absent (may be NULL).  Launches are counted in bft_gpu_kernel_time.
+ * The *_dev forms take device buffers and run on hip_stream (NULL = the handle's stream) without host synchronisation; their d_n_absent (uint64, device,
+ * may be NULL) is always written when given.  Scratch (4 bytes per k-mer of the batch) belongs to the handle: calls on different streams are serialised
+ * by the library.  Not inside a graph capture (BFT_GPU_E_ARG). */
+int bft_gpu_marks_begin(bft_gpu* h);
+int bft_gpu_marks_end(bft_gpu* h);
+/* set_flag_kmer (src/bft.c:721-741) for a batch: flags == NULL gives every k-mer `flag`; otherwise k-mer i gets flags[i] (one byte each, 0..3; the
+ * resident form cannot look at them without a synchronisation and keeps their two low bits) and `flag` is not read.  A k-mer that appears several
+ * times with different flags ends with one of them, never a mixture of their bits. */
+int bft_gpu_marks_set(bft_gpu* h, const uint8_t* kmers, uint64_t nb_kmers, const uint8_t* flags, uint8_t flag, uint64_t* n_absent);
+int bft_gpu_marks_set_dev(bft_gpu* h, const void* d_kmers, uint64_t nb_kmers, const void* d_flags, uint8_t flag, void* d_n_absent, void* hip_stream);
+/* get_flag_kmer (src/bft.c:747-765) for a batch: flags_out[i] = 0..3, or 0xFF for an absent k-mer (the reference exits there). */
+int bft_gpu_marks_get(bft_gpu* h, const uint8_t* kmers, uint64_t nb_kmers, uint8_t* flags_out, uint64_t* n_absent);
+int bft_gpu_marks_get_dev(bft_gpu* h, const void* d_kmers, uint64_t nb_kmers, void* d_flags_out, void* d_n_absent, void* hip_stream);
+/* The step of a frontier of the caller's own (the `get_flag_kmer(...) == V_NOT_VISITED` test followed by set_flag_kmer of src/snippets.c:628-630, as one
+ * atomic operation): k-mer i moves to `flag` only if it holds `expect`; won_out[i] = 1 for the ONE entry of the batch that moved it, 0 for every
+ * other entry (a repeat of the k-mer, a k-mer that held something else, an absent k-mer).  flag == expect is BFT_GPU_E_ARG. */
+int bft_gpu_marks_test_and_set(bft_gpu* h, const uint8_t* kmers, uint64_t nb_kmers, uint8_t expect, uint8_t flag, uint8_t* won_out, uint64_t* n_absent);
+int bft_gpu_marks_test_and_set_dev(bft_gpu* h, const void* d_kmers, uint64_t nb_kmers, uint8_t expect, uint8_t flag, void* d_won_out, void* d_n_absent,
+                                   void* hip_stream);
+/* Every stored k-mer gets `flag` (0: what delete + create_marking would leave, src/bft.c:696,710); the host form synchronises. */
+int bft_gpu_marks_fill(bft_gpu* h, uint8_t flag);
+int bft_gpu_marks_fill_dev(bft_gpu* h, uint8_t flag, void* hip_stream);
+/* counts[f] (4 x uint64) = stored k-mers that hold flag f. */
+int bft_gpu_marks_counts(bft_gpu* h, uint64_t* counts);
+int bft_gpu_marks_counts_dev(bft_gpu* h, void* d_counts, void* hip_stream);
+/* The k-mers whose flag is in `mask` (bit f set: flag f is wanted; 0 .. 15), in ascending row order, with the outputs, the cap and the
+ * BFT_GPU_E_NOSPACE rule of bft_gpu_kmers_by_count / _dev: packed k-mers, ASCII k-mers of k + 1 bytes with the NUL, rows; any may be NULL. */
+int bft_gpu_marks_select(bft_gpu* h, uint32_t mask, uint8_t* kmers_out, char* ascii_out, uint32_t* rows_out, uint64_t cap, uint64_t* n_out);
+int bft_gpu_marks_select_dev(bft_gpu* h, uint32_t mask, void* d_kmers_out, void* d_ascii_out, void* d_rows_out, uint64_t cap, void* d_count, void* hip_stream);
+/* Reachability restricted by flag.  A row is ELIGIBLE when its flag is `through` and its colour set holds every id of genome_ids (host array, strictly
+ * increasing as for bft_gpu_components; nb_ids = 0: every colour set qualifies).  Every eligible row connected to an eligible seed through eligible rows
+ * -- the edges of bft_gpu_components -- gets the flag `to` (`to` == `through` is BFT_GPU_E_ARG).  With through = 0, to = 1 and no ids this is what
+ * calling BFS or DFS (src/snippets.c:605-656, 743-762) on each seed in order leaves behind.  boundary != 0 reproduces the marks of BFS_subgraph /
+ * DFS_subgraph (:667-735, :773-812), which mark every unvisited k-mer they LOOK at: a seed that holds `through` without being eligible, and every
+ * row that holds `through`, is not eligible and is a neighbour of a row this call painted, get `to` as well.
+ * seeds: n_seeds packed k-mers.  seed_new[i] (may be NULL) = 1 when seed i is eligible and is the lowest-index seed of its component, else 0: what the
+ * reference's traversal would return for the seeds taken in order.  counts (3 x uint64, may be NULL in the host form): {eligible rows painted, boundary
+ * rows painted, seeds absent}.  The components are found by the union-find of bft_gpu_components, never level by level: the number of launches depends
+ * on the arguments alone.  The flattened forest stays on the handle, keyed by (through, genome_ids): painting removes whole components of eligible rows,
+ * so the next reach with the same key starts from it; any set, test-and-set, fill or write of the flags, or a reach with another key, drops it.  That
+ * is what makes a traversal of the whole graph, one reach per component, cost one union-find.  At most 2^31 - 1 k-mers (BFT_GPU_E_LIMIT). */
+int bft_gpu_marks_reach(bft_gpu* h, const uint8_t* seeds, uint64_t n_seeds, const uint32_t* genome_ids, uint32_t nb_ids, uint8_t through, uint8_t to,
+                        int boundary, uint8_t* seed_new, uint64_t* counts);
+int bft_gpu_marks_reach_dev(bft_gpu* h, const void* d_seeds, uint64_t n_seeds, const uint32_t* genome_ids, uint32_t nb_ids, uint8_t through, uint8_t to,
+                            int boundary, void* d_seed_new, void* d_counts, void* hip_stream);
+/* The whole flag array out and in, in the byte layout above.  read: *n_bytes (may be NULL) = CEIL(n_kmers / 4); bytes_out may be NULL to learn it,
+ * cap below it is BFT_GPU_E_NOSPACE.  write: n_bytes must be exactly that, and the bits behind the last row 0 (BFT_GPU_E_ARG otherwise). */
+int bft_gpu_marks_read(bft_gpu* h, uint8_t* bytes_out, uint64_t cap, uint64_t* n_bytes);
+int bft_gpu_marks_write(bft_gpu* h, const uint8_t* bytes_in, uint64_t n_bytes);
+
 /* A colour set as the reference's annotation bytes -- BFT_annotation::annot as get_annotation returns it
  * (include/bft.h:97, src/bft.c:363-387): mode 0 (bitmap, genome g <-> bit g+2), 1 (ranges) or 2 (id list), chosen the way the
  * reference chooses it: compute_best_mode re-decides at every insertion of a genome id and keeps the current mode on a size tie
