@@ -455,6 +455,73 @@ class BFT:
         _lib.check(self._lib.bft_gpu_pangenome_stats_dev(self._h, C.c_void_p(d_spectrum_ptr or 0), C.c_void_p(d_genome_total_ptr or 0),
                                                          C.c_void_p(d_genome_private_ptr or 0), cap, C.c_void_p(stream or 0)))
 
+    # -- colour-set algebra over groups (bft_gpu_combine_*: intersection / union / sym_difference of annotations, batched) -------
+    SETOPS = {"and": 0, "or": 1, "symdiff": 2}
+
+    @classmethod
+    def _setop(cls, op):
+        if op not in cls.SETOPS:
+            raise ValueError(f"op must be one of {sorted(cls.SETOPS)}, not {op!r}")
+        return cls.SETOPS[op]
+
+    @staticmethod
+    def _group_off(group_off, n):
+        """The offsets as a contiguous uint64 array, checked as the library checks them (nb_groups + 1 entries, not decreasing, the last within n)."""
+        off = np.ascontiguousarray(group_off, dtype=np.uint64)
+        if off.ndim != 1 or len(off) == 0:
+            raise ValueError("group_off must hold nb_groups + 1 offsets")
+        if (off[1:] < off[:-1]).any():
+            raise ValueError("group offsets must not decrease")
+        if len(off) > 1 and int(off[-1]) > n:
+            raise ValueError("the last group ends behind the batch")
+        return off
+
+    def combine_colors(self, kmers, group_off, op="and", skip_absent=False):
+        """intersection_annotations / union_annotations / sym_difference_annotations (include/bft.h:112-114) for groups of k-mers, reduced on the GPU
+        (bft_gpu_combine_colors): group g is kmers[group_off[g]:group_off[g + 1]].  Returns (rows uint8 [groups, CEIL(genomes / 8)], counts uint32
+        [groups] = genomes per row, found uint32 [groups] = members of the group the index stores).  An absent k-mer is the empty set, or is
+        left out of its group with skip_absent."""
+        code = self._setop(op)
+        kmers = self._chk(kmers)
+        off = self._group_off(group_off, len(kmers))
+        ng = len(off) - 1
+        self.build()  # the genome count is known once the image exists
+        g = self.info()["genomes"]
+        rows = np.zeros((ng, (g + 7) // 8), dtype=np.uint8)
+        counts = np.zeros(ng, dtype=np.uint32)
+        found = np.zeros(ng, dtype=np.uint32)
+        _lib.check(self._lib.bft_gpu_combine_colors(self._h, kmers.ctypes.data, len(kmers), off.ctypes.data, ng, code, 1 if skip_absent else 0,
+                                                    rows.ctypes.data, counts.ctypes.data, found.ctypes.data))
+        return rows, counts, found
+
+    def combine_colorsets(self, colorsets, group_off, op="and"):
+        """The same over colour-set ids (query_rows, extract, query_prefixes hand them out; 0xFFFFFFFF = an absent k-mer, the empty set):
+        (rows, counts) of bft_gpu_combine_colorsets."""
+        code = self._setop(op)
+        cs = np.ascontiguousarray(colorsets, dtype=np.uint32)
+        if cs.ndim != 1:
+            raise ValueError("colorsets must be a flat array of ids")
+        off = self._group_off(group_off, len(cs))
+        ng = len(off) - 1
+        self.build()
+        g = self.info()["genomes"]
+        rows = np.zeros((ng, (g + 7) // 8), dtype=np.uint8)
+        counts = np.zeros(ng, dtype=np.uint32)
+        _lib.check(self._lib.bft_gpu_combine_colorsets(self._h, cs.ctypes.data, len(cs), off.ctypes.data, ng, code, rows.ctypes.data, counts.ctypes.data))
+        return rows, counts
+
+    def combine_colors_dev(self, d_kmers_ptr, n, d_group_off_ptr, nb_groups, op, skip_absent, d_rows_ptr, d_counts_ptr, d_found_ptr, stream=None):
+        """Device-resident form (bft_gpu_combine_colors_dev): offsets uint64, rows nb_groups x CEIL(genomes / 8) bytes, counts / found uint32, into the
+        buffers that are not 0; no synchronisation."""
+        _lib.check(self._lib.bft_gpu_combine_colors_dev(self._h, C.c_void_p(d_kmers_ptr or 0), n, C.c_void_p(d_group_off_ptr or 0), nb_groups, self._setop(op),
+                                                        1 if skip_absent else 0, C.c_void_p(d_rows_ptr or 0), C.c_void_p(d_counts_ptr or 0),
+                                                        C.c_void_p(d_found_ptr or 0), C.c_void_p(stream or 0)))
+
+    def combine_colorsets_dev(self, d_colorsets_ptr, n, d_group_off_ptr, nb_groups, op, d_rows_ptr, d_counts_ptr, stream=None):
+        """Device-resident form over colour-set ids (bft_gpu_combine_colorsets_dev); no synchronisation."""
+        _lib.check(self._lib.bft_gpu_combine_colorsets_dev(self._h, C.c_void_p(d_colorsets_ptr or 0), n, C.c_void_p(d_group_off_ptr or 0), nb_groups,
+                                                           self._setop(op), C.c_void_p(d_rows_ptr or 0), C.c_void_p(d_counts_ptr or 0), C.c_void_p(stream or 0)))
+
     # -- vertex marking (bft_gpu_marks_*: set_marking / set_flag_kmer / get_flag_kmer and the traversals' marks) -------
     def set_marking(self):
         """set_marking (include/bft.h:143): the graph is locked (no insertion, no build) and every stored k-mer gets a flag, 0 at first; on a graph

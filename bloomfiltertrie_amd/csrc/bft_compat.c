@@ -398,6 +398,72 @@ bool presence_genome(uint32_t id_genome, BFT_annotation* bft_annot, BFT* bft) {
     return found;
 }
 
+/* intersection_annotations / union_annotations / sym_difference_annotations (src/bft.c:421-613) on the host: the annotations are host bytes already.
+ * Every argument is decoded into a bitmap in cmp_annots' result layout (src/annotation.c:2358-2551: mode 0, genome g at bit g + 2, MAX(CEIL(nb_genomes + 2,
+ * 8), 1) bytes); the AND and the OR of those bitmaps give the three results.  op: 0 intersection, 1 union, 2 symmetric difference = union minus
+ * intersection (one argument: its set). */
+static BFT_annotation* combine_annotations(BFT* bft, uint32_t nb_annotations, va_list args, int op, const char* name) {
+    if (nb_annotations == 0) DIE("%s(): no annotations given as parameters.\n", name);
+    if (bft == NULL) DIE("usage of a null pointer in function %s()\n \n", name);
+    const uint32_t G = bft->nb_genomes > 0 ? (uint32_t)bft->nb_genomes : 0;
+    const size_t len = ((size_t)G + 2 + 7) / 8 > 1 ? ((size_t)G + 2 + 7) / 8 : 1;
+    uint8_t* all = malloc(len);
+    uint8_t* any = calloc(len, 1);
+    uint8_t* cur = malloc(len);
+    if (all == NULL || any == NULL || cur == NULL) DIE("%s(): out of memory\n", name);
+    memset(all, 0xFF, len);
+    for (uint32_t i = 0; i < nb_annotations; i++) {
+        const BFT_annotation* a = va_arg(args, BFT_annotation*);
+        if (a == NULL) DIE("usage of a null pointer in function %s()\n \n", name); /* (ASSERT_NULL_PTR, include/useful_macros.h:38-43) */
+        const uint32_t n = decode_annot(a, NULL);
+        uint32_t* ids = malloc(((size_t)n + 1) * sizeof(uint32_t));
+        if (ids == NULL) DIE("%s(): out of memory\n", name);
+        decode_annot(a, ids);
+        memset(cur, 0, len);
+        for (uint32_t j = 0; j < n; j++)
+            if (ids[j] < G) cur[(ids[j] + 2) >> 3] |= (uint8_t)(1u << ((ids[j] + 2) & 7));
+        free(ids);
+        for (size_t q = 0; q < len; q++) {
+            all[q] = intersection_annots(all[q], cur[q]);
+            any[q] = union_annots(any[q], cur[q]);
+        }
+    }
+    if (op == 0) memcpy(cur, all, len);
+    else if (op == 1 || nb_annotations == 1) memcpy(cur, any, len);
+    else
+        for (size_t q = 0; q < len; q++) cur[q] = sym_difference_annots(all[q], any[q]);
+    free(all);
+    free(any);
+    BFT_annotation* out = create_BFT_annotation();
+    out->annot = cur;
+    out->size_annot = (int)len;
+    return out;
+}
+
+BFT_annotation* intersection_annotations(BFT* bft, uint32_t nb_annotations, ...) {
+    va_list args;
+    va_start(args, nb_annotations);
+    BFT_annotation* out = combine_annotations(bft, nb_annotations, args, 0, "intersection_annotations");
+    va_end(args);
+    return out;
+}
+
+BFT_annotation* union_annotations(BFT* bft, uint32_t nb_annotations, ...) {
+    va_list args;
+    va_start(args, nb_annotations);
+    BFT_annotation* out = combine_annotations(bft, nb_annotations, args, 1, "union_annotations");
+    va_end(args);
+    return out;
+}
+
+BFT_annotation* sym_difference_annotations(BFT* bft, uint32_t nb_annotations, ...) {
+    va_list args;
+    va_start(args, nb_annotations);
+    BFT_annotation* out = combine_annotations(bft, nb_annotations, args, 2, "sym_difference_annotations");
+    va_end(args);
+    return out;
+}
+
 uint32_t* intersection_list_id_genomes(uint32_t* list_a, uint32_t* list_b) { /* src/bft.c:659-688 */
     NOT_NULL(list_a, "intersection_list_id_genomes()");
     NOT_NULL(list_b, "intersection_list_id_genomes()");

@@ -2213,9 +2213,10 @@ extern "C" int bft_gpu_query_colors(bft_gpu* h, const uint8_t* kmers, uint64_t n
 
 // Bitmap form of the colour-set dictionary (one dword-aligned row per set), used by the colour-row queries when it stays
 // below 4 GiB; derived on the first such query of an image, on the handle's stream.
-static int ensure_cs_bitmaps(bft_gpu* h) {
+int bft_ensure_cs_bitmaps(bft_gpu* h) {
     if (h->cs_bm_tried) return 0;
     h->cs_bm_tried = true;
+    if (h->opt_no_cs_bitmaps) return 0;  // ("test_no_cs_bitmaps": as if the bitmaps passed 4 GiB)
     const uint64_t rowbytes = (h->im.nb_genomes + 7) / 8, nsets = h->n_sets;
     if (rowbytes && nsets && nsets * rowbytes <= (4ull << 30)) {
         const uint64_t stride = (rowbytes + 3) & ~3ull;  // dword-aligned dictionary rows (k_color_rows_bm)
@@ -2233,7 +2234,7 @@ static int ensure_cs_bitmaps(bft_gpu* h) {
 
 // d_rowidx: the row of every k-mer (scratch: overwritten with the colour-set ids when the bitmap dictionary is used)
 static int launch_color_rows(bft_gpu* h, uint32_t* d_rowidx, uint64_t n, uint32_t rowbytes, uint8_t* d_out, hipStream_t s, bool are_colorsets = false) {
-    CK(ensure_cs_bitmaps(h));
+    CK(bft_ensure_cs_bitmaps(h));
     hipEvent_t e0, e1;
     CK(bft_timing_begin(h, s, &e0, &e1));
     if (h->has_cs_bm) {
@@ -2307,7 +2308,7 @@ extern "C" int bft_gpu_query_color_rows_dev(bft_gpu* h, const void* d_kmers, uin
     if (n == 0 || rowbytes == 0) return BFT_GPU_OK;
     // with the bitmap dictionary the query kernel writes colour sets straight away (the k-mer hash holds them; bft_hit_out in the
     // walk): no row -> colour set pass
-    CK(ensure_cs_bitmaps(h));
+    CK(bft_ensure_cs_bitmaps(h));
     const bool direct = h->has_cs_bm;
     // rows of 16 bytes and up through the k-mer hash: lookup and rows in one launch (the scratch array stays unused)
     if (direct && rowbytes >= 16 && ((uintptr_t)d_rows & 15u) == 0 && h->im.kh_lines != nullptr && !h->opt_walk_hash && bft_kh_has_kernels(h->W, h->im.kh.S)) {
@@ -3102,6 +3103,15 @@ extern "C" int bft_gpu_set_option(bft_gpu* h, const char* name, int64_t value) {
             for (int i = 0; i < bft_gpu::KH_CTR_SLOTS; i++) v[i] = value == 3 ? 0ull : h->kh_ctr_base[i] - (value == 1 && h->kh_ctr_base[i] ? 1ull : 0ull);
             HIPCK(hipMemcpy(h->kh_ctr, v, sizeof(v), hipMemcpyHostToDevice));
         }
+    } else if (nm == "test_no_cs_bitmaps") {  // test hook (tests/test_gpu_setops.py): the bitmap form of the dictionary is not derived (what happens by itself
+        // where it would pass 4 GiB); one that exists is released, so the id lists serve the colour rows and the set operations from here on
+        ENTER(h);
+        CK(wait_foreign_stream(h));
+        HIPCK(hipStreamSynchronize(h->stream));
+        h->opt_no_cs_bitmaps = value != 0;
+        h->d_cs_bm.release();
+        h->has_cs_bm = false;
+        h->cs_bm_tried = false;
     } else if (nm == "composite_log") {  // 1 (default): one-word keys with room for an id are logged as composites; 0: always k-mers + ids (test hook: same image)
         if (h->log_n) return fail(BFT_GPU_E_STATE, "composite_log: the insertion log is not empty");
         h->opt_comp_log = value != 0;

@@ -1,6 +1,6 @@
 // bft_handle.h -- the handle behind the C-ABI (struct bft_gpu) and the host helpers every entry point needs, for the translation units that hold
 // entry points: bft_gpu.hip (which defines the helpers) and the analysis families bft_prefix.hip, bft_paths.hip, bft_components.hip, bft_pangenome.hip,
-// bft_subgraph.hip, bft_marking.hip.
+// bft_subgraph.hip, bft_marking.hip, bft_setops.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -144,6 +144,7 @@ struct bft_gpu {
     uint64_t n_f18 = 0, n_fent = 0;
     uint32_t opt_flat_min = BFT_TRESH_SUF_PREF;  // CCs with at least this many prefixes get the flat form ("flat_min")
     bool has_cs_bm = false, cs_bm_tried = false;
+    bool opt_no_cs_bitmaps = false; // test hook ("test_no_cs_bitmaps"): bft_ensure_cs_bitmaps declines, the id lists serve every consumer of the dictionary
     bool opt_no_composite = false;  // test hook ("build_composite" 0): the general sort + flag-array path also for ordered one-word keys
     uint32_t front_redone = 0;      // root-prefix buckets of the last build whose order check failed (bft_front.hip)
     int opt_msd = 1;                // "build_msd": root-prefix buckets + bucket sorts for 2^20 pairs and more (1), always (2: test hook), never (0)
@@ -215,6 +216,8 @@ struct bft_gpu {
     HandleScratch pg{"k-mer classes"};
     DevBuf pg_buf, pg_tmp;           // pan-genome k-mer classes (BftPgScratch, bft_pangenome.h) and their scan's temporary
     uint64_t pg_m = 0, pg_sets = 0;  // rows and colour sets pg_buf has room for
+    HandleScratch so{"colour-set algebra"};
+    DevBuf so_buf;                   // set operations over groups (BftSoScratch, bft_setops.h): colour set per k-mer, presence bits, accumulators, split list
     // Vertex marks (bft_marking.hip): on between bft_gpu_marks_begin and bft_gpu_marks_end; insertions and builds are refused meanwhile, so the rows
     // the flags are indexed by cannot move.
     bool marking = false;
@@ -250,6 +253,10 @@ bool bft_stream_capturing(hipStream_t s);
 int bft_note_foreign_stream(bft_gpu* h, hipStream_t s);
 // The log merged into the index; need_table = false: the caller is answered by the k-mer hash alone ("compact_table": the sorted table may be away)
 int bft_ensure_built(bft_gpu* h, bool need_table = true);
+// The bitmap form of the colour-set dictionary (d_cs_bm: one dword-aligned row per set behind CS_BM_SLACK zero bytes), derived on the first call per
+// image on the handle's stream (synchronises once); has_cs_bm stays false where it would pass 4 GiB or "test_no_cs_bitmaps" is set.
+#define CS_BM_SLACK 32u  // zero bytes in front of and behind the bitmap dictionary
+int bft_ensure_cs_bitmaps(bft_gpu* h);
 int bft_ensure_table(bft_gpu* h);  // "compact_table": the sorted table and the colour set per row, back from the k-mer hash (synchronises)
 
 // Timed launches ("timing"): a pair of pooled events around the kernel (no event is created on the launch path once the pool is warm).

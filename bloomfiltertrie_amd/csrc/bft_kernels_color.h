@@ -3,7 +3,7 @@
 // the host code there).
 #pragma once
 #include "bft_rows16.h"
-#define CS_BM_SLACK 32u  // zero bytes in front of and behind the bitmap dictionary (bft_gpu.hip, ensure_cs_bitmaps)
+// (CS_BM_SLACK, the zero bytes in front of and behind the bitmap dictionary: bft_handle.h)
 __global__ void k_color_counts(const uint32_t* __restrict__ rows, const uint32_t* __restrict__ tcol, const uint32_t* __restrict__ cs_off,
                                uint64_t n, uint64_t* __restrict__ counts) {
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {

@@ -17,7 +17,7 @@
  *     bft_gpu.h on bft_device_index(bft) -- that is the point of the GPU path;
  *   - insertions are collected on the GPU and the containers are rebuilt in bulk by the first query after them;
  *   - there is no CPU fallback: without a usable GPU every function reports the error and exits.
- * Not provided (outside the path): annotation set operations, prefix_matching_custom,
+ * Not provided (outside the path): prefix_matching_custom,
  * colour compression (write_BFT ignores compress_annotations and writes uncompressed annotations, which the reference loads).
  */
 #ifndef BFT_GPU_COMPAT_BFT_H
@@ -139,6 +139,25 @@ BFT_annotation* get_annotation(BFT_kmer* bft_kmer);
 bool presence_genome(uint32_t id_genome, BFT_annotation* bft_annot, BFT* bft);
 uint32_t* get_list_id_genomes(BFT_annotation* bft_annot, BFT* bft); /* [0] = count, then the sorted ids */
 uint32_t get_count_id_genomes(BFT_annotation* bft_annot, BFT* bft);
+/* include/bft.h:53-55, :100-110: the byte operators cmp_annots is given.  The reference declares them `inline` with an external definition in
+ * src/bft.c; `static inline` serves the same calls and needs none. */
+static inline uint8_t intersection_annots(const uint8_t a, const uint8_t b) { return a & b; }
+static inline uint8_t union_annots(const uint8_t a, const uint8_t b) { return a | b; }
+static inline uint8_t sym_difference_annots(const uint8_t a, const uint8_t b) { return a ^ b; }
+/* include/bft.h:112-114, src/bft.c:421-613: the set of genomes common to / held by any of / held by some but not all of nb_annotations annotations
+ * (BFT_annotation* each).  The annotations already are host bytes: they are decoded, combined and encoded on the host, and NO GPU call is made (for
+ * groups of k-mers use bft_gpu_combine_colors of bft_gpu.h on bft_device_index(bft): one call, one row per group).
+ * Result -- what cmp_annots returns (src/annotation.c:2358-2551): a malloc'd mode-0 bitmap of MAX(CEIL(nb_genomes + 2, 8), 1) bytes, genome g at bit
+ * g + 2, the two mode bits zero; size_annot is that length, annot_ext / annot_cplx are NULL; free it with free_BFT_annotation.
+ * Arguments: any annotation this library hands out -- modes 0/1/2 from get_annotation, mode 0 of any length from these functions (results nest); ids
+ * at or past bft->nb_genomes are dropped.  nb_annotations == 0 prints "<name>(): no annotations given as parameters.\n" and exits, a NULL annotation
+ * exits through the reference's ASSERT_NULL_PTR text.
+ * Two places where the reference's text is not reproduced: intersection_annotations with ONE argument never reads it and returns the empty set
+ * (src/bft.c:431-435) -- here it returns the argument's set; sym_difference_annotations with two or more arguments hands its va_list on as a
+ * variadic argument (:592-593), which is undefined -- here it is union minus intersection, what that code is written to compute (one argument: its set). */
+BFT_annotation* intersection_annotations(BFT* bft, uint32_t nb_annotations, ...);
+BFT_annotation* union_annotations(BFT* bft, uint32_t nb_annotations, ...);
+BFT_annotation* sym_difference_annotations(BFT* bft, uint32_t nb_annotations, ...);
 uint32_t* intersection_list_id_genomes(uint32_t* list_a, uint32_t* list_b);
 
 /* ---- sequence query (include/bft.h:127, src/bft.c:1241-1351) ---- */

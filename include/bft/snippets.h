@@ -14,8 +14,8 @@
  * extract_pangenome_kmers_to_disk in <bft/snippets_pangenome.h>.  This header includes both.
  *
  * Not provided: the per-k-mer callbacks extract_simple_paths and extract_core_simple_paths (vertex marking, which they need, is provided by
- * <bft/bft.h>; their reference text has undefined behaviour), and the annotation set operations intersection_annotations /
- * union_annotations / sym_difference_annotations.
+ * <bft/bft.h>; their reference text has undefined behaviour).  The annotation set operations intersection_annotations /
+ * union_annotations / sym_difference_annotations are declared in <bft/bft.h>.
  */
 #ifndef BFT_GPU_COMPAT_SNIPPETS_H
 #define BFT_GPU_COMPAT_SNIPPETS_H

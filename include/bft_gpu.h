@@ -222,6 +222,8 @@ int bft_gpu_footprint(bft_gpu* h, uint64_t* out, int n_out);
  *   instruction in lane order, 1 = wavefront ballots, stable by construction; same image), "reserve_pairs" (room in the insertion log for this many pending (k-mer, genome)
  *   pairs, so that a series of insert calls never re-allocates it), "flush_pairs" (the log is merged into the index before it holds this many pairs:
  *   2^30 by default, 1024..2^30).
+ * "test_no_cs_bitmaps" (test hook; 1: the bitmap form of the colour-set dictionary is not derived and one that exists is released -- what happens by itself where
+ *   it would pass 4 GiB --, so the colour rows and bft_gpu_combine_* read the sorted id lists; 0: it is derived again by the next call that wants it; same answers).
  * "timing" (0/1: record HIP events around query kernels; off until this option or the first bft_gpu_kernel_time call turns it on).
  * "build_stages" (0/1: bft_gpu_build records GPU time and algorithmic bytes per stage, see bft_gpu_build_stages). */
 int bft_gpu_set_option(bft_gpu* h, const char* name, int64_t value);
@@ -376,6 +378,47 @@ int bft_gpu_kmers_by_count_dev(bft_gpu* h, uint32_t min_count, uint32_t max_coun
 int bft_gpu_pangenome_stats(bft_gpu* h, uint64_t* spectrum, uint64_t* genome_total, uint64_t* genome_private, uint32_t cap);
 /* The same into device buffers (uint64) on hip_stream (NULL = the handle's stream), without host synchronisation.  Not inside a graph capture. */
 int bft_gpu_pangenome_stats_dev(bft_gpu* h, void* d_spectrum, void* d_genome_total, void* d_genome_private, uint32_t cap, void* hip_stream);
+
+/* Colour-set algebra over groups of k-mers: intersection_annotations / union_annotations / sym_difference_annotations (reference include/bft.h:112-114,
+ * src/bft.c:421-613) for a batch of groups, reduced on the GPU: one row per GROUP crosses to the caller, not one per k-mer (the route through
+ * bft_gpu_query_color_rows and a host loop).  Group g is the k-mers group_off[g] .. group_off[g + 1] of the batch (packed, the layout of every batch
+ * here): nb_groups + 1 offsets, as seq_off of bft_gpu_query_sequences; groups may leave k-mers between them uncovered, and those take part in no result.
+ *   op       BFT_GPU_SETOP_AND: the genomes that hold every member; _OR: those that hold at least one; _SYMDIFF: OR minus AND -- what src/bft.c:592-601
+ *            computes; a group of one member gives that member's set.
+ *   absent   skip_absent == 0: a k-mer the index does not store is the empty set (an AND over a group with an absent member is empty);
+ *            skip_absent != 0: it is left out of the group.
+ *   rows     nb_groups x CEIL(nb_genomes/8) bytes in the bit layout of bft_gpu_query_color_rows; the bits at and past nb_genomes are zero.
+ *   counts   counts[g] = the number of genomes in row g.     found   found[g] = the members of group g that the index stores.
+ *            Each of the three may be NULL; counts alone is a valid call, and then no row is written anywhere.
+ *   empty    a group without members gives a zero row and count 0 under every op; so does a group without a found member under skip_absent.
+ *   errors   host forms: an unknown op, offsets that decrease and group_off[nb_groups] > nb_kmers are BFT_GPU_E_ARG, and nothing is written.  The
+ *            device forms cannot look at the offsets: a group whose end lies before its start or past nb_kmers is EMPTY there; nothing is ever read
+ *            outside the batch or written outside the three outputs.  nb_genomes == 0: nothing is written to rows, counts and found are zero.
+ * The colour set of a k-mer comes out of the line of the k-mer hash that answers presence ("compact_table" stays in force: the sorted table is not brought
+ * back); an image without the k-mer hash ("kmer_hash" 0) and one with "walk_hash" 1 give the same answers through the container walk.  The dictionary is
+ * read in its bitmap form (derived by the first colour-row query or the first call here) or, where that would pass 4 GiB, as its sorted id lists
+ * ("test_no_cs_bitmaps" 1, a test hook of bft_gpu_set_option, forces the second; same bytes).  A dictionary row is fetched once per run of equal colour
+ * sets, not per member; groups of any size are served (pairs share a wavefront, a read takes one, a group of millions is split over workgroups and met
+ * in memory by 32-bit atomics).  Pending insertions are built first.  Launches are counted in bft_gpu_kernel_time; with "build_stages" on, the steps are
+ * the stages bft_gpu_build_stages reports.  Scratch (4 bytes per k-mer, ~2 rows per group) belongs to the handle and is shared with no other query
+ * family: calls on different streams are serialised by the library, and interleave with every other call on the handle.
+ * Host forms stage the whole batch through device blocks of the call's own and synchronise.  The *_dev forms take device buffers (d_group_off: uint64,
+ * d_counts / d_found: uint32, d_rows at any alignment), enqueue on hip_stream (NULL = the handle's stream) and do not synchronise.  Not inside a graph
+ * capture (BFT_GPU_E_ARG). */
+#define BFT_GPU_SETOP_AND     0   /* genomes that hold every member of the group */
+#define BFT_GPU_SETOP_OR      1   /* genomes that hold at least one              */
+#define BFT_GPU_SETOP_SYMDIFF 2   /* OR minus AND: what src/bft.c:592-601 computes; a group of one member gives that member's set */
+int bft_gpu_combine_colors(bft_gpu* h, const uint8_t* kmers, uint64_t nb_kmers, const uint64_t* group_off, uint64_t nb_groups, int op, int skip_absent,
+                           uint8_t* rows, uint32_t* counts, uint32_t* found);
+int bft_gpu_combine_colors_dev(bft_gpu* h, const void* d_kmers, uint64_t nb_kmers, const void* d_group_off, uint64_t nb_groups, int op, int skip_absent,
+                               void* d_rows, void* d_counts, void* d_found, void* hip_stream);
+/* The same over colour-set ids (what bft_gpu_query_rows, bft_gpu_extract and bft_gpu_query_prefixes hand out) instead of k-mers: nb ids, grouped by
+ * group_off.  An id equal to 0xFFFFFFFF (what bft_gpu_query_rows writes for an absent k-mer) plays the absent k-mer's role with skip_absent == 0; any
+ * other id outside the dictionary is BFT_GPU_E_ARG in the host form and the empty set in the device form.  No lookup: the ids are the members. */
+int bft_gpu_combine_colorsets(bft_gpu* h, const uint32_t* colorsets, uint64_t nb, const uint64_t* group_off, uint64_t nb_groups, int op, uint8_t* rows,
+                              uint32_t* counts);
+int bft_gpu_combine_colorsets_dev(bft_gpu* h, const void* d_colorsets, uint64_t nb, const void* d_group_off, uint64_t nb_groups, int op, void* d_rows,
+                                  void* d_counts, void* hip_stream);
 
 /* Vertex marking: set_marking / unset_marking / set_flag_kmer / get_flag_kmer (reference include/bft.h:143-146, src/bft.c:686-765) for batches, and
  * what the reference's traversals do with the marks (BFS / DFS / BFS_subgraph / DFS_subgraph, src/snippets.c:605-812) as ONE call, bft_gpu_marks_reach.
