@@ -56,6 +56,7 @@ SIGNATURES = {
     "bft_gpu_query_prefixes_dev": (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P, _P, _P, C.c_uint64, _P, _P]),
     "bft_gpu_subgraph": (C.c_int, [_P, _P, C.c_uint64, C.c_int, C.POINTER(C.c_uint64), C.POINTER(_P)]),
     "bft_gpu_subgraph_dev": (C.c_int, [_P, _P, C.c_uint64, C.c_int, C.POINTER(C.c_uint64), C.POINTER(_P), _P]),
+    "bft_gpu_merge": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(_P)]),
     "bft_gpu_simple_paths": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "bft_gpu_simple_paths_dev": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_uint64, C.c_uint64, _P, _P]),
     "bft_gpu_components": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64, _P, C.c_uint64, _P]),
@@ -136,6 +137,9 @@ def load():
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+MERGE_APPEND = 0xFFFFFFFF  # BFT_GPU_MERGE_APPEND (include/bft_gpu.h; tests/test_union_cases_host.py holds the two together)
 
 
 class BFTError(RuntimeError):

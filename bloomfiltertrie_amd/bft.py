@@ -372,6 +372,16 @@ class BFT:
                                                   C.c_void_p(stream or 0)))
         return BFT(self.k, device=self.device, _handle=h), int(absent.value)
 
+    def merge(self, other, id_base=None):
+        """merging_BFT (include/merge.h:14) on the GPU: a new BFT holding every k-mer of this index and of `other`; genome g of `other` becomes genome
+        id_base + g, a k-mer of both has the union of its two colour sets.  id_base None appends (this index's genome count); one below that count is
+        the reference's overlap of the last and the first genome; 0 means the same genomes.  Both sources stay as they are (bft_gpu_merge)."""
+        if id_base is None:
+            id_base = _lib.MERGE_APPEND  # the count once pending insertions are built
+        h = C.c_void_p()
+        _lib.check(self._lib.bft_gpu_merge(self._h, other._h, int(id_base), C.byref(h)))
+        return BFT(self.k, device=self.device, _handle=h)
+
     def simple_paths(self, min_shared=0):
         """extract_simple_paths_to_disk / extract_simple_core_paths_to_disk (reference snippets.h, src/snippets.c:115-603) on the GPU: the simple
         (non-branching) paths of the index as ASCII strings, in ascending row of their first k-mer.  min_shared = t: only k-mers of t genomes

@@ -12,6 +12,7 @@
 #include <string.h>
 
 #include "../../include/bft/bft.h"
+#include "../../include/bft/merge.h"
 #include "../../include/bft/snippets.h"
 
 #define DIE(...) do { fprintf(stderr, __VA_ARGS__); exit(EXIT_FAILURE); } while (0)
@@ -771,6 +772,28 @@ BFT* load_BFT(char* filename) {
         push_name(bft, name);
     }
     return bft;
+}
+
+/* ---------------------------------------------------------------- merge (<bft/merge.h>) */
+
+/* include/merge.h:14.  The second graph's genomes follow the first graph's; they start on its last one when that name is the second graph's first
+ * (are_genomes_ids_overlapping, include/Node.h:147-155).  One bft_gpu_merge call instead of an insertion per k-mer of the second graph. */
+void merging_BFT(char* prefix_bft1, char* prefix_bft2, char* output_prefix, int cut_lvl, bool packed_in_subtries) {
+    (void)cut_lvl;
+    (void)packed_in_subtries;
+    NOT_NULL(prefix_bft1, "merging_BFT()");
+    NOT_NULL(prefix_bft2, "merging_BFT()");
+    NOT_NULL(output_prefix, "merging_BFT()");
+    BFT* bft1 = load_BFT(prefix_bft1);
+    BFT* bft2 = load_BFT(prefix_bft2);
+    uint32_t id_base = (uint32_t)bft1->nb_genomes;
+    if (bft1->nb_genomes > 0 && bft2->nb_genomes > 0 && strcmp(bft1->filenames[bft1->nb_genomes - 1], bft2->filenames[0]) == 0) id_base--;
+    bft_gpu* g = NULL;
+    ck(bft_gpu_merge(bft1->gpu, bft2->gpu, id_base, &g), "merging_BFT()");
+    ck(bft_gpu_write_bft(g, output_prefix), "merging_BFT()");
+    bft_gpu_free(g);
+    free_cdbg(bft2);
+    free_cdbg(bft1);
 }
 
 /* ---------------------------------------------------------------- simple paths (<bft/snippets.h>) */

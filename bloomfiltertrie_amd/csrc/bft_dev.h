@@ -186,7 +186,14 @@ struct BftRunOut {
     DevBuf tk, tcol, cs_off, cs_ids;
     uint64_t n = 0, n_sets = 0, n_ids = 0;
 };
-int bft_merge_runs(int W, const BftRun& a, const BftRun& b, hipStream_t s, BftRunOut& out);
+// How the k-mers are placed.  An insertion build searches every run row in the index (the default: a run is small beside its index); a merge of two
+// indexes (bft_union.hip) may stream both tables instead (coranked), has its launches timed on a handle and records its stages ("build_stages").
+struct BftMergeOpt {
+    bool coranked = false;
+    bool stages = false;
+    bft_gpu* timed = nullptr;
+};
+int bft_merge_runs(int W, const BftRun& a, const BftRun& b, hipStream_t s, BftRunOut& out, const BftMergeOpt& opt = BftMergeOpt());
 int bft_count_pairs(const uint32_t* d_tcol, uint64_t n, const uint32_t* d_cs_off, hipStream_t s, uint64_t* total);
 
 // The build's front end behind the root-prefix split (bft_front.hip): bucket-wise sort of the composites c = T << gb | genome on the

@@ -982,6 +982,7 @@ static void drop_table(bft_gpu* h) {
     h->im.tcol = nullptr;
     h->info[12] = image_bytes(h);
 }
+void bft_drop_table(bft_gpu* h) { drop_table(h); }
 int bft_ensure_table(bft_gpu* h) {
     if (!h->table_dropped) return 0;
     CK(wait_foreign_stream(h));
@@ -3118,6 +3119,9 @@ extern "C" int bft_gpu_set_option(bft_gpu* h, const char* name, int64_t value) {
         if (h->log_cap) { h->log_k.release(); h->log_g.release(); h->log_cap = 0; }  // (a reserved, empty log: its format is decided again)
     } else if (nm == "build_stages") {
         h->opt_build_stages = value != 0;
+    } else if (nm == "merge_place") {  // bft_gpu_merge(h, other, ...): 1 = co-ranked placement, 0 = the search of an insertion build (same image)
+        if (value != 0 && value != 1) return fail(BFT_GPU_E_ARG, "merge_place must be 0 or 1");
+        h->opt_merge_place = (int)value;
     } else if (nm == "flat_min") {
         if (value < 1 || value > 65536) return fail(BFT_GPU_E_ARG, "flat_min must be in [1,65536]");
         h->opt_flat_min = (uint32_t)value;

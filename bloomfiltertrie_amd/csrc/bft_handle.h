@@ -1,6 +1,6 @@
 // bft_handle.h -- the handle behind the C-ABI (struct bft_gpu) and the host helpers every entry point needs, for the translation units that hold
 // entry points: bft_gpu.hip (which defines the helpers) and the analysis families bft_prefix.hip, bft_paths.hip, bft_components.hip, bft_pangenome.hip,
-// bft_subgraph.hip, bft_marking.hip, bft_setops.hip.
+// bft_subgraph.hip, bft_marking.hip, bft_setops.hip, bft_union.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -231,6 +231,9 @@ struct bft_gpu {
     std::vector<uint32_t> mk_forest_ids;
 
     bool inject_build_failure = false;  // test hook: the next bft_gpu_build fails right before its commit point (one shot)
+    int opt_merge_place = 1;            // "merge_place": how bft_gpu_merge places the k-mers of (this, other): 1 = co-ranked tiles of both tables (bft_union.hip),
+                                        // 0 = every row of `other` searched in this one's table, as an insertion build does
+                                        // (the default follows tools/bench_merge.py's placement stages at the 50 / 50 split: DESIGN 16)
     bool opt_build_stages = false;      // "build_stages": the next builds record GPU time and bytes per stage (bft_gpu_build_stages)
     struct Stage { std::string name; double ms, bytes; };
     std::vector<Stage> stages;          // of the last build
@@ -258,6 +261,7 @@ int bft_ensure_built(bft_gpu* h, bool need_table = true);
 #define CS_BM_SLACK 32u  // zero bytes in front of and behind the bitmap dictionary
 int bft_ensure_cs_bitmaps(bft_gpu* h);
 int bft_ensure_table(bft_gpu* h);  // "compact_table": the sorted table and the colour set per row, back from the k-mer hash (synchronises)
+void bft_drop_table(bft_gpu* h);   // "compact_table": dropped again where the option and the k-mer hash allow it (nothing may still be reading it)
 
 // Timed launches ("timing"): a pair of pooled events around the kernel (no event is created on the launch path once the pool is warm).
 int bft_timing_begin(bft_gpu* h, hipStream_t s, hipEvent_t* e0, hipEvent_t* e1);

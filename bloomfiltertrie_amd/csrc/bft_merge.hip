@@ -18,6 +18,7 @@
 #include "bft_image.h"
 #include "bft_scan.h"
 #include "bft_sort.h"
+#include "bft_union.h"
 #include "bft_walk.h"
 
 #define MBLK 256
@@ -249,11 +250,12 @@ __global__ void k_sum32(const uint32_t* __restrict__ v, uint64_t n, unsigned lon
     if ((threadIdx.x & 63u) == 0 && acc) atomicAdd(total, acc);
 }
 
-template <int W>
-int merge_w(const BftRun& a, const BftRun& b, hipStream_t s, BftRunOut& out) {
-    const uint64_t n_a = a.n, n_b = b.n;
 #define G(n) dim3(bft_grid_for(((uint64_t)(n) + MBLK - 1) / MBLK)), dim3(MBLK), 0, s
-    Scan32 scan(s);
+// Placement by search: every row of b looks its place up in a.  Leaves the merged keys in out.tk and, per merged row, the colour set of a's row (pa)
+// and of b's row (pb; none: NONE32), per row of b its merged row (orow).
+template <int W>
+int place_search(const BftRun& a, const BftRun& b, hipStream_t s, Scan32& scan, BftRunOut& out, DevBuf& pa, DevBuf& pb, DevBuf& orow, uint64_t* n_out) {
+    const uint64_t n_a = a.n, n_b = b.n;
     DevBuf pos, ins, pex, cnt, qex;
     CK(pos.alloc(n_b * 4));
     CK(ins.alloc(n_b * 4));
@@ -270,7 +272,6 @@ int merge_w(const BftRun& a, const BftRun& b, hipStream_t s, BftRunOut& out) {
     TRACE_STAGE(s, "  merge: counts + scans");
     const uint64_t n_o = n_a + n_ins;
     if (n_o >= 0x7FFFFFFFull) return bft_fail(BFT_GPU_E_LIMIT, "more than 2^31-1 distinct k-mers");
-    DevBuf pa, pb, orow;
     CK(out.tk.alloc(n_o * W * 8));
     CK(out.tcol.alloc(n_o * 4));
     CK(pa.alloc(n_o * 4));
@@ -284,6 +285,26 @@ int merge_w(const BftRun& a, const BftRun& b, hipStream_t s, BftRunOut& out) {
     HIPCK(hipGetLastError());
     TRACE_STAGE(s, "  merge: scatter of both sides");
     pos.release(); ins.release(); pex.release(); cnt.release(); qex.release();
+    *n_out = n_o;
+    return 0;
+}
+
+template <int W>
+int merge_w(const BftRun& a, const BftRun& b, hipStream_t s, BftRunOut& out, const BftMergeOpt& opt) {
+    const uint64_t n_a = a.n, n_b = b.n;
+    Scan32 scan(s);
+    DevBuf pa, pb, orow;
+    uint64_t n_o = 0;
+    if (opt.coranked) {
+        CK(bft_union_place(W, a, b, s, opt.timed, out.tk, pa, pb, orow, &n_o));
+        CK(out.tcol.alloc(n_o * 4));
+        // both tables read by the count and by the emit, the merged rows and the three maps written
+        if (opt.stages) bft_stage("merge: k-mers placed (co-ranked)", (double)(n_a + n_b) * (16.0 * W + 4) + (double)n_o * (8.0 * W + 8) + (double)n_b * 4, s);
+    } else {
+        CK(place_search<W>(a, b, s, scan, out, pa, pb, orow, &n_o));
+        // b and its maps read, a and its scans streamed, the merged rows and the three maps written (the search's gathers in a are not counted)
+        if (opt.stages) bft_stage("merge: k-mers placed (search)", (double)n_b * (8.0 * W + 24) + (double)n_a * (8.0 * W + 16) + (double)n_o * (8.0 * W + 12), s);
+    }
     bft_trace_mark("  merge: k-mers placed");
 
     // ---- colour sets: U = old sets still on a row of their own + the unique (old | none, run) combinations ----
@@ -351,19 +372,20 @@ int merge_w(const BftRun& a, const BftRun& b, hipStream_t s, BftRunOut& out) {
     hipLaunchKernelGGL(k_tcol_new, G(n_b), orow.as<uint32_t>(), urow.as<uint32_t>(), n_b, tcol_u.as<uint32_t>(), out.tcol.as<uint32_t>());
     HIPCK(hipGetLastError());
     HIPCK(hipStreamSynchronize(s));
+    if (opt.stages) bft_stage("merge: colour sets united and interned", (double)n_b * 40 + (double)n_o * 16 + (double)out.n_ids * 8, s);
     out.n = n_o;
-#undef G
     return 0;
 }
+#undef G
 
 }  // namespace
 
-int bft_merge_runs(int W, const BftRun& a, const BftRun& b, hipStream_t s, BftRunOut& out) {
+int bft_merge_runs(int W, const BftRun& a, const BftRun& b, hipStream_t s, BftRunOut& out, const BftMergeOpt& opt) {
     switch (W) {
-    case 1: return merge_w<1>(a, b, s, out);
-    case 2: return merge_w<2>(a, b, s, out);
-    case 3: return merge_w<3>(a, b, s, out);
-    default: return merge_w<4>(a, b, s, out);
+    case 1: return merge_w<1>(a, b, s, out, opt);
+    case 2: return merge_w<2>(a, b, s, out, opt);
+    case 3: return merge_w<3>(a, b, s, out, opt);
+    default: return merge_w<4>(a, b, s, out, opt);
     }
 }
 

@@ -17,6 +17,7 @@
  *     bft_gpu.h on bft_device_index(bft) -- that is the point of the GPU path;
  *   - insertions are collected on the GPU and the containers are rebuilt in bulk by the first query after them;
  *   - there is no CPU fallback: without a usable GPU every function reports the error and exits.
+ * merging_BFT (the reference's include/merge.h) is in <bft/merge.h>.
  * Not provided (outside the path): prefix_matching_custom,
  * colour compression (write_BFT ignores compress_annotations and writes uncompressed annotations, which the reference loads).
  */

@@ -302,6 +302,25 @@ int bft_gpu_subgraph(bft_gpu* src, const uint8_t* kmers, uint64_t nb_kmers, int 
 int bft_gpu_subgraph_dev(bft_gpu* src, const void* d_kmers, uint64_t nb_kmers, int colors, uint64_t* n_absent, bft_gpu** out,
                          void* hip_stream);
 
+/* merging_BFT (include/merge.h:14; body commented out in src/merge.c): a new index holding every k-mer of a and of b;
+ * genome g of b becomes genome id_base + g, a k-mer of both has the union of its two sets.
+ *   id_base   at most a's number of genomes (bft_gpu_info [11] once a's pending insertions are built; beyond it: BFT_GPU_E_ARG).  Equal to it -- or
+ *             BFT_GPU_MERGE_APPEND, which stands for it -- b's genomes are appended; one below it, b's first genome is a's last (the reference's
+ *             are_genomes_ids_overlapping, include/Node.h:147-155); 0: the same genomes, their k-mers split between the two handles.  An id that
+ *             would pass 2^32 is BFT_GPU_E_LIMIT.
+ *   sources   same k and same device (BFT_GPU_E_ARG otherwise: bft_gpu_image_pack / bft_gpu_image_unpack move a handle to another device); the Bloom
+ *             seeds may differ.  a == b is allowed (with id_base 0 the result is a's own image).  Pending insertions of either are built first; a
+ *             sorted table that "compact_table" dropped comes back for the call and is dropped again before it returns.  Otherwise both are
+ *             untouched, their answers unchanged, and they share no device buffer with *out: any of the three may be freed first.
+ *   *out      a full handle with a's seeds: max(a's genomes, id_base + b's genomes) genomes, a's names and then b's for the ids beyond a's genomes; options at
+ *             the library defaults ("build_stages" follows a: the stages of the call are the new handle's; the new launches are counted in a's
+ *             bft_gpu_kernel_time); no marking.  At most 2^31 - 1 distinct k-mers in the result (BFT_GPU_E_LIMIT).
+ *   "merge_place" on a: 1 (default; DESIGN 16 says on what evidence) = both sorted tables streamed and co-ranked tile by tile, 0 = every k-mer of b searched in a's table, as an
+ *             insertion build places its run; the image is the same.
+ * Synchronous: the handle is whole when the call returns.  Not while either source's stream is being captured (BFT_GPU_E_ARG). */
+#define BFT_GPU_MERGE_APPEND 0xFFFFFFFFu
+int bft_gpu_merge(bft_gpu* a, bft_gpu* b, uint32_t id_base, bft_gpu** out);
+
 /* Simple (non-branching) paths, or unitigs: extract_simple_paths_to_disk(bft, filename) and extract_simple_core_paths_to_disk(bft, core_ratio,
  * filename) (reference snippets.h, src/snippets.c:115-603) without the disk, for a threshold t = min_shared on shared genomes (0: plain simple
  * paths; the core form passes (int)(core_ratio * nb_genomes)).
