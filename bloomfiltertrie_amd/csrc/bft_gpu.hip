@@ -2241,30 +2241,11 @@ static int launch_color_rows(bft_gpu* h, uint32_t* d_rowidx, uint64_t n, uint32_
     if (h->has_cs_bm) {
         if (!are_colorsets)
             hipLaunchKernelGGL(k_row_colorsets, dim3(grid_for((n + 255) / 256)), dim3(256), 0, s, d_rowidx, h->im.tcol, n, d_rowidx);  // row -> colour set, in place
-        // tiles of ~32 KiB of output (a multiple of 4 k-mers: tiles start dword aligned); magic number of the division by rowbytes
-        // (round-up method, exact on u32)
         // (16-byte rows and up, 16-byte aligned output: the 16-bytes-per-lane kernel, whose tiles are a multiple of 16 k-mers)
         const bool wide16 = rowbytes >= 16 && ((uintptr_t)d_out & 15u) == 0;
-        uint32_t tile_rows = std::min<uint32_t>(CR_MAX_TILE_ROWS, std::max<uint32_t>(4u, ((32768u / rowbytes) + 3u) & ~3u));
-        if (wide16) {
-            // tiles of the 16-byte kernel belong to wavefronts, which answer 64 x CR16_UNROLL chunks of 16 bytes per turn: among the tiles of
-            // 16..64 KiB of output (a multiple of 16 k-mers, at most CR16_WAVE_ROWS) the one whose last turn is the fullest
-            const uint32_t per_turn = 64u * CR16_UNROLL;
-            double best = -1.0;
-            tile_rows = 16u;
-            for (uint32_t tr = 16u; tr <= CR16_WAVE_ROWS; tr += 16u) {
-                const uint64_t bytes = (uint64_t)tr * rowbytes;
-                // (tiles of 2-4, 4-8, 8-16 and 128-256 KiB were measured on config 5: 0.29-0.32 ms per GB written, no better than these)
-                if (bytes > (64u << 10) && best >= 0.0) break;
-                if (bytes < (16u << 10) && tr + 16u <= CR16_WAVE_ROWS && (uint64_t)(tr + 16u) * rowbytes <= (64u << 10)) continue;
-                const uint64_t nch = (bytes + 15u) / 16u, turns = (nch + per_turn - 1) / per_turn;
-                const double eff = (double)nch / (double)(turns * per_turn);
-                if (eff >= best) { best = eff; tile_rows = tr; }
-            }
-        }
-        uint32_t div_l = 0;
-        while ((1ull << div_l) < rowbytes) div_l++;
-        const uint32_t div_m = div_l ? (uint32_t)(((1ull << 32) * ((1ull << div_l) - rowbytes)) / rowbytes + 1ull) : 0u;
+        // the tile (a multiple of 4 / 16 k-mers) and the magic number of the division by rowbytes: bft_color_plan.h
+        const BftColorRowsPlan plan = bft_color_rows_plan(rowbytes, wide16 ? BFT_ROWS_FORM_16 : BFT_ROWS_FORM_DWORD);
+        const uint32_t tile_rows = plan.tile_rows, div_m = plan.div_m, div_l = plan.div_l;
         const uint64_t tiles = (n + tile_rows - 1) / tile_rows;
         dim3 cgrid((unsigned)std::min<uint64_t>(tiles, 256ull * 8));
         if (wide16) {
@@ -2772,6 +2753,21 @@ extern "C" int bft_gpu_debug_get_array(bft_gpu* h, const char* name, void* out, 
             return BFT_GPU_OK;
         }
     return fail(BFT_GPU_E_ARG, "unknown array");
+}
+
+// Test hook (tests/test_colour_cases_host.py, tests/test_gpu_colour_retrieval.py): the tile and the division constants the colour-row kernels
+// are launched with for rows of `rowbytes` bytes (bft_color_plan.h).  form 0: the dword kernels (k_color_rows_bm<false>, <true>), 1: the 16-byte
+// kernel (k_color_rows_bm16), 2: the row kernel of the k-mer hash (k_color_rows_kh); 1 and 2 serve rows of 16 bytes and up.  out: tile_rows, div_m,
+// div_l.  No handle, no HIP call.
+extern "C" int bft_gpu_debug_color_rows_plan(uint32_t rowbytes, int form, uint32_t out[3]) {
+    if (!out) return fail(BFT_GPU_E_ARG, "NULL argument");
+    if (form < BFT_ROWS_FORM_DWORD || form > BFT_ROWS_FORM_KH) return fail(BFT_GPU_E_ARG, "form must be 0, 1 or 2");
+    if (rowbytes == 0 || (form != BFT_ROWS_FORM_DWORD && rowbytes < 16)) return fail(BFT_GPU_E_ARG, "no such kernel for rows of this width");
+    const BftColorRowsPlan plan = bft_color_rows_plan(rowbytes, form);
+    out[0] = plan.tile_rows;
+    out[1] = plan.div_m;
+    out[2] = plan.div_l;
+    return BFT_GPU_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

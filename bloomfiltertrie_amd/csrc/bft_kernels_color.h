@@ -1,34 +1,9 @@
-// bft_kernels_color.h -- colour-set retrieval: id lists (k_color_counts / k_color_fill), bitmap dictionary and fixed-width rows (k_cs_bitmaps, k_color_rows_bm, k_color_rows), k_row_colorsets
+// bft_kernels_color.h -- colour-set retrieval: id lists (k_color_fill_cs), bitmap dictionary and fixed-width rows (k_cs_bitmaps, k_color_rows_bm, k_color_rows_bm16, k_color_rows), k_row_colorsets
 // Device code of libbft_gpu.so, included by bft_gpu.hip only (one translation unit: the kernels are templates launched from
 // the host code there).
 #pragma once
 #include "bft_rows16.h"
 // (CS_BM_SLACK, the zero bytes in front of and behind the bitmap dictionary: bft_handle.h)
-__global__ void k_color_counts(const uint32_t* __restrict__ rows, const uint32_t* __restrict__ tcol, const uint32_t* __restrict__ cs_off,
-                               uint64_t n, uint64_t* __restrict__ counts) {
-    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t r = rows[i];
-        uint64_t c = 0;
-        if (r != BFT_ABSENT_ROW) {
-            const uint32_t cs = tcol[r];
-            c = cs_off[cs + 1] - cs_off[cs];
-        }
-        counts[i] = c;
-    }
-}
-
-__global__ void k_color_fill(const uint32_t* __restrict__ rows, const uint32_t* __restrict__ tcol, const uint32_t* __restrict__ cs_off,
-                             const void* __restrict__ cs_ids, uint32_t cs_w, const uint64_t* __restrict__ offsets, uint64_t n, uint32_t* __restrict__ ids) {
-    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t r = rows[i];
-        if (r == BFT_ABSENT_ROW) continue;
-        const uint32_t cs = tcol[r];
-        const uint32_t a = cs_off[cs], b = cs_off[cs + 1];
-        uint64_t o = offsets[i];
-        for (uint32_t q = a; q < b; q++) ids[o++] = bft_cs_id_at(cs_ids, cs_w, q);
-    }
-}
-
 // ---- id lists out of colour-set ids (what the k-mer hash hands out with emit_cs: no row, no sorted table) ----
 // length of k-mer i's id list as the input "iterator" of the offsets' scan (entry n: 0, so that offsets[n] = the total)
 struct BftCsLen {
@@ -136,7 +111,7 @@ __device__ __forceinline__ uint32_t color_dword_cs(const uint32_t* cs, const uin
 // The first version resolved row -> colour set -> dictionary row per output DWORD (three dependent loads per 4 bytes) and was
 // latency-bound at 1.2 TB/s written; dwords that straddle two rows (rowbytes % 4 != 0) go through color_dword.
 #define CR_UNROLL 8
-#define CR_MAX_TILE_ROWS 2048
+// (CR_MAX_TILE_ROWS, the most k-mers of a tile: bft_color_plan.h, with the rule that picks the tile)
 // WIDE: rowbytes >= 4 -- an output dword touches at most two rows, handled without a branch (the second row's first dword is
 // loaded only by the lanes that straddle).  Rows of 1-3 bytes (<= 24 genomes) take the generic per-byte path.
 // The straddling dwords matter: with 250-byte rows one lane in 62 straddles, i.e. nearly every wavefront holds one, and a

@@ -113,10 +113,7 @@ __global__ __launch_bounds__(BFT_KH_BLOCK) void k_query_kh(BftImage im, const ui
 // tiles belong to wavefronts as in k_color_rows_bm16 (bft_kernels_color.h), but the wavefront looks its tile's k-mers up itself -- 64 at a
 // time, the lookup of k_query_kh -- and keeps their dictionary rows in its LDS slice; nothing but the presence words and the rows is
 // written.  Round 5 ran the lookup as its own launch, writing a colour-set id per k-mer that the row kernel read back.
-// tile_rows: a multiple of 64 (a presence word per lookup round; tiles start 16-byte aligned), at most BFT_KH_ROWS_TILE.
-#ifndef BFT_KH_ROWS_TILE
-#define BFT_KH_ROWS_TILE 256u
-#endif
+// tile_rows: a multiple of 64 (a presence word per lookup round; tiles start 16-byte aligned), at most BFT_KH_ROWS_TILE (bft_color_plan.h).
 template <int W, int S>
 __global__ __launch_bounds__(256) void k_color_rows_kh(BftImage im, const uint8_t* __restrict__ packed, uint64_t n, int B, uint64_t* __restrict__ bits64,
                                                        const uint8_t* __restrict__ bm, uint32_t stride, uint32_t rowbytes, uint32_t tile_rows, uint32_t div_m, uint32_t div_l,
@@ -844,14 +841,8 @@ static void kh_color_rows_launch(const BftImage& im, const uint8_t* d_kmers, uin
 // dictionary (rows of `stride` bytes, slack on either side: ensure_cs_bitmaps)
 int bft_kh_color_rows(const BftImage& im, const uint8_t* d_kmers, uint64_t n, int rec, uint64_t* d_bits64, const uint8_t* bm, uint32_t stride, uint32_t rowbytes, uint8_t* d_out,
                       int device, hipStream_t s) {
-    // tiles of about 16 KiB of output, a multiple of 64 k-mers.  (Config 5, 250-byte rows, 4x10^6 k-mers: tiles of 64 / 128 / 256 k-mers at 4, 5, 6
-    // workgroups per CU all take 0.37-0.40 ms, the smallest tiles and the most workgroups the least -- the launch costs what the lookups and the
-    // rows cost one after the other, whichever way they are interleaved: DESIGN.md.)
-    const uint32_t tile_rows = std::max(64u, std::min(BFT_KH_ROWS_TILE, ((16u << 10) / rowbytes) & ~63u));
-    uint32_t div_l = 0;
-    while ((1ull << div_l) < rowbytes) div_l++;
-    const uint32_t div_m = (uint32_t)(((1ull << 32) * ((1ull << div_l) - rowbytes)) / rowbytes + 1ull);
-    KH_DISPATCH(im.W, (int)im.kh.S, (kh_color_rows_launch<KW, KS>(im, d_kmers, n, rec, d_bits64, bm, stride, rowbytes, tile_rows, div_m, div_l, d_out, device, s)));
+    const BftColorRowsPlan plan = bft_color_rows_plan(rowbytes, BFT_ROWS_FORM_KH);  // (tiles of about 16 KiB of output, a multiple of 64 k-mers: bft_color_plan.h)
+    KH_DISPATCH(im.W, (int)im.kh.S, (kh_color_rows_launch<KW, KS>(im, d_kmers, n, rec, d_bits64, bm, stride, rowbytes, plan.tile_rows, plan.div_m, plan.div_l, d_out, device, s)));
     HIPCK(hipGetLastError());
     return 0;
 }

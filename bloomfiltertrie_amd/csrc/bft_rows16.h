@@ -3,9 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "bft_color_plan.h"  // CR16_UNROLL, CR16_WAVE_ROWS: with the rule that picks the tile
 
-#define CR16_UNROLL 1
-#define CR16_WAVE_ROWS 1024u
 #define CR16_ABSENT 0xFFFFFFFFu
 
 // s_cs[j], j <= nt: dword offset of the dictionary row of k-mer j of the tile (CR16_ABSENT: absent; entry nt: CR16_ABSENT); tout: the tile's

@@ -152,7 +152,10 @@ int bft_gpu_load_bft(const char* path, int device, bft_gpu** out);
 int bft_gpu_write_bft(bft_gpu* h, const char* path);
 
 /* Device-resident variant: d_rows = n * CEIL(nb_genomes/8) bytes, d_scratch_rows_u32 = n * 4 bytes of scratch (the row
- * index of every k-mer), d_present_bits as in bft_gpu_query_presence_dev; runs on hip_stream, does not synchronise. */
+ * index of every k-mer), d_present_bits as in bft_gpu_query_presence_dev; runs on hip_stream, does not synchronise.
+ * d_rows may have any alignment: the same bytes come out wherever it starts.  A 16-byte aligned d_rows with rows of 16 bytes and up takes
+ * the fast kernels (16-byte stores: one launch with the lookup inside when the k-mer hash answers); any other d_rows, and narrower rows,
+ * are written 4 bytes at a time. */
 int bft_gpu_query_color_rows_dev(bft_gpu* h, const void* d_kmers, uint64_t nb_kmers, void* d_present_bits, void* d_rows,
                                  void* d_scratch_rows_u32, void* hip_stream);
 
@@ -231,6 +234,11 @@ int bft_gpu_set_option(bft_gpu* h, const char* name, int64_t value);
 /* Test hook: raw device->host copy of one array of the image ("nodes", "bfT", "ccs", "f2w", "clus",
  * "child", "uck", "ucrow", "tk", "tcol", and the derived "ccx", "f18", "fent", "kh"); out may be NULL to query the size. */
 int bft_gpu_debug_get_array(bft_gpu* h, const char* name, void* out, uint64_t cap_bytes, uint64_t* nbytes);
+/* Test hook: how the colour-row kernels cut a batch of rows of `rowbytes` bytes into tiles and divide by the row width.  form 0: the
+ * kernels that store 4 bytes at a time (any rowbytes >= 1), 1: the kernel that stores 16 bytes at a time, 2: the row kernel of the k-mer hash
+ * (1 and 2: rowbytes >= 16).  out[0] = k-mers per tile, out[1], out[2] = m and l of the division: byte / rowbytes =
+ * (t + ((byte - t) >> 1)) >> (l - 1) with t = the high 32 bits of byte * m, and byte itself when l == 0.  No handle, no device. */
+int bft_gpu_debug_color_rows_plan(uint32_t rowbytes, int form, uint32_t out[3]);
 
 /* HIP-event timing of the query kernels launched through this handle since the last reset:
  * *ms = summed kernel time, *launches = number of launches.  Timing is off by default (no event on the launch path); the
