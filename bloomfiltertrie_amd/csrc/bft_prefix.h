@@ -3,8 +3,23 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bft_walk.h"  // BFT_HD
+
 // workgroups of k_pm_count / k_pm_emit: each takes one contiguous chunk of the batch's candidates
 #define BFT_PM_CHUNKS 2048
+// threads of a workgroup of the k_pm_* kernels = candidates of a tile
+constexpr int PM_THREADS = 256;
+
+// Chunk g (of G) of the candidates [0, C): whole tiles, one chunk per workgroup.  The one definition of the rule: k_pm_count and k_pm_emit call
+// it, and bft_gpu_debug_prefix_plan hands it to the tests (tests/test_prefix_cases_host.py) without a device.
+BFT_HD void pm_chunk(uint64_t C, uint32_t g, uint32_t G, uint64_t* begin, uint64_t* end, uint64_t* size = nullptr) {
+    uint64_t cs = (C + G - 1) / G;
+    cs = (cs + PM_THREADS - 1) / PM_THREADS * PM_THREADS;
+    const uint64_t b = (uint64_t)g * cs;
+    *begin = b < C ? b : C;
+    *end = *begin + cs < C ? *begin + cs : C;
+    if (size) *size = cs;
+}
 
 // Per-batch arrays, carved out of one block of the handle's (n = prefixes of the batch):
 struct BftPmScratch {

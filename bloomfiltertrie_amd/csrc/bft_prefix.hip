@@ -24,7 +24,7 @@
 
 namespace {
 
-constexpr int PM_THREADS = 256, PM_WAVES = PM_THREADS / 64;
+constexpr int PM_WAVES = PM_THREADS / 64;  // (PM_THREADS, pm_chunk: bft_prefix.h)
 constexpr uint32_t PM_NOFILT = 0xFFFFFFFFu;
 
 __device__ __forceinline__ uint64_t lanes_below(uint32_t lane) { return lane ? (~0ull >> (64 - lane)) : 0ull; }  // lane in [0, 64]
@@ -99,14 +99,6 @@ __device__ __forceinline__ PmLane pm_lane(uint64_t j0, uint64_t end, const uint6
         r.kept = ((v >> ((f >> 2) & 63u)) & 3u) == (f & 3u);
     }
     return r;
-}
-
-// chunk g of the candidates [0, C): whole tiles, one chunk per workgroup
-__device__ __forceinline__ void pm_chunk(uint64_t C, uint32_t g, uint32_t G, uint64_t* begin, uint64_t* end) {
-    uint64_t cs = (C + G - 1) / G;
-    cs = (cs + PM_THREADS - 1) / PM_THREADS * PM_THREADS;
-    *begin = min(C, (uint64_t)g * cs);
-    *end = min(C, *begin + cs);
 }
 
 template <int W>
@@ -247,6 +239,15 @@ int bft_pm_emit(int W, uint64_t n, int k, int B, const uint64_t* d_tk, const uin
     }
     HIPCK(hipGetLastError());
     return 0;
+}
+
+// Test hook (tests/test_prefix_cases_host.py, tests/test_gpu_prefix_edges.py): how k_pm_count / k_pm_emit cut C candidates into their
+// BFT_PM_CHUNKS chunks (pm_chunk, bft_prefix.h).  out: the chunk size, then [begin, end) of chunk `chunk`.  No handle, no HIP call.
+extern "C" int bft_gpu_debug_prefix_plan(uint64_t C, uint32_t chunk, uint64_t out[3]) {
+    if (!out) return bft_fail(BFT_GPU_E_ARG, "NULL argument");
+    if (chunk >= BFT_PM_CHUNKS) return bft_fail(BFT_GPU_E_ARG, "no such chunk");
+    pm_chunk(C, chunk, BFT_PM_CHUNKS, &out[1], &out[2], &out[0]);
+    return BFT_GPU_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -239,6 +239,10 @@ int bft_gpu_debug_get_array(bft_gpu* h, const char* name, void* out, uint64_t ca
  * (1 and 2: rowbytes >= 16).  out[0] = k-mers per tile, out[1], out[2] = m and l of the division: byte / rowbytes =
  * (t + ((byte - t) >> 1)) >> (l - 1) with t = the high 32 bits of byte * m, and byte itself when l == 0.  No handle, no device. */
 int bft_gpu_debug_color_rows_plan(uint32_t rowbytes, int form, uint32_t out[3]);
+/* Test hook: how the prefix kernels cut the C candidates of a batch (the rows of every prefix's interval, one after the other) into their
+ * 2048 chunks of whole tiles of 256 candidates, one chunk per workgroup.  out[0] = the chunk size, out[1], out[2] = [begin, end) of chunk
+ * `chunk` (both C for a chunk behind the last candidate).  BFT_GPU_E_ARG for a NULL out or chunk >= 2048.  No handle, no device. */
+int bft_gpu_debug_prefix_plan(uint64_t C, uint32_t chunk, uint64_t out[3]);
 
 /* HIP-event timing of the query kernels launched through this handle since the last reset:
  * *ms = summed kernel time, *launches = number of launches.  Timing is off by default (no event on the launch path); the
@@ -292,7 +296,8 @@ int bft_gpu_query_prefixes(bft_gpu* h, const uint8_t* prefixes, const uint8_t* l
  * first to learn the size.  A length outside [1, k] gives that prefix no match (checking it would cost a host synchronisation).  Scratch
  * (~40 bytes per prefix) belongs to the handle: calls on different streams are serialised by the library.  Recorded into a HIP graph (its
  * stream is being captured), the call needs the sorted table resident and its scratch sized by a direct call of the same size before --
- * else it returns BFT_GPU_E_ARG: nothing synchronises or allocates inside a capture. */
+ * else it returns BFT_GPU_E_ARG: nothing synchronises or allocates inside a capture.  d_kmers_out may have any alignment (its entries are
+ * B bytes each); d_rows_out, d_colorsets_out (uint32), d_offsets and d_needed (uint64) are naturally aligned. */
 int bft_gpu_query_prefixes_dev(bft_gpu* h, const void* d_prefixes, const void* d_lengths, uint64_t nb_prefixes, void* d_offsets, void* d_kmers_out,
                                void* d_rows_out, void* d_colorsets_out, uint64_t cap, void* d_needed, void* hip_stream);
 

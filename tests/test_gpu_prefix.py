@@ -9,7 +9,7 @@ from bloomfiltertrie_amd import BFT, _lib, synth as S
 
 pytestmark = pytest.mark.gpu
 
-KS = (9, 18, 27, 31, 36, 63, 64, 126)
+KS = (9, 18, 27, 31, 36, 63, 64, 90, 126)
 N_GENOMES = 4
 
 

@@ -12,7 +12,7 @@ import pytest
 from bloomfiltertrie_amd import _lib, synth as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KS = (9, 10, 17, 27, 31, 36, 63, 64, 126)
+KS = (9, 10, 17, 27, 31, 36, 63, 64, 72, 80, 90, 126)
 
 
 @pytest.fixture(scope="module")
