@@ -38,6 +38,11 @@ SIGNATURES = {
     "bft_gpu_query_branching_dev": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P]),
     "bft_gpu_query_sequences": (C.c_int, [_P, C.c_char_p, _P, C.c_uint64, C.c_double, C.c_int, _P]),
     "bft_gpu_query_sequences_dev": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint64, C.c_double, C.c_int, _P, _P]),
+    "bft_gpu_insert_sequences": (C.c_int, [_P, C.c_char_p, _P, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "bft_gpu_insert_sequences_dev": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), _P]),
+    "bft_gpu_insert_sequence_file": (C.c_int, [_P, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "bft_gpu_debug_ingest_plan": (C.c_int, [C.POINTER(C.c_uint64)]),
+    "bft_gpu_debug_ingest_chunks": (C.c_int, [_P, C.c_uint64, C.c_int, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "bft_gpu_load_bft": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(_P)]),
     "bft_gpu_write_bft": (C.c_int, [_P, C.c_char_p]),
     "bft_gpu_set_option": (C.c_int, [_P, C.c_char_p, C.c_int64]),

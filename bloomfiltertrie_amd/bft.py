@@ -7,6 +7,7 @@ get_list_id_genomes.  Batches are numpy uint8 arrays [n, CEIL(2k/8)] in the refe
 """
 import atexit
 import ctypes as C
+import os
 import weakref
 
 import numpy as np
@@ -27,6 +28,7 @@ def _close_all():
             pass
 
 
+INGEST_STATS = ("positions", "skipped", "distinct", "appended")  # stats[4] of bft_gpu_insert_sequences
 INFO_FIELDS = ["k", "kmers", "nodes", "ccs", "uc_rows", "child_nodes", "prefixes", "ccs_s4", "max_ccs_per_node",
                "pairs", "colorsets", "genomes", "image_bytes", "root_ccs", "root_uc_rows", "pending_pairs"]
 
@@ -135,6 +137,31 @@ class BFT:
             raise ValueError("k-mer with a character outside ACGTU (reference get_kmer/insert path exits, src/bft.c:239)")
         self.insert_kmers(packed, gid)
         return gid
+
+    def insert_sequences(self, sequences, id_genome, canonical=False, min_abundance=0):
+        """Every k-mer of a list of ASCII sequences into genome id_genome (bft_gpu_insert_sequences): windows with a character outside ACGTU are
+        skipped, canonical=True inserts what query_sequences(canonical=True) looks up, min_abundance >= 1 keeps the k-mers seen at least that
+        often in this call.  Returns the stats: positions, skipped, distinct (0 without counting), appended."""
+        enc = [x.encode() if isinstance(x, str) else bytes(x) for x in sequences]
+        off = np.zeros(len(enc) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(e) for e in enc])
+        blob = b"".join(enc) + b"\0"
+        st = (C.c_uint64 * 4)()
+        _lib.check(self._lib.bft_gpu_insert_sequences(self._h, blob, off.ctypes.data, len(enc), int(canonical), int(min_abundance), id_genome, st))
+        return dict(zip(INGEST_STATS, (int(x) for x in st)))
+
+    def insert_sequences_dev(self, d_seqs_ptr, d_seq_off_ptr, n_seqs, total_chars, id_genome, canonical=False, min_abundance=0, stream=None):
+        """Device-resident variant of insert_sequences (raw pointers; any alignment of the blob): runs on `stream` and synchronises it."""
+        st = (C.c_uint64 * 4)()
+        _lib.check(self._lib.bft_gpu_insert_sequences_dev(self._h, C.c_void_p(d_seqs_ptr or 0), C.c_void_p(d_seq_off_ptr or 0), n_seqs, total_chars, int(canonical),
+                                                          int(min_abundance), id_genome, st, C.c_void_p(stream or 0)))
+        return dict(zip(INGEST_STATS, (int(x) for x in st)))
+
+    def insert_sequence_file(self, path, id_genome, canonical=False, min_abundance=0):
+        """A plain-text FASTA or four-line FASTQ file into genome id_genome (bft_gpu_insert_sequence_file)."""
+        st = (C.c_uint64 * 4)()
+        _lib.check(self._lib.bft_gpu_insert_sequence_file(self._h, os.fsencode(path), int(canonical), int(min_abundance), id_genome, st))
+        return dict(zip(INGEST_STATS, (int(x) for x in st)))
 
     def build(self):
         _lib.check(self._lib.bft_gpu_build(self._h))

@@ -12,6 +12,7 @@
 #include <string.h>
 
 #include "../../include/bft/bft.h"
+#include "../../include/bft/ingest.h"
 #include "../../include/bft/merge.h"
 #include "../../include/bft/snippets.h"
 
@@ -157,6 +158,20 @@ void insert_genomes_from_files(int nb_files, char** paths, BFT* bft, char* prefi
         free(batch);
     }
     ck(bft_gpu_build(bft->gpu), "insert_genomes_from_files()");
+}
+
+/* <bft/ingest.h>: one genome per FASTA / FASTQ file, its k-mers cut (and counted) on the GPU */
+void insert_genomes_from_sequence_files(int nb_files, char** paths, int canonical, uint32_t min_abundance, BFT_Root* root) {
+    NOT_NULL(root, "insert_genomes_from_sequence_files()");
+    if (nb_files > 0) NOT_NULL(paths, "insert_genomes_from_sequence_files()");
+    for (int i = 0; i < nb_files; i++) {
+        NOT_NULL(paths[i], "insert_genomes_from_sequence_files()");
+        char* tmp = strdup(paths[i]);
+        const uint32_t gid = new_genome(root, basename(tmp));
+        free(tmp);
+        ck(bft_gpu_insert_sequence_file(root->gpu, paths[i], canonical, min_abundance, gid, NULL), "insert_genomes_from_sequence_files()");
+    }
+    ck(bft_gpu_build(root->gpu), "insert_genomes_from_sequence_files()");
 }
 
 /* ---------------------------------------------------------------- k-mers */

@@ -459,6 +459,28 @@ static int log_reserve(bft_gpu* h, uint64_t need) {
     return 0;
 }
 
+int bft_log_prepare(bft_gpu* h, uint64_t n, uint32_t id_genome) {
+    if (h->log_n && h->log_n + n > h->opt_flush_pairs) CK(bft_gpu_build(h));
+    CK(log_reserve(h, h->log_n + n));
+    if (h->log_comp && (id_genome >> h->log_gb) != 0) CK(log_decompose(h));  // (an id the composites have no room for)
+    return 0;
+}
+// n rows for id_genome were written behind the log's end
+static void log_appended(bft_gpu* h, uint64_t n, uint32_t id_genome) {
+    if (h->log_n > 0 && id_genome < h->log_last_gid) h->log_g_sorted = false;
+    h->log_last_gid = id_genome;
+    h->log_n += n;
+    if (!h->lb_gid.empty() && h->lb_gid.back() == id_genome) h->lb_end.back() = h->log_n;
+    else { h->lb_end.push_back(h->log_n); h->lb_gid.push_back(id_genome); }
+    h->max_gid_seen = std::max(h->max_gid_seen, id_genome);
+    h->any_insert = true;
+}
+int bft_log_commit(bft_gpu* h, uint64_t n, uint32_t id_genome, hipStream_t s) {
+    if (s && s != h->stream) CK(bft_note_foreign_stream(h, s));
+    log_appended(h, n, id_genome);
+    return 0;
+}
+
 template <int W>
 static int launch_pack(bft_gpu* h, const uint8_t* d_packed, uint64_t n, uint32_t gid, hipStream_t s) {
     const uint64_t nblk = (n + BFT_BLOCK - 1) / BFT_BLOCK;
@@ -484,9 +506,7 @@ static int insert_dev(bft_gpu* h, const void* d_kmers, uint64_t n, uint32_t id_g
         CK(insert_dev(h, d_kmers, half, id_genome, s, ordered, own_async));
         return insert_dev(h, (const uint8_t*)d_kmers + half * (uint64_t)h->B, n - half, id_genome, s, ordered, own_async);
     }
-    if (h->log_n && h->log_n + n > h->opt_flush_pairs) CK(bft_gpu_build(h));
-    CK(log_reserve(h, h->log_n + n));
-    if (h->log_comp && (id_genome >> h->log_gb) != 0) CK(log_decompose(h));  // (an id the composites have no room for)
+    CK(bft_log_prepare(h, n, id_genome));
     const hipStream_t run = ordered ? s : h->stream;
     const uint8_t* p = (const uint8_t*)d_kmers;
     switch (h->W) {
@@ -497,13 +517,7 @@ static int insert_dev(bft_gpu* h, const void* d_kmers, uint64_t n, uint32_t id_g
     }
     if (ordered) CK(bft_note_foreign_stream(h, s));
     else if (!own_async) HIPCK(hipStreamSynchronize(h->stream));
-    if (h->log_n > 0 && id_genome < h->log_last_gid) h->log_g_sorted = false;
-    h->log_last_gid = id_genome;
-    h->log_n += n;
-    if (!h->lb_gid.empty() && h->lb_gid.back() == id_genome) h->lb_end.back() = h->log_n;
-    else { h->lb_end.push_back(h->log_n); h->lb_gid.push_back(id_genome); }
-    h->max_gid_seen = std::max(h->max_gid_seen, id_genome);
-    h->any_insert = true;
+    log_appended(h, n, id_genome);
     return BFT_GPU_OK;
 }
 extern "C" int bft_gpu_insert_kmers_dev(bft_gpu* h, const void* d_kmers, uint64_t n, uint32_t id_genome) { return insert_dev(h, d_kmers, n, id_genome, nullptr, false); }
@@ -2980,6 +2994,9 @@ extern "C" int bft_gpu_set_option(bft_gpu* h, const char* name, int64_t value) {
         if (value < 0 || (uint64_t)value > h->opt_flush_pairs) return fail(BFT_GPU_E_ARG, "reserve_pairs must be in [0, flush_pairs]");
         ENTER(h);
         CK(log_reserve(h, (uint64_t)value));
+    } else if (nm == "ingest_chunk_chars") {  // characters per staged chunk of bft_gpu_insert_sequences' stream path (default 2^26; a test hook below that)
+        if (value < (int64_t)BFT_ING_CHUNK_MIN || value > (1ll << 30)) return fail(BFT_GPU_E_ARG, "ingest_chunk_chars must be in [1024, 2^30]");
+        h->opt_ingest_chunk = (uint64_t)value;
     } else if (nm == "flush_pairs") {  // the insertion log is merged into the index before it holds this many pairs (default 2^30; a test hook below that)
         if (value < 1024 || value > (1ll << 30)) return fail(BFT_GPU_E_ARG, "flush_pairs must be in [1024, 2^30]");
         h->opt_flush_pairs = (uint64_t)value;

@@ -2,8 +2,8 @@
  * bft_gpu_cli.c -- host-side C harness over the C-ABI of include/bft_gpu.h, with the command line of the reference's
  * `bft` binary for the hot path (src/main.c:40-47, :180-316):
  *
- *   bft_gpu build k {kmers|kmers_comp} list_genome_files output_file
- *   bft_gpu load file_bft [-add_genomes {kmers|kmers_comp} list_genome_files output_file]
+ *   bft_gpu build k {kmers|kmers_comp|sequences|sequences_canonical} list_genome_files output_file [-min_abundance N]
+ *   bft_gpu load file_bft [-add_genomes {kmers|kmers_comp|sequences|sequences_canonical} list_genome_files output_file [-min_abundance N]]
  *                         [-query_kmers {kmers|kmers_comp} list_kmer_files]
  *                         [-query_branching {kmers|kmers_comp} list_kmer_files]
  *                         [-query_sequences threshold {canonical|non_canonical} list_sequence_files]
@@ -16,6 +16,8 @@
  *   - line 1 = genome names joined by ','; one "0,1,..." line per input line (an all-0 line for a line that is not
  *     a valid k-mer, src/file_io.c:844-850); the final '\n' is overwritten by '\0' (src/file_io.c:873-876);
  *   - stdout: "Nb k-mers present = <n>" (src/main.c:266), "Nb branching k-mers = <n>" (src/main.c:312).
+ * An extension: with `sequences` / `sequences_canonical` the listed files are plain-text FASTA or four-line FASTQ and their k-mers are cut on the
+ * GPU (bft_gpu_insert_sequence_file); -min_abundance N keeps the k-mers a file holds at least N times.
  */
 #define _GNU_SOURCE
 #include <libgen.h>
@@ -212,6 +214,44 @@ static void query_sequences(bft_gpu* h, const char* path, double threshold, int 
     free(row); free(outname); free(tmp); free(rows); free(off); free(blob);
 }
 
+/* file-type word of build / -add_genomes: 0 kmers, 1 kmers_comp, 2 sequences, 3 sequences_canonical (anything else is `kmers`, as before) */
+static int genome_file_type(const char* word) {
+    if (strcmp(word, "kmers_comp") == 0) return 1;
+    if (strcmp(word, "sequences") == 0) return 2;
+    if (strcmp(word, "sequences_canonical") == 0) return 3;
+    return 0;
+}
+/* the optional "-min_abundance N" at argv[i]: *used = arguments consumed */
+static uint32_t min_abundance_arg(int argc, char** argv, int i, int type, int* used) {
+    *used = 0;
+    if (i + 1 >= argc || strcmp(argv[i], "-min_abundance") != 0) return 0;
+    if (type < 2) DIE("-min_abundance applies to sequences and sequences_canonical only.\n");
+    char* end = NULL;
+    const long v = strtol(argv[i + 1], &end, 10);
+    if (end == argv[i + 1] || *end || v < 0) DIE("Could not parse the count of -min_abundance.\n");
+    *used = 2;
+    return (uint32_t)v;
+}
+
+/* one genome per listed FASTA / FASTQ file, ids in file order: the k-mers are cut on the GPU */
+static void insert_sequence_genomes(bft_gpu* h, const char* list_path, int canonical, uint32_t min_abundance) {
+    char buffer[2048];
+    FILE* lst = fopen(list_path, "r");
+    if (!lst) DIE("Invalid list_genome_files.\n");
+    while (fgets(buffer, sizeof buffer, lst)) {
+        buffer[strcspn(buffer, "\r\n")] = 0;
+        if (!buffer[0]) continue;
+        uint32_t gid;
+        char* tmp = strdup(buffer);
+        ck(bft_gpu_add_genome(h, basename(tmp), &gid));
+        free(tmp);
+        printf("\nFile %u: %s\n\n", gid, buffer);
+        ck(bft_gpu_insert_sequence_file(h, buffer, canonical, min_abundance, gid, NULL));
+    }
+    fclose(lst);
+    ck(bft_gpu_build(h));
+}
+
 /* insert_Genomes_from_KmerFiles (src/file_io.c:89-213): one genome per listed file, ids in file order */
 static void insert_genomes(bft_gpu* h, const char* list_path, int k, int binary) {
     char buffer[2048];
@@ -270,8 +310,8 @@ int main(int argc, char** argv) {
     }
     if (argc < 3)
         DIE("\nUsage:\n"
-            "bft_gpu build k {kmers|kmers_comp} list_genome_files output_file\n"
-            "bft_gpu load file_bft [-add_genomes {kmers|kmers_comp} list_genome_files output_file] [Options]\n\nOptions:\n"
+            "bft_gpu build k {kmers|kmers_comp|sequences|sequences_canonical} list_genome_files output_file [-min_abundance N]\n"
+            "bft_gpu load file_bft [-add_genomes {kmers|kmers_comp|sequences|sequences_canonical} list_genome_files output_file [-min_abundance N]] [Options]\n\nOptions:\n"
             "[-query_kmers {kmers|kmers_comp} list_kmer_files]\n"
             "[-query_branching {kmers|kmers_comp} list_kmer_files]\n"
             "[-query_sequences threshold {canonical|non_canonical} list_sequence_files]\n"
@@ -284,20 +324,27 @@ int main(int argc, char** argv) {
         k = atoi(argv[2]);
         if (k <= 0) DIE("Provided length k (for k-mers) is either <= 0 or not a number.\n");
         if (k % 9 != 0) DIE("Length k (for k-mers) must be a multiple of 9.\n"); /* src/main.c:63 */
-        const int binary = strcmp(argv[3], "kmers_comp") == 0;
+        const int type = genome_file_type(argv[3]);
+        int used = 0;
+        const uint32_t min_abundance = min_abundance_arg(argc, argv, 6, type, &used);
         ck(bft_gpu_create(k, 0, &h));
-        insert_genomes(h, argv[4], k, binary);
+        if (type >= 2) insert_sequence_genomes(h, argv[4], type == 3, min_abundance);
+        else insert_genomes(h, argv[4], k, type == 1);
         ck(bft_gpu_write_bft(h, argv[5]));
-        i = 6;
+        i = 6 + used;
     } else if (strcmp(argv[1], "load") == 0) {
         ck(bft_gpu_load_bft(argv[2], 0, &h));
         i = 3;
         if (i + 3 < argc && strcmp(argv[i], "-add_genomes") == 0) { /* src/main.c:217-246 */
             uint64_t inf[16];
             ck(bft_gpu_info(h, inf, 16));
-            insert_genomes(h, argv[i + 2], (int)inf[0], strcmp(argv[i + 1], "kmers_comp") == 0);
+            const int type = genome_file_type(argv[i + 1]);
+            int used = 0;
+            const uint32_t min_abundance = min_abundance_arg(argc, argv, i + 4, type, &used);
+            if (type >= 2) insert_sequence_genomes(h, argv[i + 2], type == 3, min_abundance);
+            else insert_genomes(h, argv[i + 2], (int)inf[0], type == 1);
             ck(bft_gpu_write_bft(h, argv[i + 3]));
-            i += 4;
+            i += 4 + used;
         }
     } else
         DIE("Unrecognized command %s.\n", argv[1]);

@@ -1,6 +1,6 @@
 // bft_handle.h -- the handle behind the C-ABI (struct bft_gpu) and the host helpers every entry point needs, for the translation units that hold
 // entry points: bft_gpu.hip (which defines the helpers) and the analysis families bft_prefix.hip, bft_paths.hip, bft_components.hip, bft_pangenome.hip,
-// bft_subgraph.hip, bft_marking.hip, bft_setops.hip, bft_union.hip.
+// bft_subgraph.hip, bft_marking.hip, bft_setops.hip, bft_union.hip, bft_ingest.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,6 +9,7 @@
 
 #include "bft_dev.h"
 #include "bft_image.h"
+#include "bft_ingest.h"
 #include "bft_kh.h"
 
 // Scratch of ONE query family of a handle: blocks (DevBufs beside it in struct bft_gpu) that belong to the handle, not to a stream -- one stream uses
@@ -218,6 +219,12 @@ struct bft_gpu {
     uint64_t pg_m = 0, pg_sets = 0;  // rows and colour sets pg_buf has room for
     HandleScratch so{"colour-set algebra"};
     DevBuf so_buf;                   // set operations over groups (BftSoScratch, bft_setops.h): colour set per k-mer, presence bits, accumulators, split list
+    HandleScratch ig{"sequence ingest"};
+    DevBuf ig_seq, ig_soff;          // insertion from sequences (bft_ingest.hip): the host form's chunk of the blob and its offsets
+    DevBuf ig_codes, ig_bad, ig_npos, ig_poff, ig_seqtile, ig_tmp;  // codes, plan and the scans' temporary (as sq_*)
+    DevBuf ig_cnt, ig_off;           // valid positions (kept runs) per tile of 64 and their scan
+    DevBuf ig_keys, ig_sorted, ig_perm;  // the counting path: the valid windows' keys, sorted, and the permutation of the multi-word sort
+    uint64_t opt_ingest_chunk = BFT_ING_CHUNK_DEFAULT;  // "ingest_chunk_chars": characters of the blob the host form stages per chunk (stream path)
     // Vertex marks (bft_marking.hip): on between bft_gpu_marks_begin and bft_gpu_marks_end; insertions and builds are refused meanwhile, so the rows
     // the flags are indexed by cannot move.
     bool marking = false;
@@ -256,6 +263,12 @@ bool bft_stream_capturing(hipStream_t s);
 int bft_note_foreign_stream(bft_gpu* h, hipStream_t s);
 // The log merged into the index; need_table = false: the caller is answered by the k-mer hash alone ("compact_table": the sorted table may be away)
 int bft_ensure_built(bft_gpu* h, bool need_table = true);
+// The insertion log around a batch of n pairs for id_genome that a kernel of the caller's writes (n <= "flush_pairs"): bft_log_prepare merges the log into
+// the index first where it would pass "flush_pairs", makes room for n more rows and takes the log out of its composite form where the id has no room
+// there; the caller then writes rows [log_n, log_n + n) as k_pack_to_tform does (log_comp ? T << log_gb | id : T-form words + id) and, with the
+// writes enqueued (s: a caller's stream they run on, or null for the handle's), bft_log_commit does the bookkeeping of bft_gpu_insert_kmers_dev.
+int bft_log_prepare(bft_gpu* h, uint64_t n, uint32_t id_genome);
+int bft_log_commit(bft_gpu* h, uint64_t n, uint32_t id_genome, hipStream_t s);
 // The bitmap form of the colour-set dictionary (d_cs_bm: one dword-aligned row per set behind CS_BM_SLACK zero bytes), derived on the first call per
 // image on the handle's stream (synchronises once); has_cs_bm stays false where it would pass 4 GiB or "test_no_cs_bitmaps" is set.
 #define CS_BM_SLACK 32u  // zero bytes in front of and behind the bitmap dictionary

@@ -141,6 +141,42 @@ int bft_gpu_query_sequences(bft_gpu* h, const char* seqs, const uint64_t* seq_of
 int bft_gpu_query_sequences_dev(bft_gpu* h, const void* d_seqs, const void* d_seq_off, uint64_t nb_seqs, uint64_t total_chars,
                                 double threshold, int canonical, void* d_rows, void* hip_stream);
 
+/* Insertion from SEQUENCES (an extension: the reference inserts k-mers that a counter has cut out beforehand).  The layout is that of
+ * bft_gpu_query_sequences: an ASCII blob and nb_seqs + 1 offsets; no k-mer spans two sequences.  Every window of k characters none of which is
+ * outside ACGTU (either case) is a k-mer of genome id_genome; with canonical != 0 the inserted k-mer is the one
+ * bft_gpu_query_sequences(..., canonical = 1) looks up (the reverse complement when the window is not lexicographically smaller), so an index
+ * ingested canonically is queried canonically.  The effect on the handle is that of bft_gpu_insert_kmers_dev on the selected k-mers: the same log,
+ * the same "flush_pairs" rule (a build in front when the log would pass it, pieces for a larger call), BFT_GPU_E_STATE under marking, BFT_GPU_E_ARG
+ * for id_genome >= 2^24, for NULL with work to do and -- host form -- for offsets that decrease; nb_seqs == 0 appends nothing.
+ *   min_abundance == 0  the stream path: every valid window is appended, duplicates included (the build de-duplicates); windows go from the code
+ *                       stream straight into log rows, invalid ones leave no hole.
+ *   min_abundance >= 1  the counting path: the valid windows' keys are sorted and a k-mer is appended once when it occurs at least min_abundance
+ *                       times in THIS call (both strands together with canonical).  The whole call is one counting unit: a call with more than
+ *                       "flush_pairs" k-mer positions returns BFT_GPU_E_LIMIT and inserts nothing; nothing is counted across calls.
+ *   stats (may be NULL) [0] k-mer positions = sum over the sequences of max(len - k + 1, 0), [1] positions skipped for a character outside ACGTU,
+ *                       [2] distinct k-mers among the valid positions (0 when min_abundance == 0: nothing is counted), [3] pairs appended to the log.
+ * The host form stages the blob through device blocks of the handle; on the stream path in chunks of "ingest_chunk_chars" characters
+ * (bft_gpu_set_option, default 2^26, at least 1024), a long sequence split with k - 1 characters of overlap -- the result does not depend on it. */
+int bft_gpu_insert_sequences(bft_gpu* h, const char* seqs, const uint64_t* seq_off, uint64_t nb_seqs, int canonical, uint32_t min_abundance,
+                             uint32_t id_genome, uint64_t stats[4]);
+/* The same on device-resident buffers (d_seqs: total_chars bytes, any alignment; d_seq_off: nb_seqs + 1 uint64, the last one <= total_chars), on
+ * hip_stream (NULL = the handle's stream).  The call SYNCHRONISES that stream before it returns -- the host's count of log rows must be exact, and
+ * the number of appended rows is known on the device only -- once per piece of "flush_pairs" positions.  Not inside a graph capture
+ * (BFT_GPU_E_ARG).  Scratch belongs to the handle. */
+int bft_gpu_insert_sequences_dev(bft_gpu* h, const void* d_seqs, const void* d_seq_off, uint64_t nb_seqs, uint64_t total_chars, int canonical,
+                                 uint32_t min_abundance, uint32_t id_genome, uint64_t stats[4], void* hip_stream);
+/* A plain-text FASTA (">" header, sequence lines joined) or four-line FASTQ ("@" header, sequence, "+", quality) file, decided by its first
+ * non-blank character, read on the host (CR LF tolerated, empty records kept as sequences of length 0, no gzip, no multi-line FASTQ;
+ * BFT_GPU_E_IO for anything else, a truncated FASTQ record included) and inserted by bft_gpu_insert_sequences. */
+int bft_gpu_insert_sequence_file(bft_gpu* h, const char* path, int canonical, uint32_t min_abundance, uint32_t id_genome, uint64_t stats[4]);
+/* Test hook: out[0] = k-mer positions per tile of the ingest kernels' compaction (pieces of a call beyond "flush_pairs" are whole tiles), out[1] = the
+ * default of "ingest_chunk_chars", out[2] = its minimum.  BFT_GPU_E_ARG for a NULL out.  No handle, no device. */
+int bft_gpu_debug_ingest_plan(uint64_t out[3]);
+/* Test hook: the chunks the host form of the stream path stages for these offsets with "ingest_chunk_chars" = chunk_chars (>= 1024 and 2k):
+ * chunk i is the characters [out[3i], out[3i + 1]) of the blob, cut into out[3i + 2] (pieces of) sequences; a sequence that does not fit is cut and
+ * its next piece starts k - 1 characters before the cut.  *n_out = the number of chunks; the first `cap` of them are written (out may be NULL). */
+int bft_gpu_debug_ingest_chunks(const uint64_t* seq_off, uint64_t nb_seqs, int k, uint64_t chunk_chars, uint64_t* out, uint64_t cap, uint64_t* n_out);
+
 /* load_BFT / read_BFT_Root (include/bft.h:176, src/write_to_disk.c:260-776): parse a reference .bft file
  * (compressed == 0; annotation modes 0/1/2 and extended-annotation bytes) and build the GPU image from its
  * k-mers and colour sets, with the file's Bloom seeds and genome names.  The file is mapped and decoded by a pool of host threads
@@ -224,7 +260,8 @@ int bft_gpu_footprint(bft_gpu* h, uint64_t* out, int n_out);
  *   radix sort -- csrc/bft_sort.h -- ranks the keys of a wavefront: 0, default = one LDS atomic per key once the device has shown that it serves the lanes of such an
  *   instruction in lane order, 1 = wavefront ballots, stable by construction; same image), "reserve_pairs" (room in the insertion log for this many pending (k-mer, genome)
  *   pairs, so that a series of insert calls never re-allocates it), "flush_pairs" (the log is merged into the index before it holds this many pairs:
- *   2^30 by default, 1024..2^30).
+ *   2^30 by default, 1024..2^30), "ingest_chunk_chars" (characters of the blob that the host form of bft_gpu_insert_sequences stages per chunk on its stream
+ *   path: 2^26 by default, 1024..2^30; the result does not depend on it).
  * "test_no_cs_bitmaps" (test hook; 1: the bitmap form of the colour-set dictionary is not derived and one that exists is released -- what happens by itself where
  *   it would pass 4 GiB --, so the colour rows and bft_gpu_combine_* read the sorted id lists; 0: it is derived again by the next call that wants it; same answers).
  * "timing" (0/1: record HIP events around query kernels; off until this option or the first bft_gpu_kernel_time call turns it on).
