@@ -182,9 +182,13 @@ struct BftRun {
     const uint32_t* cs_ids;
     uint64_t n_sets;
 };
-struct BftRunOut {
+struct BftRunOut {  // ... built aside: the output of a merge, and the image-to-be that bft_commit_image takes (bft_handle.h)
     DevBuf tk, tcol, cs_off, cs_ids;
     uint64_t n = 0, n_sets = 0, n_ids = 0;
+    void swap(BftRunOut& o) {
+        tk.swap(o.tk); tcol.swap(o.tcol); cs_off.swap(o.cs_off); cs_ids.swap(o.cs_ids);
+        std::swap(n, o.n); std::swap(n_sets, o.n_sets); std::swap(n_ids, o.n_ids);
+    }
 };
 // How the k-mers are placed.  An insertion build searches every run row in the index (the default: a run is small beside its index); a merge of two
 // indexes (bft_union.hip) may stream both tables instead (coranked), has its launches timed on a handle and records its stages ("build_stages").
@@ -198,12 +202,13 @@ int bft_count_pairs(const uint32_t* d_tcol, uint64_t n, const uint32_t* d_cs_off
 
 // The build's front end behind the root-prefix split (bft_front.hip): bucket-wise sort of the composites c = T << gb | genome on the
 // bits [gb, split_bit) and the de-duplicated outputs: sorted distinct k-mers, offsets of their genome-id lists, the genome ids.
+// what steps 1-3 of a build make of the insertion log (bft_run.hip): sorted distinct T-form k-mers, the offsets of their genome-id lists, the ids
+struct BftPairRun { DevBuf tk, seg_off, ids; uint64_t nk = 0, np = 0; };
 uint32_t bft_front_bucket_capacity(void);
 void bft_test_front_rank_mode(int mode);   // test hook: k_bucket_sort's mode (0 atomics + check, 1 ballots only, 2 the check always fails)
 // d_vals (vw bytes per id): d_c holds whole T-form k-mers grouped by the bits from split_bit - gb up, the ids beside them
-int bft_front_buckets(uint64_t* d_c, uint64_t n, const uint32_t* d_boff, uint32_t nb, uint32_t gb, uint32_t split_bit, hipStream_t s, DevBuf& tk, DevBuf& seg_off,
-                      DevBuf& pg, uint64_t& nk, uint64_t& np, const uint32_t* d_max_bucket, uint32_t* max_bucket, bool* done, uint32_t* n_redone,
-                      const void* d_vals = nullptr, uint32_t vw = 0);
+int bft_front_buckets(uint64_t* d_c, uint64_t n, const uint32_t* d_boff, uint32_t nb, uint32_t gb, uint32_t split_bit, hipStream_t s, BftPairRun& run,
+                      const uint32_t* d_max_bucket, uint32_t* max_bucket, bool* done, uint32_t* n_redone, const void* d_vals = nullptr, uint32_t vw = 0);
 // (d_max_bucket: the size of the largest bucket, on the device -- it reaches the host, *max_bucket, while the first sort kernel runs;
 // *done = false: that bucket is beyond bft_front_bucket_capacity() and nothing was produced (d_c may have been reordered inside its
 // buckets); *n_redone: buckets whose order check failed and that were sorted again)
@@ -211,5 +216,5 @@ int bft_front_buckets(uint64_t* d_c, uint64_t n, const uint32_t* d_boff, uint32_
 // bits below, id: the genome} (12 bytes each) beside them.  *done = false: a bucket is beyond bft_front2_bucket_capacity(): nothing was produced
 // (the arrays may have been reordered inside their buckets); *n_redone as bft_front_buckets'.
 uint32_t bft_front2_bucket_capacity(void);
-int bft_front2_buckets(uint64_t* d_hk, void* d_items, uint64_t n, const uint32_t* d_boff, uint32_t nb, int k, hipStream_t s, DevBuf& tk, DevBuf& seg_off, DevBuf& pg, uint64_t& nk, uint64_t& np,
+int bft_front2_buckets(uint64_t* d_hk, void* d_items, uint64_t n, const uint32_t* d_boff, uint32_t nb, int k, hipStream_t s, BftPairRun& run,
                        const uint32_t* d_max_bucket, uint32_t* max_bucket, bool* done, uint32_t* n_redone, uint32_t max_gid);

@@ -1021,9 +1021,8 @@ uint32_t bft_front_bucket_capacity(void) { return FB_CAP; }
 static int g_rank_mode = 0;                 // k_bucket_sort's mode ("test_front_rank_mode")
 void bft_test_front_rank_mode(int mode) { g_rank_mode = mode; }
 
-int bft_front_buckets(uint64_t* d_c, uint64_t n, const uint32_t* d_boff, uint32_t nb, uint32_t gb, uint32_t split_bit, hipStream_t s, DevBuf& tk, DevBuf& seg_off,
-                      DevBuf& pg, uint64_t& nk, uint64_t& np, const uint32_t* d_max_bucket, uint32_t* max_bucket, bool* done, uint32_t* n_redone,
-                      const void* d_vals, uint32_t vw) {
+int bft_front_buckets(uint64_t* d_c, uint64_t n, const uint32_t* d_boff, uint32_t nb, uint32_t gb, uint32_t split_bit, hipStream_t s, BftPairRun& run,
+                      const uint32_t* d_max_bucket, uint32_t* max_bucket, bool* done, uint32_t* n_redone, const void* d_vals, uint32_t vw) {
     *done = false;
     PinBlock pin;  // [0] the largest bucket, [1] k-mers << 32 | pairs, [2] buckets sorted again
     if (!pin.p) return bft_fail(BFT_GPU_E_HIP, "hipHostMalloc (front end counts)");
@@ -1069,14 +1068,13 @@ int bft_front_buckets(uint64_t* d_c, uint64_t n, const uint32_t* d_boff, uint32_
     CK(bft_pin_wait_for(pin, s, ticket2));
     const uint64_t total = pin.p[1];
     if (n_redone) *n_redone = (uint32_t)pin.p[2];
-    nk = total >> 32;
-    np = total & 0xFFFFFFFFull;
+    const uint64_t nk = run.nk = total >> 32, np = run.np = total & 0xFFFFFFFFull;
     bft_trace_mark("bucket sort done (sync)");
-    CK(tk.alloc(nk * 8));
-    CK(seg_off.alloc((nk + 1) * 4));
-    CK(pg.alloc(np * 4));
+    CK(run.tk.alloc(nk * 8));
+    CK(run.seg_off.alloc((nk + 1) * 4));
+    CK(run.ids.alloc(np * 4));
     // (seg_off[nk] = np is the kernel's too: nothing of this call is left on the host's side when it returns, the stream goes on)
-    hipLaunchKernelGGL(k_bucket_emit, grid, block, 0, s, d_c, d_boff, nb, gb, bases.as<uint64_t>(), tk.as<uint64_t>(), seg_off.as<uint32_t>(), pg.as<uint32_t>(), d_vals ? 1 : 0, split_bit - gb,
+    hipLaunchKernelGGL(k_bucket_emit, grid, block, 0, s, d_c, d_boff, nb, gb, bases.as<uint64_t>(), run.tk.as<uint64_t>(), run.seg_off.as<uint32_t>(), run.ids.as<uint32_t>(), d_vals ? 1 : 0, split_bit - gb,
                        (uint32_t)nk, (uint32_t)np);
     HIPCK(hipGetLastError());
     bft_stage("bucket emit (k-mers, offsets, genome ids)", (double)n * 8 + (double)nk * 12 + (double)np * 4, s);
@@ -1087,7 +1085,7 @@ int bft_front_buckets(uint64_t* d_c, uint64_t n, const uint32_t* d_boff, uint32_
 uint32_t bft_front2_bucket_capacity(void) { return FB_BLOCK * 32; }
 
 // the two-word front end behind the split (items grouped by the top 18 bits of hk): see k_bucket2_sort
-int bft_front2_buckets(uint64_t* d_hk, void* d_items, uint64_t n, const uint32_t* d_boff, uint32_t nb, int k, hipStream_t s, DevBuf& tk, DevBuf& seg_off, DevBuf& pg, uint64_t& nk, uint64_t& np,
+int bft_front2_buckets(uint64_t* d_hk, void* d_items, uint64_t n, const uint32_t* d_boff, uint32_t nb, int k, hipStream_t s, BftPairRun& run,
                        const uint32_t* d_max_bucket, uint32_t* max_bucket, bool* done, uint32_t* n_redone, uint32_t max_gid) {
     *done = false;
     const bool pack = max_gid < (1u << 18);  // (ids that fit the 18 free bits above hk's 46: k_bucket2_sort_wave)
@@ -1144,13 +1142,12 @@ int bft_front2_buckets(uint64_t* d_hk, void* d_items, uint64_t n, const uint32_t
     if (n_redone) *n_redone = (uint32_t)pin.p[3];
     if (pin.p[2] != 0) return 0;  // (a bucket beyond this front end: the caller sorts device-wide)
     const uint64_t total = pin.p[1];
-    nk = total >> 32;
-    np = total & 0xFFFFFFFFull;
-    CK(tk.alloc(nk * 16));
-    CK(seg_off.alloc((nk + 1) * 4));
-    CK(pg.alloc(np * 4));
-    hipLaunchKernelGGL(k_bucket2_emit, dim3(std::min<uint32_t>(nb, 256u * 16u)), block, 0, s, d_hk, d_it, d_boff, nb, bases.as<uint64_t>(), tk.as<uint64_t>(), seg_off.as<uint32_t>(),
-                       pg.as<uint32_t>(), sh, (uint32_t)nk, (uint32_t)np);
+    const uint64_t nk = run.nk = total >> 32, np = run.np = total & 0xFFFFFFFFull;
+    CK(run.tk.alloc(nk * 16));
+    CK(run.seg_off.alloc((nk + 1) * 4));
+    CK(run.ids.alloc(np * 4));
+    hipLaunchKernelGGL(k_bucket2_emit, dim3(std::min<uint32_t>(nb, 256u * 16u)), block, 0, s, d_hk, d_it, d_boff, nb, bases.as<uint64_t>(), run.tk.as<uint64_t>(), run.seg_off.as<uint32_t>(),
+                       run.ids.as<uint32_t>(), sh, (uint32_t)nk, (uint32_t)np);
     HIPCK(hipGetLastError());
     bft_stage("two-word buckets: emit (k-mers, offsets, genome ids)", (double)n * 20 + (double)np * 4 + (double)nk * 20, s);
     *done = true;

@@ -1,4 +1,4 @@
-// bft_gpu.hip -- the C-ABI of include/bft_gpu.h: handle (bft_handle.h), device-memory cache, insertion log, bulk build, k-mer and sequence query entry
+// bft_gpu.hip -- the C-ABI of include/bft_gpu.h: handle (bft_handle.h), device-memory cache, insertion log, bulk build (its run stage: bft_run.hip), k-mer and sequence query entry
 // points, residency / probe tuning, .bft files, image replication (prefixes, sub-graphs, paths, components: beside their kernels).  With its device code:
 //   bft_kernels_query.h  k_pack_to_tform (packed 2-bit k-mers -> T-form words: the per-level rev[]/rotation work of
 //                        src/presenceNode.c:1327-1371 done once per k-mer), k_query_kh / k_branching_kh (the same queries through the
@@ -7,11 +7,10 @@
 //                        Bloom block + root CC headers staged in LDS, 64 presence bits per wavefront via __ballot),
 //                        k_branching / k_branching8 (src/branchingNode.c)
 //   bft_kernels_seq.h    query_sequence (src/bft.c:1241-1351) around k_query
-//   bft_kernels_build.h  de-duplication of sorted (k-mer, genome) pairs for the bulk build
 //   bft_kernels_color.h  batched get_annotation + get_list_id_genomes (src/bft.c:363-387, 622-641)
 //   bft_walk.h           the per-k-mer walk itself (shared with the host-side test helper)
-// The bulk build sorts and scans with the library's own kernels (bft_sort.h, bft_scan.h); colour-set interning and container
-// assembly are the kernels of bft_assemble.hip -- see DESIGN.md "Insertion".
+// The bulk build turns the log into a sorted, de-duplicated run in bft_run.hip (the library's own sort and scan: bft_sort.h, bft_scan.h -- here
+// only for the test hooks at the end); colour-set interning and container assembly are the kernels of bft_assemble.hip -- see DESIGN.md "Insertion".
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,6 +32,7 @@
 #include "bft_index.h"
 #include "bft_kh.h"
 #include "bft_paths.h"
+#include "bft_run.h"
 #include "bft_scan.h"
 #include "bft_sort.h"
 #include "bft_walk.h"
@@ -89,7 +89,6 @@ void bft_stage(const char* name, double bytes, hipStream_t s) {
 // device code, by topic
 #include "bft_kernels_query.h"
 #include "bft_kernels_seq.h"
-#include "bft_kernels_build.h"
 #include "bft_kernels_color.h"
 // ------------------------------------------------------------------------------------------------
 // device-memory cache (see bft_dev.h)
@@ -415,6 +414,14 @@ static uint32_t log_comp_bits(const bft_gpu* h) {  // id bits of a composite log
     const int room = 63 - 2 * h->k;
     return (h->W == 1 && h->opt_comp_log && !h->opt_no_composite && room >= 7) ? (uint32_t)std::min(room, 24) : 0u;
 }
+// a log of composites back into T-form k-mers and their ids (in place + the id array)
+__global__ void k_log_decompose(uint64_t* __restrict__ log_k, uint64_t n, uint32_t cgb, uint32_t* __restrict__ log_g) {
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t c = log_k[i];
+        log_g[i] = (uint32_t)(c & ((1ull << cgb) - 1ull));
+        log_k[i] = c >> cgb;
+    }
+}
 // composites -> k-mers + ids, for whatever cannot take composites (the id array is allocated here)
 static int log_decompose(bft_gpu* h) {
     if (!h->log_comp) return 0;
@@ -563,76 +570,6 @@ extern "C" int bft_gpu_insert_kmers(bft_gpu* h, const uint8_t* kmers, uint64_t n
 // ------------------------------------------------------------------------------------------------
 // bulk build
 // ------------------------------------------------------------------------------------------------
-static int bits_for(uint64_t v) {
-    int b = 1;
-    while (b < 64 && (v >> b)) b++;
-    return b;
-}
-
-int bft_sort_pairs(bft_gpu* h, const uint64_t* keys, uint64_t stride, const uint32_t* g, uint64_t total, uint64_t* okeys, uint64_t ostride, uint32_t* og,
-                   bool g_already_ordered, bool is_log) {
-    const int W = h->W;
-    if (W == 1) {
-        // one-word keys: sort the (key, genome) pairs themselves; the radix sort is stable, so a genome-id pass
-        // first (skipped when the ids already ascend) followed by the key pass gives (T, genome) order
-        DevBuf k2, g2;
-        const uint64_t* kin = keys;
-        const uint32_t* gin = g;
-        if (!g_already_ordered) {
-            CK(k2.alloc(total * 8));
-            CK(g2.alloc(total * 4));
-            const int gb = bits_for(h->max_gid_seen);
-            CK((bft_rs::sort_pairs<uint32_t, uint64_t>(gin, kin, total, g2.as<uint32_t>(), k2.as<uint64_t>(), 0, gb, h->stream)));
-            kin = k2.as<uint64_t>();
-            gin = g2.as<uint32_t>();
-        }
-        CK((bft_rs::sort_pairs<uint64_t, uint32_t>(kin, gin, total, okeys, og, 0, 2 * h->k, h->stream)));
-        HIPCK(hipGetLastError());
-        HIPCK(hipStreamSynchronize(h->stream));
-        return 0;
-    }
-    DevBuf perm, perm2, ku, ku2, kg2;
-    CK(perm.alloc(total * 4));
-    CK(perm2.alloc(total * 4));
-    CK(ku.alloc(total * 8));
-    CK(ku2.alloc(total * 8));
-    const int grid = grid_for((total + 255) / 256);
-    hipLaunchKernelGGL(k_iota, dim3(grid), dim3(256), 0, h->stream, perm.as<uint32_t>(), total);
-    // pass 0: genome id (least significant); skipped when the input is already in genome-id order
-    // (ids inserted in non-decreasing order, as the reference requires: the stable key passes keep it)
-    if (!g_already_ordered) {
-        CK(kg2.alloc(total * 4));
-        const int gb = bits_for(h->max_gid_seen);
-        CK((bft_rs::sort_pairs<uint32_t, uint32_t>(g, perm.as<uint32_t>(), total, kg2.as<uint32_t>(), perm2.as<uint32_t>(), 0, gb, h->stream)));
-        perm.swap(perm2);
-    }
-    // passes over the key words, least significant word (W-1) first
-    for (int w = W - 1; w >= 0; w--) {
-        const int nbits = (w == 0) ? (2 * h->k - 64 * (W - 1)) : 64;
-        const uint64_t* kin = keys + (uint64_t)w * stride;
-        if (w != W - 1 || !g_already_ordered) {  // (the first pass of an id-ordered log: the permutation is still the identity, the word is sorted where it lies)
-            hipLaunchKernelGGL(k_gather<uint64_t>, dim3(grid), dim3(256), 0, h->stream, kin, perm.as<uint32_t>(), ku.as<uint64_t>(), total);
-            kin = ku.as<uint64_t>();
-        }
-        CK((bft_rs::sort_pairs<uint64_t, uint32_t>(kin, perm.as<uint32_t>(), total, ku2.as<uint64_t>(), perm2.as<uint32_t>(), 0, nbits, h->stream)));
-        perm.swap(perm2);
-    }
-    // (one pass over the permutation for every word and the id, instead of a pass each; the ids of the LOG come out of the table of its insert calls)
-    DevBuf lbe, lbg;
-    uint32_t nlb = 0;
-    if (is_log && !h->lb_end.empty() && h->lb_end.size() <= (1u << 16) && h->lb_end.back() == total) {
-        nlb = (uint32_t)h->lb_end.size();
-        CK(lbe.alloc(nlb * 8));
-        CK(lbg.alloc(nlb * 4));
-        HIPCK(hipMemcpyAsync(lbe.p, h->lb_end.data(), nlb * 8, hipMemcpyHostToDevice, h->stream));
-        HIPCK(hipMemcpyAsync(lbg.p, h->lb_gid.data(), nlb * 4, hipMemcpyHostToDevice, h->stream));
-    }
-    hipLaunchKernelGGL(k_gather_pairs, dim3(grid), dim3(256), 0, h->stream, keys, stride, W, g, perm.as<uint32_t>(), okeys, ostride, og, total, lbe.as<uint64_t>(), lbg.as<uint32_t>(), nlb);
-    HIPCK(hipGetLastError());
-    HIPCK(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
 template <class T>
 static int upload(DevBuf& d, const std::vector<T>& v) {
     CK(d.alloc(v.size() * sizeof(T)));
@@ -826,17 +763,21 @@ static void derive_node_hash(bft_gpu* h) {
 
 static bool kh_wanted(const bft_gpu* h, uint64_t nk) { return h->opt_kmer_hash && nk > 0 && nk < (1ull << 31); }
 static bool kh_geo_ok(const bft_gpu* h, const BftKhGeo& g) { return bft_kh_has_kernels(h->W, g.S) && g.nl + BFT_KH_TAIL_LINES < (1ull << 32); }
+// the handle's second stream (low priority: the k-mer hash fill and the interning's tail run beside the build's own chain), made on first use
+static bool ensure_stream2(bft_gpu* h) {
+    if (h->stream2) return true;
+    int lo = 0, hi = 0;  // (numerically larger = lower priority)
+    if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) { lo = 0; (void)hipGetLastError(); }
+    if (hipStreamCreateWithPriority(&h->stream2, hipStreamNonBlocking, lo) != hipSuccess) { h->stream2 = nullptr; (void)hipGetLastError(); }
+    return h->stream2 != nullptr;
+}
 // the host side of the build that needs no table yet: the second stream, the table's memory, the events (a millisecond of driver
 // calls for a gigabyte table that is not in the cache).  n_values: the colour sets of the index, or -- before they are known -- a bound
 // (sets <= k-mers): fewer slots per line at worst, i.e. a table allocated larger than needed, never smaller.
 static void kh_prepare(bft_gpu* h, uint64_t nk, uint64_t n_values, KhFill& f) {
     f.prepared = false;
     if (!kh_wanted(h, nk)) return;
-    if (!h->stream2) {
-        int lo = 0, hi = 0;  // (numerically larger = lower priority)
-        if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) { lo = 0; (void)hipGetLastError(); }
-        if (hipStreamCreateWithPriority(&h->stream2, hipStreamNonBlocking, lo) != hipSuccess) { h->stream2 = nullptr; (void)hipGetLastError(); return; }
-    }
+    if (!ensure_stream2(h)) return;
     f.geo = bft_kh_geometry(h->k, nk, std::max<uint64_t>(1, n_values), h->opt_kh_load);
     if (!kh_geo_ok(h, f.geo)) return;
     f.lines_cap = f.geo.nl + BFT_KH_TAIL_LINES;
@@ -1179,86 +1120,6 @@ static int host_colorsets(bft_gpu* h) {
     return 0;
 }
 
-// One-word keys, sorted, with their genome ids (GT wide): flags on the fly, one 64-bit scan, scatter into the genome-id lists, the
-// distinct-k-mer table and the segment offsets (bft_kernels_build.h).
-template <class GT>
-static int dedupe_w1(bft_gpu* h, const uint64_t* sk, const GT* sg, uint64_t total, DevBuf& tk, DevBuf& seg_off, DevBuf& npg, uint64_t& nk,
-                     uint64_t& np) {
-    DevBuf tmp, pos;
-    CK(pos.alloc(total * 8));
-    const BftPairFlags2<GT> pf{sk, sg};
-    CK((bft_scan::exclusive_sum<uint64_t>(pf, pos.as<uint64_t>(), total, h->stream, tmp)));
-    uint64_t last_pos = 0, last_k[2] = {0, 0};
-    GT last_g[2] = {0, 0};
-    HIPCK(hipMemcpyAsync(&last_pos, pos.as<uint64_t>() + total - 1, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCK(hipMemcpyAsync(&last_k[1], sk + total - 1, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCK(hipMemcpyAsync(&last_g[1], sg + total - 1, sizeof(GT), hipMemcpyDeviceToHost, h->stream));
-    if (total > 1) {
-        HIPCK(hipMemcpyAsync(&last_k[0], sk + total - 2, 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCK(hipMemcpyAsync(&last_g[0], sg + total - 2, sizeof(GT), hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCK(hipStreamSynchronize(h->stream));
-    const bool last_head = total == 1 || last_k[1] != last_k[0], last_keep = last_head || last_g[1] != last_g[0];
-    nk = (last_pos >> 32) + (last_head ? 1 : 0);
-    np = (last_pos & 0xFFFFFFFFull) + (last_keep ? 1 : 0);
-    CK(tk.alloc(nk * 8));
-    CK(seg_off.alloc((nk + 1) * 4));
-    CK(npg.alloc(np * 4));
-    hipLaunchKernelGGL(k_scatter_2<GT>, dim3(grid_for((total + 255) / 256)), dim3(256), 0, h->stream, sk, sg, total, pos.as<uint64_t>(), npg.as<uint32_t>(),
-                       tk.as<uint64_t>(), seg_off.as<uint32_t>());
-    const uint32_t np32 = (uint32_t)np;
-    HIPCK(hipMemcpyAsync(seg_off.as<uint32_t>() + nk, &np32, 4, hipMemcpyHostToDevice, h->stream));
-    HIPCK(hipGetLastError());
-    HIPCK(hipStreamSynchronize(h->stream));
-    return 0;
-}
-// Stable sort of ordered one-word keys with their ids narrowed to GT (values through a transform iterator over the log), then dedupe_w1.
-template <class GT>
-static int sort_dedupe_w1_narrow(bft_gpu* h, const uint64_t* src_k, const uint32_t* src_g, uint64_t total, DevBuf& tk, DevBuf& seg_off, DevBuf& npg,
-                                 uint64_t& nk, uint64_t& np) {
-    DevBuf sk, sg;
-    CK(sk.alloc(total * 8));
-    CK(sg.alloc(total * sizeof(GT)));
-    CK((bft_rs::sort_in<uint64_t, GT>(BftPairIn<GT>{src_k, src_g}, total, sk.as<uint64_t>(), sg.as<GT>(), 0u, (unsigned)(2 * h->k), h->stream)));
-    HIPCK(hipGetLastError());
-    return dedupe_w1<GT>(h, sk.as<uint64_t>(), sg.as<GT>(), total, tk, seg_off, npg, nk, np);
-}
-
-// The same front end for ordered one-word keys whose composite does not fit 63 bits (k = 31 beyond a couple of genomes, k = 27 beyond
-// 512): a stable key + value sort on the 18 root-prefix bits -- the ids travel beside the keys, narrowed to VT --, then the buckets
-// (bft_front.hip), where the bits a bucket's k-mers share make room for the id.  done = false: a bucket is too large, nothing was built.
-template <class VT>
-static int split_dedupe_w1(bft_gpu* h, const uint64_t* src_k, const uint32_t* src_g, uint64_t total, int gb, DevBuf& tk, DevBuf& seg_off, DevBuf& npg,
-                           uint64_t& nk, uint64_t& np, bool& done) {
-    done = false;
-    const unsigned top = (unsigned)std::min(18, 2 * h->k), rest = (unsigned)(2 * h->k) - top;
-    DevBuf sk, sv, boff, maxb;
-    CK(sk.alloc(total * 8));
-    CK(sv.alloc(total * sizeof(VT)));
-    CK(boff.alloc(((1u << top) + 1) * 4));
-    CK(maxb.alloc_zero(4, h->stream));
-    {
-        DevBuf tk2, tv2, scratch;
-        const bft_rs::Plan spl = bft_rs::make_plan(rest, (unsigned)(2 * h->k));
-        if (spl.P > 1) {
-            CK(tk2.alloc(total * 8));
-            CK(tv2.alloc(total * sizeof(VT)));
-        }
-        const uint32_t* dbase = nullptr;
-        CK((bft_rs::sort<uint64_t, VT, BftPairIn<VT>>(BftPairIn<VT>{src_k, src_g}, total, sk.as<uint64_t>(), sv.as<VT>(), tk2.as<uint64_t>(), tv2.as<VT>(), rest, (unsigned)(2 * h->k),
-                                                      h->stream, scratch, &dbase)));
-        hipLaunchKernelGGL(k_msd_bounds, dim3(((1u << top) + 1 + 255) / 256), dim3(256), 0, h->stream, sk.as<uint64_t>(), total, (uint32_t)rest, 1u << top, boff.as<uint32_t>(), dbase,
-                           spl.P ? spl.nbits[spl.P - 1] : 0u, top);
-        hipLaunchKernelGGL(k_msd_max, dim3(((1u << top) + 255) / 256), dim3(256), 0, h->stream, boff.as<uint32_t>(), 1u << top, maxb.as<uint32_t>());
-    }
-    bft_stage("split (root-prefix, 2 x 9 bits, pairs)", (double)total * (12 + 12 + 2 * (8 + sizeof(VT)) + (8 + sizeof(VT))), h->stream);
-    uint32_t mx = 0;
-    CK(bft_front_buckets(sk.as<uint64_t>(), total, boff.as<uint32_t>(), 1u << top, (uint32_t)gb, (uint32_t)gb + rest, h->stream, tk, seg_off, npg, nk, np, maxb.as<uint32_t>(), &mx, &done,
-                         &h->front_redone, sv.p, (uint32_t)sizeof(VT)));
-    h->msd_max_bucket = mx;
-    return 0;
-}
-
 StageScope::StageScope(bft_gpu* hh, hipStream_t s) : h(hh) {
     t_stages_on = h->opt_build_stages;
     t_stage_marks.clear();
@@ -1285,23 +1146,27 @@ StageScope::~StageScope() {
     t_stage_marks.clear();
 }
 
-int bft_commit_image(bft_gpu* h, DevBuf& tk, DevBuf& n_tcol, DevBuf& n_cs_off, DevBuf& n_cs_ids, uint64_t nk, uint64_t n_sets, uint64_t n_ids, uint64_t np,
-                     KhFill& khf, BftInternTail& tail, DevBuf& seg_off, DevBuf& npg, double t0, double t1) {
+int bft_commit_image(bft_gpu* h, BftRunOut& img, uint64_t np, double t0, double t1, BftBuildSide* side) {
+    // (a caller that neither interned nor prepared the k-mer hash: nothing prepared, nothing pending)
+    if (!side) { BftBuildSide none; return bft_commit_image(h, img, np, t0, t1, &none); }
     const int W = h->W;
-    struct KhStart {  // (from here on tk, n_tcol and the number of colour sets are final)
+    KhFill& khf = side->khf;
+    BftInternTail& tail = side->tail;
+    const uint64_t nk = img.n;
+    struct KhStart {  // (from here on the table, the colour set per row and the number of colour sets are final)
         bft_gpu* h; const uint64_t* tk; const uint32_t* tcol; uint64_t nk, n_sets; KhFill* f;
         static void run(void* c, hipStream_t s) { KhStart* k = (KhStart*)c; kh_start(k->h, k->tk, k->tcol, k->nk, k->n_sets, *k->f, s, nullptr); }
-    } khs{h, tk.as<uint64_t>(), n_tcol.as<uint32_t>(), nk, n_sets, &khf};
+    } khs{h, img.tk.as<uint64_t>(), img.tcol.as<uint32_t>(), nk, img.n_sets, &khf};
     // (started HERE instead -- beside the root's table passes -- the sort-based table build was measured too: 17.2-18.4 ms against 17.0)
     // (and earlier still -- behind the root's prefix scans, or before them: 15.7 ms each way, round 5: the build is bound by the device's total work,
     // not by either stream's chain)
-    const BftAssembleHook hook{tk.p ? &KhStart::run : nullptr, &khs};
+    const BftAssembleHook hook{img.tk.p ? &KhStart::run : nullptr, &khs};
     const double t2 = bft_now_ms();
 
     // 5. containers, level by level, on the GPU
-    if (!tk.p) CK(tk.alloc(8));
+    if (!img.tk.p) CK(img.tk.alloc(8));
     BftDeviceIndex idx;
-    CK(bft_assemble_gpu(tk.as<uint64_t>(), nk, h->k, h->d_hashmod.as<uint32_t>(), h->stream, idx, &hook));
+    CK(bft_assemble_gpu(img.tk.as<uint64_t>(), nk, h->k, h->d_hashmod.as<uint32_t>(), h->stream, idx, &hook));
     bft_trace_mark("containers assembled");
     bft_stage("containers: concatenation", 0, h->stream);
     double t3 = bft_now_ms();
@@ -1320,24 +1185,24 @@ int bft_commit_image(bft_gpu* h, DevBuf& tk, DevBuf& n_tcol, DevBuf& n_cs_off, D
             (void)kh_finish(h, khf, &ms_);  // (the table under construction holds the wrong colour sets, and reads the arrays replaced below)
             khf.buf.release();
             kh_redo = true;
-            CK(bft_intern_colors_gpu(seg_off.as<uint32_t>(), npg.as<uint32_t>(), nk, np, h->stream, n_tcol, n_cs_off, n_cs_ids, n_sets, n_ids, 0, nullptr, true));
+            CK(bft_intern_colors_gpu(side->lists.seg_off.as<uint32_t>(), side->lists.ids.as<uint32_t>(), side->lists.nk, side->lists.np, h->stream, img.tcol, img.cs_off, img.cs_ids, img.n_sets, img.n_ids, 0, nullptr, true));
         }
-        seg_off.release();
-        npg.release();
+        side->lists.seg_off.release();
+        side->lists.ids.release();
     }
     const uint32_t new_cs_w = id_width(h->max_gid_seen);
     DevBuf n_cs_ids_w;
     bool narrowed_here = false;
     if (!kh_redo && tail.narrow.p && tail.narrow_w == new_cs_w) {  // (done by the interning's tail on the side stream)
         n_cs_ids_w.swap(tail.narrow);
-        n_cs_ids.release();
+        img.cs_ids.release();
     } else {
-        CK(narrow_ids(n_cs_ids, n_ids, new_cs_w, h->stream, n_cs_ids_w));
+        CK(narrow_ids(img.cs_ids, img.n_ids, new_cs_w, h->stream, n_cs_ids_w));
         narrowed_here = new_cs_w < 4;
     }
     CK(wait_foreign_stream(h));  // queries a caller still has in flight on its own stream read the arrays released below
     bft_trace_mark("ids narrowed, foreign stream waited");
-    bft_stage("dictionary ids narrowed", narrowed_here ? (double)n_ids * (4 + new_cs_w) : 0.0, h->stream);
+    bft_stage("dictionary ids narrowed", narrowed_here ? (double)img.n_ids * (4 + new_cs_w) : 0.0, h->stream);
     double kh_ms = 0;
     const bool kh_ok = !kh_redo && kh_finish(h, khf, &kh_ms);
     bft_trace_mark("k-mer hash fill waited");
@@ -1348,12 +1213,12 @@ int bft_commit_image(bft_gpu* h, DevBuf& tk, DevBuf& n_tcol, DevBuf& n_cs_off, D
     }
 
     // ---- commit: nothing above touched the handle; from here on nothing can fail before the image is whole ----
-    h->d_tcol.swap(n_tcol);
-    h->d_cs_off.swap(n_cs_off);
+    h->d_tcol.swap(img.tcol);
+    h->d_cs_off.swap(img.cs_off);
     h->d_cs_ids.swap(n_cs_ids_w);
     h->cs_w = new_cs_w;
-    h->n_sets = n_sets;
-    h->n_ids = n_ids;
+    h->n_sets = img.n_sets;
+    h->n_ids = img.n_ids;
     h->cs_on_host = false;
     h->cs_off.clear();
     h->cs_ids.clear();
@@ -1373,7 +1238,7 @@ int bft_commit_image(bft_gpu* h, DevBuf& tk, DevBuf& n_tcol, DevBuf& n_cs_off, D
     h->d_child.swap(idx.child);
     h->d_uck.swap(idx.uck);
     h->d_ucrow.swap(idx.ucrow);
-    h->d_tk.swap(tk);
+    h->d_tk.swap(img.tk);
     h->n_pairs = np;
     h->log_n = 0;
     h->lb_end.clear();
@@ -1399,12 +1264,11 @@ int bft_commit_image(bft_gpu* h, DevBuf& tk, DevBuf& n_tcol, DevBuf& n_cs_off, D
     I[7] = idx.n_ccs_s4;
     I[8] = idx.max_ccs_per_node;
     I[9] = np;
-    I[10] = n_sets;
+    I[10] = img.n_sets;
     I[11] = im.nb_genomes;
     I[12] = image_bytes(h);
     I[13] = idx.root_ncc;
     I[14] = idx.root_uc;
-    h->root_ncc = (uint32_t)idx.root_ncc;
     h->build_ms[0] = t1 - t0;
     h->build_ms[1] = t2 - t1;
     h->build_ms[2] = t3 - t2;
@@ -1443,236 +1307,59 @@ extern "C" int bft_gpu_build(bft_gpu* h) {
     CK(wait_foreign_stream(h));  // batches still being packed into the log on a caller's stream (bft_gpu_insert_kmers_dev_async)
     if (h->log_comp && (!h->log_g_sorted || h->opt_no_composite)) CK(log_decompose(h));  // (only the composite path below takes a log of composites)
     if (h->built) CK(bft_ensure_table(h));  // ("compact_table": the merge reads the index's sorted table)
-    const int W = h->W;
-    const uint64_t total = h->log_n;  // the run: what was inserted since the last build
-    double t0 = bft_now_ms();
+    const double t0 = bft_now_ms();
     bft_trace_mark(nullptr);
     StageScope stage_scope(h);
 
-    DevBuf tk, seg_off, npg;
-    uint64_t nk = 0, np = 0;
-    h->front_redone = 0;
-    h->msd_max_bucket = 0;
-    if (total > 0) {
-        // 1. the pairs to sort: the insertion log
-        DevBuf ck, cg, sk, sg;
-        const uint64_t* src_k = h->log_k.as<uint64_t>();
-        const uint32_t* src_g = h->log_g.as<uint32_t>();
-        const uint64_t src_stride = h->log_cap;
-        const int gb = h->log_comp ? (int)h->log_gb : bits_for(h->max_gid_seen);  // (a log of composites: their id field as logged)
-        // (composites of up to 63 bits: a limit from the time of the library sort -- rocPRIM's radix sort mis-sorts the bit range [2, 64), found by
-        // test_any_k_against_ground_truth[31-0] -- kept: the paths behind it are the tested ones for such k)
-        if (W == 1 && h->log_g_sorted && 2 * h->k + gb <= 63 && !h->opt_no_composite) {
-            // 2c + 3c. composite path (bft_kernels_build.h): sort (T << gb | genome) on the T bits, flags on the fly, one scan
-            DevBuf cs, tmp, pos;
-            CK(cs.alloc(total * 8));
-            CK(pos.alloc(total * 8));
-            const BftCompose comp{src_k, h->log_comp ? nullptr : src_g, (uint32_t)gb};
-            // MSD first: a stable sort on the top 18 bits of T (the rotated root prefix: 2^18 buckets of ~10^3 composites on a
-            // pan-genome index), then every bucket on its own on the remaining bits, in LDS, with the duplicates flagged and counted
-            // on the way (bft_front.hip) -- one read and one write of the array instead of the four or five full passes those
-            // bits cost a device-wide LSD sort, and no flag scan over the pairs.  Skewed inputs (a bucket beyond what one workgroup
-            // sorts) keep the one-sort path.
-            const unsigned top = (unsigned)std::min(18, 2 * h->k), rest = (unsigned)(2 * h->k) - top;
-            const bool msd = h->opt_msd && (total >= (1u << 20) || h->opt_msd == 2);
-            bool done = false;
-            h->msd_max_bucket = 0;
-            if (msd) {
-                DevBuf boff, maxb;
-                CK(boff.alloc(((1u << top) + 1) * 4));
-                CK(maxb.alloc_zero(4, h->stream));
-                // (the library's own partition, bft_sort.h: one histogram kernel, a first pass that needs no look-back, a second in 64 chains;
-                // the composites are formed from the log by the kernels that read it; `pos` carries them between the two passes)
-                const uint32_t* dbase = nullptr;  // (where the last pass's digit -- the top bits of the prefix -- changes: in `tmp`)
-                CK((bft_rs::sort<uint64_t, bft_rs::NoVal, BftCompose>(comp, total, cs.as<uint64_t>(), (bft_rs::NoVal*)nullptr, pos.as<uint64_t>(), (bft_rs::NoVal*)nullptr,
-                                                                      (unsigned)gb + rest, (unsigned)(gb + 2 * h->k), h->stream, tmp, &dbase)));
-                const bft_rs::Plan spl = bft_rs::make_plan((unsigned)gb + rest, (unsigned)(gb + 2 * h->k));
-                hipLaunchKernelGGL(k_msd_bounds, dim3(((1u << top) + 1 + 255) / 256), dim3(256), 0, h->stream, cs.as<uint64_t>(), total, (uint32_t)(gb + rest), 1u << top,
-                                   boff.as<uint32_t>(), dbase, spl.P ? spl.nbits[spl.P - 1] : 0u, top);
-                hipLaunchKernelGGL(k_msd_max, dim3(((1u << top) + 255) / 256), dim3(256), 0, h->stream, boff.as<uint32_t>(), 1u << top, maxb.as<uint32_t>());
-                // (histogram: the log, 12 B per pair; pass 1: the log in, composites out; pass 2: composites in and out)
-                bft_stage("split (root-prefix, 2 x 9 bits)", (double)total * ((h->log_comp ? 8 : 12) * 2 + 8 + 8 + 8), h->stream);
-                uint32_t mx = 0;
-                CK(bft_front_buckets(cs.as<uint64_t>(), total, boff.as<uint32_t>(), 1u << top, (uint32_t)gb, (uint32_t)gb + rest, h->stream, tk, seg_off, npg, nk, np, maxb.as<uint32_t>(), &mx,
-                                     &done, &h->front_redone));
-                h->msd_max_bucket = mx;
-                if (done) pos.release();
-            }
-            if (!done) {
-            if (!pos.p) CK(pos.alloc(total * 8));
-            CK((bft_rs::sort<uint64_t, bft_rs::NoVal, BftCompose>(comp, total, cs.as<uint64_t>(), (bft_rs::NoVal*)nullptr, pos.as<uint64_t>(), (bft_rs::NoVal*)nullptr, (unsigned)gb,
-                                                                  (unsigned)(gb + 2 * h->k), h->stream, tmp)));
-            const BftPairFlags pf{cs.as<uint64_t>(), (uint32_t)gb};
-            CK((bft_scan::exclusive_sum<uint64_t>(pf, pos.as<uint64_t>(), total, h->stream, tmp)));
-            uint64_t last_pos = 0, last_c[2] = {0, 0};
-            HIPCK(hipMemcpyAsync(&last_pos, pos.as<uint64_t>() + total - 1, 8, hipMemcpyDeviceToHost, h->stream));
-            HIPCK(hipMemcpyAsync(&last_c[1], cs.as<uint64_t>() + total - 1, 8, hipMemcpyDeviceToHost, h->stream));
-            if (total > 1) HIPCK(hipMemcpyAsync(&last_c[0], cs.as<uint64_t>() + total - 2, 8, hipMemcpyDeviceToHost, h->stream));
-            HIPCK(hipStreamSynchronize(h->stream));
-            const bool last_head = total == 1 || (last_c[1] >> gb) != (last_c[0] >> gb), last_keep = total == 1 || last_c[1] != last_c[0];
-            nk = (last_pos >> 32) + (last_head ? 1 : 0);
-            np = (last_pos & 0xFFFFFFFFull) + (last_keep ? 1 : 0);
-            CK(tk.alloc(nk * 8));
-            CK(seg_off.alloc((nk + 1) * 4));
-            CK(npg.alloc(np * 4));
-            hipLaunchKernelGGL(k_scatter_c, dim3(grid_for((total + 255) / 256)), dim3(256), 0, h->stream, cs.as<uint64_t>(), (uint32_t)gb, total, pos.as<uint64_t>(),
-                               npg.as<uint32_t>(), tk.as<uint64_t>(), seg_off.as<uint32_t>());
-            const uint32_t np32 = (uint32_t)np;
-            HIPCK(hipMemcpyAsync(seg_off.as<uint32_t>() + nk, &np32, 4, hipMemcpyHostToDevice, h->stream));
-            HIPCK(hipGetLastError());
-            HIPCK(hipStreamSynchronize(h->stream));
-            }
-            ck.release();
-            cg.release();
-        } else if (W == 1 && h->log_g_sorted && !h->opt_no_composite && (h->max_gid_seen < 65536 || (2 * h->k - std::min(18, 2 * h->k)) + gb <= 64)) {
-            // 2s. ordered one-word keys whose composite does not fit (k = 31 with more than a few genomes): the root-prefix split with
-            // the ids beside the keys, then the buckets -- where the composite does fit, the bucket's number being implied
-            bool done = false;
-            h->msd_max_bucket = 0;
-            // (not at k = 32: a limit from the time of the library sort, which mis-sorted the bit range [46, 64) the split would sort -- found by
-            // tools/stress_parity.py, k = 32 with build_msd = 2; bft_rs sorts that very range for two-word keys, but k = 32 stays on its tested path)
-            if (h->opt_msd && (total >= (1u << 20) || h->opt_msd == 2) && (2 * h->k - std::min(18, 2 * h->k)) + gb <= 64 && 2 * h->k < 64) {
-                if (h->max_gid_seen < 256) CK(split_dedupe_w1<uint8_t>(h, src_k, src_g, total, gb, tk, seg_off, npg, nk, np, done));
-                else if (h->max_gid_seen < 65536) CK(split_dedupe_w1<uint16_t>(h, src_k, src_g, total, gb, tk, seg_off, npg, nk, np, done));
-                else CK(split_dedupe_w1<uint32_t>(h, src_k, src_g, total, gb, tk, seg_off, npg, nk, np, done));
-            }
-            // 2n + 3'. ... or one key + value sort over every bit with the ids narrowed to one or two bytes (the values are a third of
-            // the sort's traffic at four), flags on the fly, one scan
-            if (!done) {
-                if (h->max_gid_seen < 256) CK(sort_dedupe_w1_narrow<uint8_t>(h, src_k, src_g, total, tk, seg_off, npg, nk, np));
-                else if (h->max_gid_seen < 65536) CK(sort_dedupe_w1_narrow<uint16_t>(h, src_k, src_g, total, tk, seg_off, npg, nk, np));
-                else CK(sort_dedupe_w1_narrow<uint32_t>(h, src_k, src_g, total, tk, seg_off, npg, nk, np));
-            }
-            ck.release();
-            cg.release();
-        } else {
-        bool done2 = false;
-        if (W == 2 && h->log_g_sorted && h->opt_msd && (total >= (1u << 20) || h->opt_msd == 2)) {
-            // 2w. two-word keys (33 <= k <= 64) whose ids arrived ascending: the root-prefix split on the top 18 bits of the T-form -- moving (top 64
-            // bits, the bits below, id) --, then every bucket on its own: grouped by a hash of its key bits, only the distinct k-mers ordered (bft_front.hip)
-            DevBuf hk, items, hk2, items2, boff, maxb, scratch;
-            CK(hk.alloc(total * 8));
-            CK(items.alloc(total * sizeof(BftSplit2Val)));
-            CK(hk2.alloc(total * 8));
-            CK(items2.alloc(total * sizeof(BftSplit2Val)));
-            CK(boff.alloc(((1u << 18) + 1) * 4));
-            CK(maxb.alloc_zero(4, h->stream));
-            const BftSplit2In in2{src_k, src_k + src_stride, src_g, (uint32_t)(2 * h->k - 64)};
-            const uint32_t* dbase = nullptr;
-            CK((bft_rs::sort<uint64_t, BftSplit2Val, BftSplit2In>(in2, total, hk.as<uint64_t>(), items.as<BftSplit2Val>(), hk2.as<uint64_t>(), items2.as<BftSplit2Val>(), 46u, 64u, h->stream,
-                                                                  scratch, &dbase)));
-            hipLaunchKernelGGL(k_msd_bounds, dim3(((1u << 18) + 1 + 255) / 256), dim3(256), 0, h->stream, hk.as<uint64_t>(), total, 46u, 1u << 18, boff.as<uint32_t>(), dbase, 9u, 18u);
-            hipLaunchKernelGGL(k_msd_max, dim3(((1u << 18) + 255) / 256), dim3(256), 0, h->stream, boff.as<uint32_t>(), 1u << 18, maxb.as<uint32_t>());
-            bft_stage("split (root-prefix, 2 x 9 bits, two-word keys)", (double)total * (20 + 8 + 20 * 4), h->stream);
-            hk2.release();
-            items2.release();
-            uint32_t mx = 0;
-            CK(bft_front2_buckets(hk.as<uint64_t>(), items.p, total, boff.as<uint32_t>(), 1u << 18, h->k, h->stream, tk, seg_off, npg, nk, np, maxb.as<uint32_t>(), &mx, &done2, &h->front_redone, h->max_gid_seen));
-            h->msd_max_bucket = mx;
-        }
-        if (!done2) {
-        // 2. sort by (T, genome)
-        CK(sk.alloc(total * W * 8));
-        CK(sg.alloc(total * 4));
-        CK(bft_sort_pairs(h, src_k, src_stride, src_g, total, sk.as<uint64_t>(), total, sg.as<uint32_t>(), h->log_g_sorted, true));
-        ck.release();
-        cg.release();
-        // (the insertion log stays until the new image is committed below: a failed build loses nothing)
-        if (W == 1) {
-            // 3'. one-word keys: flags on the fly, one 64-bit scan (as on the composite path)
-            CK(dedupe_w1<uint32_t>(h, sk.as<uint64_t>(), sg.as<uint32_t>(), total, tk, seg_off, npg, nk, np));
-        } else {
-        // 3. flags, scans, compaction
-        DevBuf head, keep, posK, posP, tmp;
-        CK(head.alloc(total * 4));
-        CK(keep.alloc(total * 4));
-        CK(posK.alloc(total * 4));
-        CK(posP.alloc(total * 4));
-        const int grid = grid_for((total + 255) / 256);
-        hipLaunchKernelGGL(k_flags, dim3(grid), dim3(256), 0, h->stream, sk.as<uint64_t>(), total, W, sg.as<uint32_t>(), total, head.as<uint32_t>(), keep.as<uint32_t>());
-        CK(bft_scan::exclusive_sum_ptr<uint32_t>(head.as<uint32_t>(), posK.as<uint32_t>(), total, h->stream, tmp));
-        DevBuf tmp2;  // (a scratch of its own: the first scan may still be running on the stream)
-        CK(bft_scan::exclusive_sum_ptr<uint32_t>(keep.as<uint32_t>(), posP.as<uint32_t>(), total, h->stream, tmp2));
-        uint32_t lastK[2], lastP[2];
-        HIPCK(hipMemcpyAsync(&lastK[0], posK.as<uint32_t>() + total - 1, 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCK(hipMemcpyAsync(&lastK[1], head.as<uint32_t>() + total - 1, 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCK(hipMemcpyAsync(&lastP[0], posP.as<uint32_t>() + total - 1, 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCK(hipMemcpyAsync(&lastP[1], keep.as<uint32_t>() + total - 1, 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCK(hipStreamSynchronize(h->stream));
-        nk = (uint64_t)lastK[0] + lastK[1];
-        np = (uint64_t)lastP[0] + lastP[1];
-        CK(tk.alloc(nk * W * 8));
-        CK(seg_off.alloc((nk + 1) * 4));
-        CK(npg.alloc(np * 4));
-        hipLaunchKernelGGL(k_scatter, dim3(grid), dim3(256), 0, h->stream, sk.as<uint64_t>(), total, W, sg.as<uint32_t>(), total,
-                           head.as<uint32_t>(), keep.as<uint32_t>(), posK.as<uint32_t>(), posP.as<uint32_t>(), npg.as<uint32_t>(), tk.as<uint64_t>(),
-                           seg_off.as<uint32_t>());
-        const uint32_t np32 = (uint32_t)np;
-        HIPCK(hipMemcpyAsync(seg_off.as<uint32_t>() + nk, &np32, 4, hipMemcpyHostToDevice, h->stream));
-        HIPCK(hipGetLastError());
-        HIPCK(hipStreamSynchronize(h->stream));
-        }
-        }
-        }
-    }
+    // 1-3. the run: what was inserted since the last build, sorted and de-duplicated (bft_run.hip)
+    BftRunOut img;      // built aside, like every array of the new image
+    BftBuildSide side;  // (declared behind img: the k-mer hash fill and the interning's tail are waited for before the arrays they read go)
+    BftPairRun& run = side.lists;
+    CK(bft_make_run(h, run));
     bft_trace_mark("sort + dedupe done");
     bft_stage("sort + dedupe (rest)", 0, h->stream);
-    double t1 = bft_now_ms();
+    const double t1 = bft_now_ms();
 
     // 4. colour sets: signature sort + exact run detection + verification, all on the GPU
-    uint64_t n_sets = 0, n_ids = 0;
-    if (nk == 0) {
-        CK(seg_off.alloc_zero(4, h->stream));
-        CK(npg.alloc(4));
+    img.tk.swap(run.tk);
+    img.n = run.nk;
+    if (img.n == 0) {
+        CK(run.seg_off.alloc_zero(4, h->stream));
+        CK(run.ids.alloc(4));
     }
-    DevBuf n_tcol, n_cs_off, n_cs_ids;  // built aside, like every array of the new image
-    KhFill khf;  // the k-mer hash, filled beside the container assembly
-    if (!h->stream2 && nk > 0) {  // (the second stream, made here: the helper thread below and the interning's tail both use it)
-        int lo = 0, hi = 0;  // (numerically larger = lower priority)
-        if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) { lo = 0; (void)hipGetLastError(); }
-        if (hipStreamCreateWithPriority(&h->stream2, hipStreamNonBlocking, lo) != hipSuccess) { h->stream2 = nullptr; (void)hipGetLastError(); }
-    }
-    if (!(h->built && h->n_kmers > 0) && nk > 0) {  // (a merge changes the k-mers: kh_start does everything then)
-        // (the table's sort by home line started HERE, beside the colour-set interning, was measured: the interning's persistent grids and the
-        // sort starve each other -- 4.1 -> 10.5 ms for the interning, 20 -> 25.8 ms for the build; it starts behind the assembly's table passes)
-        kh_prepare_async(h, nk, nk, khf);
-    }
+    // (the second stream, made here: the helper thread below and the interning's tail both use it)
+    if (img.n > 0) (void)ensure_stream2(h);
+    const bool merging = h->built && h->n_kmers > 0 && img.n > 0;
+    // (the table's sort by home line started HERE, beside the colour-set interning, was measured: the interning's persistent grids and the
+    // sort starve each other -- 4.1 -> 10.5 ms for the interning, 20 -> 25.8 ms for the build; it starts behind the assembly's table passes)
+    if (img.n > 0 && !merging) kh_prepare_async(h, img.n, img.n, side.khf);  // (a merge changes the k-mers: kh_start does everything then)
     // (the interning's tail -- dictionary copy + verification of every list -- goes to the second stream, idle until the k-mer hash build starts
     // behind the first level's table passes; its verdict is collected before the commit.  A merge reads the dictionary at once: not deferred.)
-    const bool merging = h->built && h->n_kmers > 0 && nk > 0;
-    BftInternTail tail;
-    tail.side = merging ? nullptr : h->stream2;
-    tail.narrow_w = id_width(h->max_gid_seen);  // (the tail also leaves the dictionary in the width the image keeps)
-    CK(bft_intern_colors_gpu(seg_off.as<uint32_t>(), npg.as<uint32_t>(), nk, np, h->stream, n_tcol, n_cs_off, n_cs_ids, n_sets, n_ids, 0, &tail));
+    side.tail.side = merging ? nullptr : h->stream2;
+    side.tail.narrow_w = id_width(h->max_gid_seen);  // (the tail also leaves the dictionary in the width the image keeps)
+    CK(bft_intern_colors_gpu(run.seg_off.as<uint32_t>(), run.ids.as<uint32_t>(), run.nk, run.np, h->stream, img.tcol, img.cs_off, img.cs_ids, img.n_sets, img.n_ids, 0, &side.tail));
     bft_trace_mark("colour sets interned");
     bft_stage("colour sets (rest)", 0, h->stream);
-    if (!tail.pending) {
-        seg_off.release();
-        npg.release();
+    if (!side.tail.pending) {
+        run.seg_off.release();
+        run.ids.release();
     }
     // 4b. an index exists already: the run is merged into it (bft_merge.hip) -- k-mers by position, colour sets by union
-    uint64_t total_pairs = np;
-    if (h->built && h->n_kmers > 0 && nk > 0) {
+    uint64_t total_pairs = run.np;
+    if (merging) {
         DevBuf wide;
         const uint32_t* old_ids = nullptr;
         CK(widen_ids(h->d_cs_ids, h->n_ids, h->cs_w, h->stream, wide, &old_ids));
         const BftRun old_run{h->d_tk.as<uint64_t>(), h->d_tcol.as<uint32_t>(), h->n_kmers, h->d_cs_off.as<uint32_t>(), old_ids, h->n_sets};
-        const BftRun new_run{tk.as<uint64_t>(), n_tcol.as<uint32_t>(), nk, n_cs_off.as<uint32_t>(), n_cs_ids.as<uint32_t>(), n_sets};
+        const BftRun new_run{img.tk.as<uint64_t>(), img.tcol.as<uint32_t>(), img.n, img.cs_off.as<uint32_t>(), img.cs_ids.as<uint32_t>(), img.n_sets};
         BftRunOut mo;
-        CK(bft_merge_runs(W, old_run, new_run, h->stream, mo));
-        tk.swap(mo.tk);
-        n_tcol.swap(mo.tcol);
-        n_cs_off.swap(mo.cs_off);
-        n_cs_ids.swap(mo.cs_ids);
-        nk = mo.n;
-        n_sets = mo.n_sets;
-        n_ids = mo.n_ids;
-        CK(bft_count_pairs(n_tcol.as<uint32_t>(), nk, n_cs_off.as<uint32_t>(), h->stream, &total_pairs));
+        CK(bft_merge_runs(h->W, old_run, new_run, h->stream, mo));
+        img.swap(mo);
+        CK(bft_count_pairs(img.tcol.as<uint32_t>(), img.n, img.cs_off.as<uint32_t>(), h->stream, &total_pairs));
     }
-    np = total_pairs;
     bft_trace_mark("merge / bookkeeping");
     bft_stage("merge into the index", 0, h->stream);
-    return bft_commit_image(h, tk, n_tcol, n_cs_off, n_cs_ids, nk, n_sets, n_ids, np, khf, tail, seg_off, npg, t0, t1);
+    return bft_commit_image(h, img, total_pairs, t0, t1, &side);
 }
 
 int bft_ensure_built(bft_gpu* h, bool need_table) {

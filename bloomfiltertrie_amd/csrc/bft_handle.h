@@ -1,5 +1,5 @@
 // bft_handle.h -- the handle behind the C-ABI (struct bft_gpu) and the host helpers every entry point needs, for the translation units that hold
-// entry points: bft_gpu.hip (which defines the helpers) and the analysis families bft_prefix.hip, bft_paths.hip, bft_components.hip, bft_pangenome.hip,
+// entry points: bft_gpu.hip (which defines the helpers), bft_run.hip (the build's run stage) and the analysis families bft_prefix.hip, bft_paths.hip, bft_components.hip, bft_pangenome.hip,
 // bft_subgraph.hip, bft_marking.hip, bft_setops.hip, bft_union.hip, bft_ingest.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -296,7 +296,7 @@ struct StageScope {
 
 // presence bits (and rows, or colour sets with im.emit_cs) of n packed k-mers on stream s, by whichever of the k-mer hash and the walk answers
 int bft_launch_query(bft_gpu* h, const uint8_t* d_kmers, uint64_t n, uint64_t* d_bits64, uint32_t* d_rows, hipStream_t s, int rec_bytes = 0);
-// Stable LSD sort of `total` entries by (keys word 0..W-1 as one big integer, then g) on the handle's stream, synchronised.  keys: SoA with stride `stride`; result in okeys (stride ostride) / og.
+// (bft_run.hip) Stable LSD sort of `total` entries by (keys word 0..W-1 as one big integer, then g) on the handle's stream, synchronised.  keys: SoA with stride `stride`; result in okeys (stride ostride) / og.
 int bft_sort_pairs(bft_gpu* h, const uint64_t* keys, uint64_t stride, const uint32_t* g, uint64_t total, uint64_t* okeys, uint64_t ostride, uint32_t* og,
                    bool g_already_ordered, bool is_log = false);
 
@@ -324,9 +324,12 @@ struct KhFill {
         if (ew) (void)hipEventDestroy(ew);
     }
 };
-// Steps 5-7 of a build, from the point where the sorted table tk (nk rows), the colour set per row n_tcol and the dictionary n_cs_off / n_cs_ids
-// (32-bit ids) are final: containers, flat forms, k-mer hash (on the second stream), narrowing, commit into h, root tables.  Shared by
-// bft_gpu_build and bft_gpu_subgraph.  khf: the k-mer hash fill (prepared or not); tail / seg_off / npg: the interning's deferred tail and
-// its input (a default tail -- nothing pending -- where there was no interning); t0 / t1: start and end of the sort (bft_gpu_build_time).
-int bft_commit_image(bft_gpu* h, DevBuf& tk, DevBuf& n_tcol, DevBuf& n_cs_off, DevBuf& n_cs_ids, uint64_t nk, uint64_t n_sets, uint64_t n_ids, uint64_t np,
-                     KhFill& khf, BftInternTail& tail, DevBuf& seg_off, DevBuf& npg, double t0, double t1);
+// What only bft_gpu_build carries into the commit: the run's genome-id lists (the input of the interning: its deferred tail reads them, and the exact
+// interning runs on them again where two lists shared a signature), the k-mer hash fill it prepared, and that tail.  (In this order: the fill and
+// the tail are waited for by their destructors before the lists they read go back to the cache.)
+struct BftBuildSide { BftPairRun lists; KhFill khf; BftInternTail tail; };
+// Steps 5-7 of a build, from the point where the image-to-be img -- the sorted table, the colour set per row, the dictionary (32-bit ids), their
+// counts -- is final: containers, flat forms, k-mer hash (on the second stream), narrowing, commit into h, root tables.  Shared by bft_gpu_build,
+// bft_gpu_subgraph and bft_gpu_merge.  np: the (k-mer, genome) pairs img holds; side: null where nothing was interned or prepared (a default
+// one then: nothing pending); t0 / t1: start and end of the sort (bft_gpu_build_time).
+int bft_commit_image(bft_gpu* h, BftRunOut& img, uint64_t np, double t0, double t1, BftBuildSide* side = nullptr);

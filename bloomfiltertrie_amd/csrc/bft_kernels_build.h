@@ -1,15 +1,7 @@
-// bft_kernels_build.h -- de-duplication of the sorted (k-mer, genome) pairs for the bulk build: k_iota, k_gather, k_flags, k_scatter
-// Device code of libbft_gpu.so, included by bft_gpu.hip only (one translation unit: the kernels are templates launched from
-// the host code there).
+// bft_kernels_build.h -- de-duplication of the sorted (k-mer, genome) pairs for the bulk build: k_iota, k_gather, k_flags, k_scatter, the
+// root-prefix bucket bounds, the on-the-fly scatters.  Device code of libbft_gpu.so, included by bft_run.hip only (one translation unit: the
+// kernels are launched from the host code there; the sort and scan inputs that go with them: bft_run.h).
 #pragma once
-// a log of composites back into T-form k-mers and their ids (in place + the id array)
-__global__ void k_log_decompose(uint64_t* __restrict__ log_k, uint64_t n, uint32_t cgb, uint32_t* __restrict__ log_g) {
-    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t c = log_k[i];
-        log_g[i] = (uint32_t)(c & ((1ull << cgb) - 1ull));
-        log_k[i] = c >> cgb;
-    }
-}
 __global__ void k_iota(uint32_t* p, uint64_t n) {
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) p[i] = (uint32_t)i;
 }
@@ -63,53 +55,6 @@ __global__ void k_scatter(const uint64_t* __restrict__ keys, uint64_t stride, in
     }
 }
 
-// ---- composite path: one-word keys whose genome ids arrive in ascending order and fit the key's spare low bits ----------------
-// c = (T << gb) | genome: ONE 8-byte array is sorted (on the T bits only: the sort is stable, so the ids keep their ascending
-// order inside a k-mer) instead of 8-byte keys + 4-byte values -- a third less traffic in each of the seven radix passes -- and the
-// de-duplication flags come out of neighbouring composites on the fly instead of through two flag arrays and two scans.
-struct BftCompose {  // input "iterator" of the sort: composite i from the insertion log
-    const uint64_t* k;
-    const uint32_t* g;
-    uint32_t gb;
-    __host__ __device__ uint64_t operator()(uint32_t i) const { return g ? (k[i] << gb) | (uint64_t)g[i] : k[i]; }  // (g == NULL: the log already holds composites)
-    __device__ uint64_t key(uint32_t i) const { return (*this)(i); }  // (as the input of bft_rs::sort)
-    __device__ bft_rs::NoVal val(uint32_t) const { return bft_rs::NoVal{}; }
-};
-// two-word keys: what the root-prefix split moves -- the top 64 bits of the T-form (left-aligned: their top 18 bits are the root prefix) as the
-// key, the bits below them and the genome id as the value (bft_front.hip: BftItem2)
-struct __attribute__((packed, aligned(4))) BftSplit2Val {
-    uint64_t lo;
-    uint32_t id;
-};
-struct BftSplit2In {
-    const uint64_t* k0;  // word 0 (most significant), word 1 of the log
-    const uint64_t* k1;
-    const uint32_t* g;
-    uint32_t sh;  // 2k - 64: the bits of word 1 that belong to the T-form's low part once the top 64 are taken (2 .. 64)
-    __device__ uint64_t key(uint32_t i) const { return sh == 64 ? k0[i] : (k0[i] << (64 - sh)) | (k1[i] >> sh); }
-    __device__ BftSplit2Val val(uint32_t i) const {
-        BftSplit2Val v;
-        v.lo = sh == 64 ? k1[i] : (k1[i] & ((1ull << sh) - 1ull));
-        v.id = g[i];
-        return v;
-    }
-};
-template <class GT>
-struct BftPairIn {  // input of the sorts that move (k-mer, id) pairs: the log's k-mers, its ids narrowed to GT
-    const uint64_t* k;
-    const uint32_t* g;
-    __device__ uint64_t key(uint32_t i) const { return k[i]; }
-    __device__ GT val(uint32_t i) const { return (GT)g[i]; }
-};
-struct BftPairFlags {  // input of the scan: (first pair of its k-mer) << 32 | (first pair of its (k-mer, genome))
-    const uint64_t* c;
-    uint32_t gb;
-    __host__ __device__ uint64_t operator()(uint32_t i) const {
-        const uint64_t a = c[i], b = i ? c[i - 1] : ~a;
-        const uint64_t head = (a >> gb) != (b >> gb), keep = a != b;
-        return (head << 32) | keep;
-    }
-};
 // root-prefix buckets of the composites sorted on their top bits: off[r] = first composite whose prefix is >= r (r = 0..nb), and the
 // size of the largest bucket.  dbase (optional): where the top `dbits` bits of the prefix change -- the last pass of the sort that made the
 // order left that table behind (bft_rs::sort, last_dbase) --: a bucket is then searched inside its digit's stretch (19 steps instead of 28
@@ -143,6 +88,7 @@ __global__ void k_msd_max(const uint32_t* __restrict__ off, uint32_t nb, uint32_
         if (m) atomicMax(max_bucket, m);
     }
 }
+// sorted composites (BftCompose, bft_run.h) and the scan of their flags (BftPairFlags) -> genome-id lists, distinct k-mers, segment offsets
 __global__ void k_scatter_c(const uint64_t* __restrict__ c, uint32_t gb, uint64_t n, const uint64_t* __restrict__ pos, uint32_t* __restrict__ pg,
                             uint64_t* __restrict__ tk, uint32_t* __restrict__ seg_off) {
     const uint64_t gmask = (1ull << gb) - 1ull;
@@ -159,11 +105,6 @@ __global__ void k_scatter_c(const uint64_t* __restrict__ c, uint32_t gb, uint64_
 
 // The same on-the-fly flags for sorted one-word keys with their genome ids in a second array (the general sort's output).  GT: the
 // width the ids were sorted at (uint8_t / uint16_t when every id fits: the values are a third of the sort's traffic at 4 bytes).
-template <class GT>
-struct BftNarrowIds {  // value "iterator" of that sort: genome id i of the log, narrowed
-    const uint32_t* g;
-    __host__ __device__ GT operator()(uint32_t i) const { return (GT)g[i]; }
-};
 template <class GT>
 struct BftPairFlags2 {
     const uint64_t* k;

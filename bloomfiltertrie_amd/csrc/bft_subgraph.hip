@@ -207,8 +207,7 @@ static int subgraph_fill(bft_gpu* src, bft_gpu* d, const uint8_t* d_kmers, uint6
     if (n_absent) *n_absent = n - m;
 
     // 3. order (the library's sort, keys only: equal keys carry equal ids) and de-duplication (first record of every run: one scan)
-    DevBuf tk, tcol;
-    uint64_t nk = 0;
+    BftRunOut img;  // the new handle's table, colour set per row and dictionary
     if (m) {
         DevBuf sk, sg, pos, tmp;
         CK(sk.alloc(m * W * 8));
@@ -222,19 +221,19 @@ static int subgraph_fill(bft_gpu* src, bft_gpu* d, const uint8_t* d_kmers, uint6
         uint32_t nk32 = 0;
         HIPCK(hipMemcpyAsync(&nk32, pos.as<uint32_t>() + m, 4, hipMemcpyDeviceToHost, ds));
         HIPCK(hipStreamSynchronize(ds));
-        nk = nk32;
-        CK(tk.alloc(nk * W * 8));
-        CK(tcol.alloc(nk * 4));
-        CK(bft_timed_launch(src, ds, [&] { return bft_sg_scatter(W, sk.as<uint64_t>(), m, sg.as<uint32_t>(), m, pos.as<uint32_t>(), tk.as<uint64_t>(), tcol.as<uint32_t>(), ds); }));
+        img.n = nk32;
+        CK(img.tk.alloc(img.n * W * 8));
+        CK(img.tcol.alloc(img.n * 4));
+        CK(bft_timed_launch(src, ds, [&] { return bft_sg_scatter(W, sk.as<uint64_t>(), m, sg.as<uint32_t>(), m, pos.as<uint32_t>(), img.tk.as<uint64_t>(), img.tcol.as<uint32_t>(), ds); }));
         HIPCK(hipStreamSynchronize(ds));
     } else {
-        CK(tcol.alloc(4));
+        CK(img.tcol.alloc(4));
     }
+    const uint64_t nk = img.n;
     bft_stage("sub-graph: sort + dedupe", (double)m * (8 * W + 4) * 6 + (double)nk * (8 * W + 4), ds);
 
     // 4. the dictionary: the used sets of the source in their old order (colours), or the one set {0}
-    DevBuf cs_off, cs_ids;
-    uint64_t n_sets = 0, n_ids = 0, np = 0;
+    uint64_t np = 0;
     if (nk && colors) {
         const uint64_t S = src->n_sets;
         DevBuf used, new_id, id_pos, tmp;
@@ -242,7 +241,7 @@ static int subgraph_fill(bft_gpu* src, bft_gpu* d, const uint8_t* d_kmers, uint6
         CK(new_id.alloc((S + 1) * 4));
         CK(id_pos.alloc((S + 1) * 4));
         const uint32_t* old_off = src->d_cs_off.as<uint32_t>();
-        CK(bft_timed_launch(src, ds, [&] { return bft_sg_mark(tcol.as<uint32_t>(), nk, used.as<uint32_t>(), ds); }));
+        CK(bft_timed_launch(src, ds, [&] { return bft_sg_mark(img.tcol.as<uint32_t>(), nk, used.as<uint32_t>(), ds); }));
         CK(bft_timed_launch(src, ds, [&] { return bft_scan::exclusive_sum_ptr<uint32_t>(used.as<uint32_t>(), new_id.as<uint32_t>(), S, ds, tmp, nullptr, true); }));
         const BftSgUsedLen lens{used.as<uint32_t>(), old_off, S};
         CK(bft_timed_launch(src, ds, [&] { return bft_scan::exclusive_sum<uint32_t>(lens, id_pos.as<uint32_t>(), S, ds, tmp, nullptr, true); }));
@@ -250,39 +249,36 @@ static int subgraph_fill(bft_gpu* src, bft_gpu* d, const uint8_t* d_kmers, uint6
         HIPCK(hipMemcpyAsync(&tot[0], new_id.as<uint32_t>() + S, 4, hipMemcpyDeviceToHost, ds));
         HIPCK(hipMemcpyAsync(&tot[1], id_pos.as<uint32_t>() + S, 4, hipMemcpyDeviceToHost, ds));
         HIPCK(hipStreamSynchronize(ds));
-        n_sets = tot[0];
-        n_ids = tot[1];
-        CK(cs_off.alloc((n_sets + 1) * 4));
-        CK(cs_ids.alloc(n_ids * 4));
-        CK(bft_timed_launch(src, ds, [&] { return bft_sg_remap(tcol.as<uint32_t>(), nk, new_id.as<uint32_t>(), ds); }));
+        img.n_sets = tot[0];
+        img.n_ids = tot[1];
+        CK(img.cs_off.alloc((img.n_sets + 1) * 4));
+        CK(img.cs_ids.alloc(img.n_ids * 4));
+        CK(bft_timed_launch(src, ds, [&] { return bft_sg_remap(img.tcol.as<uint32_t>(), nk, new_id.as<uint32_t>(), ds); }));
         CK(bft_timed_launch(src, ds, [&] {
-            return bft_sg_dict(used.as<uint32_t>(), new_id.as<uint32_t>(), id_pos.as<uint32_t>(), old_off, src->d_cs_ids.p, src->cs_w, S, cs_off.as<uint32_t>(),
-                               cs_ids.as<uint32_t>(), ds);
+            return bft_sg_dict(used.as<uint32_t>(), new_id.as<uint32_t>(), id_pos.as<uint32_t>(), old_off, src->d_cs_ids.p, src->cs_w, S, img.cs_off.as<uint32_t>(),
+                               img.cs_ids.as<uint32_t>(), ds);
         }));
-        CK(bft_count_pairs(tcol.as<uint32_t>(), nk, cs_off.as<uint32_t>(), ds, &np));
-        bft_stage("sub-graph: used part of the dictionary", (double)nk * 12 + (double)S * 16 + (double)n_ids * (src->cs_w + 4), ds);
+        CK(bft_count_pairs(img.tcol.as<uint32_t>(), nk, img.cs_off.as<uint32_t>(), ds, &np));
+        bft_stage("sub-graph: used part of the dictionary", (double)nk * 12 + (double)S * 16 + (double)img.n_ids * (src->cs_w + 4), ds);
     } else if (nk) {
         static const uint32_t one_set[3] = {0, 1, 0};  // cs_off = {0, 1}, cs_ids = {0}
-        CK(cs_off.alloc(8));
-        CK(cs_ids.alloc(4));
-        HIPCK(hipMemsetAsync(tcol.p, 0, nk * 4, ds));
-        HIPCK(hipMemcpyAsync(cs_off.p, one_set, 8, hipMemcpyHostToDevice, ds));
-        HIPCK(hipMemcpyAsync(cs_ids.p, one_set + 2, 4, hipMemcpyHostToDevice, ds));
-        n_sets = 1;
-        n_ids = 1;
+        CK(img.cs_off.alloc(8));
+        CK(img.cs_ids.alloc(4));
+        HIPCK(hipMemsetAsync(img.tcol.p, 0, nk * 4, ds));
+        HIPCK(hipMemcpyAsync(img.cs_off.p, one_set, 8, hipMemcpyHostToDevice, ds));
+        HIPCK(hipMemcpyAsync(img.cs_ids.p, one_set + 2, 4, hipMemcpyHostToDevice, ds));
+        img.n_sets = 1;
+        img.n_ids = 1;
         np = nk;
     } else {
-        CK(cs_off.alloc_zero(4, ds));
-        CK(cs_ids.alloc(4));
+        CK(img.cs_off.alloc_zero(4, ds));
+        CK(img.cs_ids.alloc(4));
     }
     HIPCK(hipStreamSynchronize(ds));
     const double t1 = bft_now_ms();
 
     // 5-7. containers, flat forms, k-mer hash, root tables, commit: the build's own tail
-    KhFill khf;
-    BftInternTail tail;  // (nothing deferred: no interning here)
-    DevBuf seg_off, npg;
-    return bft_commit_image(d, tk, tcol, cs_off, cs_ids, nk, n_sets, n_ids, np, khf, tail, seg_off, npg, t0, t1);
+    return bft_commit_image(d, img, np, t0, t1);  // (nothing deferred: no interning here)
 }
 
 static int subgraph_new(bft_gpu* src, const uint8_t* d_kmers, uint64_t n, int colors, uint64_t* n_absent, bft_gpu** out, hipStream_t s) {

@@ -358,10 +358,7 @@ int merge_fill(bft_gpu* a, bft_gpu* b, uint32_t id_base, bft_gpu* d) {
     bft_stage("merge: pairs counted", (double)mo.n * 12, ds);
     const double t1 = bft_now_ms();
 
-    KhFill khf;
-    BftInternTail tail;  // (nothing deferred: the merge interns on its own stream)
-    DevBuf seg_off, npg;
-    return bft_commit_image(d, mo.tk, mo.tcol, mo.cs_off, mo.cs_ids, mo.n, mo.n_sets, mo.n_ids, np, khf, tail, seg_off, npg, t0, t1);
+    return bft_commit_image(d, mo, np, t0, t1);  // (nothing deferred: the merge interns on its own stream)
 }
 
 }  // namespace
