@@ -1,5 +1,5 @@
 // bft_color_plan.h -- how a batch of colour rows is cut into tiles, and the magic number of the division by the row width: host code only,
-// shared by launch_color_rows (bft_gpu.hip: k_color_rows_bm<false>, k_color_rows_bm<true>, k_color_rows_bm16) and bft_kh_color_rows
+// shared by launch_color_rows (bft_query.hip: k_color_rows_bm<false>, k_color_rows_bm<true>, k_color_rows_bm16) and bft_kh_color_rows
 // (bft_kh.hip: k_color_rows_kh), and readable without a device through bft_gpu_debug_color_rows_plan (tests/test_colour_cases_host.py checks the
 // division over every byte offset a tile can hold, and the bounds the kernels' LDS arrays rely on).
 #pragma once

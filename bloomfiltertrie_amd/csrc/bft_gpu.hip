@@ -1,22 +1,15 @@
-// bft_gpu.hip -- the C-ABI of include/bft_gpu.h: handle (bft_handle.h), device-memory cache, insertion log, bulk build (its run stage: bft_run.hip), k-mer and sequence query entry
-// points, residency / probe tuning, .bft files, image replication (prefixes, sub-graphs, paths, components: beside their kernels).  With its device code:
+// bft_gpu.hip -- the C-ABI of include/bft_gpu.h: handle (bft_handle.h), device-memory cache, insertion log, bulk build (its run stage: bft_run.hip), image
+// binding and commit with the derived tables, .bft files, image replication, options and info.  The k-mer and sequence queries, their tuner and the claim
+// slots are bft_query.hip; prefixes, sub-graphs, paths, components and the other analysis families sit beside their kernels.  Device code from
 //   bft_kernels_query.h  k_pack_to_tform (packed 2-bit k-mers -> T-form words: the per-level rev[]/rotation work of
-//                        src/presenceNode.c:1327-1371 done once per k-mer), k_query_kh / k_branching_kh (the same queries through the
-//                        k-mer hash: one cache line per k-mer), k_query / k_query8 / k_query6 (batched isKmerPresent as a container walk,
-//                        src/presenceNode.c:1823-1921: one lane per k-mer, coalesced dword loads of the batch, hash table + root
-//                        Bloom block + root CC headers staged in LDS, 64 presence bits per wavefront via __ballot),
-//                        k_branching / k_branching8 (src/branchingNode.c)
-//   bft_kernels_seq.h    query_sequence (src/bft.c:1241-1351) around k_query
-//   bft_kernels_color.h  batched get_annotation + get_list_id_genomes (src/bft.c:363-387, 622-641)
-//   bft_walk.h           the per-k-mer walk itself (shared with the host-side test helper)
-// The bulk build turns the log into a sorted, de-duplicated run in bft_run.hip (the library's own sort and scan: bft_sort.h, bft_scan.h -- here
-// only for the test hooks at the end); colour-set interning and container assembly are the kernels of bft_assemble.hip -- see DESIGN.md "Insertion".
+//                        src/presenceNode.c:1327-1371 done once per k-mer)
+//   bft_walk.h           the per-k-mer walk (the root tables are derived with it)
+// The bulk build turns the log into a sorted, de-duplicated run in bft_run.hip (the library's own sort and scan: bft_sort.h, bft_scan.h);
+// colour-set interning and container assembly are the kernels of bft_assemble.hip -- see DESIGN.md "Insertion".
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <chrono>
-#include <cmath>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -24,16 +17,11 @@
 #include <vector>
 
 #include "../../include/bft_gpu.h"
-#include "bft_dev.h"
+#include "bft_color_plan.h"
 #include "bft_file.h"
 #include "bft_handle.h"
 #include "bft_hash.h"
-#include "bft_image.h"
 #include "bft_index.h"
-#include "bft_kh.h"
-#include "bft_paths.h"
-#include "bft_run.h"
-#include "bft_scan.h"
 #include "bft_sort.h"
 #include "bft_walk.h"
 
@@ -43,8 +31,6 @@
 // (the reference's own annotation codec holds 6 bits per byte, include/log2.h:45-50: 2^24 ids already take 4-byte entries).
 #define BFT_MAX_GENOME_ID (1u << 24)
 
-thread_local bft_rs::RunRecord bft_rs::g_bft_rs_last;  // what this thread's last library sort ran (test hooks: bft_gpu_test_sort_last)
-int bft_rs::g_bft_rs_rank_mode = -1;  // how bft_sort.h ranks: 0 LDS atomics (lane order checked on the device), 1 ballots ("sort_ballots")
 static thread_local std::string g_err;
 int bft_fail(int code, const std::string& msg) {
     g_err = msg;
@@ -86,10 +72,7 @@ void bft_stage(const char* name, double bytes, hipStream_t s) {
     t_stage_marks.push_back({name, bytes, ev});
 }
 
-// device code, by topic
-#include "bft_kernels_query.h"
-#include "bft_kernels_seq.h"
-#include "bft_kernels_color.h"
+#include "bft_kernels_query.h"  // k_pack_to_tform
 // ------------------------------------------------------------------------------------------------
 // device-memory cache (see bft_dev.h)
 // ------------------------------------------------------------------------------------------------
@@ -251,8 +234,6 @@ extern "C" uint64_t bft_gpu_cache_release(void) {
 // handle (struct bft_gpu: bft_handle.h)
 // ------------------------------------------------------------------------------------------------
 static int grid_for(uint64_t nblk) { return bft_grid_for(nblk); }
-// rows per probe block of the suffix-group search ("query_probe": 4 or 8) -> BftImage::probe_big
-static uint32_t probe_mode(int rows) { return rows == 8 ? 1u : 0u; }
 
 int bft_set_device(bft_gpu* h) {
     HIPCK(hipSetDevice(h->device));
@@ -583,8 +564,6 @@ static uint64_t image_bytes(const bft_gpu* h) {
            h->d_f18.bytes + h->d_fent.bytes + h->d_rdir.bytes + h->d_rstart.bytes + h->d_rq.bytes + h->d_nph.bytes + h->d_kh.bytes + h->d_rspec.bytes + h->d_kh_ovf_k.bytes + h->d_kh_ovf_v.bytes;
 }
 
-static int tune_residency(bft_gpu* h);
-static void ensure_claim_counters(bft_gpu* h);
 
 // Points h->im at the device arrays of the handle (cannot fail).
 static void point_image(bft_gpu* h, uint32_t nb_genomes) {
@@ -630,7 +609,7 @@ static void point_image(bft_gpu* h, uint32_t nb_genomes) {
     im.emit_cs = 0;
     h->tuned_wgs = 0;
     h->tuned_probe = 0;
-    h->im.probe_big = probe_mode(h->opt_probe);
+    h->im.probe_big = bft_probe_mode(h->opt_probe);
 }
 
 // Root direct table: one thread per 18-bit prefix evaluates the root level's Bloom probe + CC lookup on the bound image.
@@ -981,7 +960,7 @@ static void default_launch_shape(bft_gpu* h) {
     // (rows per ROOT prefix: the groups most queries end in hang off the root; deeper levels add prefixes, not rows)
     const uint64_t prefixes = std::max<uint64_t>(1, std::min<uint64_t>(h->info[6], 1ull << 18));
     h->tuned_probe = h->n_kmers / prefixes >= 48 ? 8 : 4;
-    h->im.probe_big = probe_mode(h->opt_probe ? h->opt_probe : h->tuned_probe);
+    h->im.probe_big = bft_probe_mode(h->opt_probe ? h->opt_probe : h->tuned_probe);
     if (h->opt_root_direct == 3 && h->rstart_ok) {
         h->tuned_rstart = h->info[5] * 4 < (1u << 18) ? 1 : 0;
         h->im.rstart = h->tuned_rstart ? h->d_rstart.as<uint32_t>() : nullptr;
@@ -1023,7 +1002,7 @@ static void derive_root_direct(bft_gpu* h) {
     hipLaunchKernelGGL(k_root_ranges_check, g, b, 0, h->stream, h->im.rdir, h->d_rstart.as<uint32_t>());
     if (hipGetLastError() != hipSuccess) return;  // (no wait here: the stream is synchronised below, or by whoever uses the tables next)
     h->rstart_ok = true;
-    h->im.rstart = h->d_rstart.as<uint32_t>();  // (mode 3: tune_residency decides whether it stays)
+    h->im.rstart = h->d_rstart.as<uint32_t>();  // (mode 3: bft_tune_residency decides whether it stays)
     h->rq_ok = false;
     if (!h->opt_root_quartiles || h->L < 2 || (h->d_rq.bytes < (4u << 18) && h->d_rq.alloc(4u << 18) != 0)) {
         if (hipStreamSynchronize(h->stream) != hipSuccess) { h->im.rdir = nullptr; h->im.rstart = nullptr; h->rstart_ok = false; }
@@ -1274,7 +1253,7 @@ int bft_commit_image(bft_gpu* h, BftRunOut& img, uint64_t np, double t0, double 
     h->build_ms[2] = t3 - t2;
     h->build_ms[3] = (double)h->front_redone;
     h->built = true;
-    ensure_claim_counters(h);
+    h->claims.ensure();
     bft_trace_mark("committed (buffers released)");
     derive_root_direct(h);
     if (kh_ok) kh_adopt(h, khf, kh_ms);  // built during the assembly
@@ -1366,813 +1345,6 @@ int bft_ensure_built(bft_gpu* h, bool need_table) {
     if (!h->built || h->log_n) CK(bft_gpu_build(h));
     if (need_table) CK(bft_ensure_table(h));
     return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// queries
-// ------------------------------------------------------------------------------------------------
-// Resident k_query workgroups per CU.  Measured on MI355X (tools/perf_probe.py): a one-level index whose suffix-group
-// table exceeds the L2 runs at the beyond-L2 gather rate with 4 waves per SIMD and loses 10 % with 8; deep walks and
-// L2-resident indexes gain 10-40 % from 8; which side an index falls on is measured, not guessed (tune_residency).
-static int query_residency(const bft_gpu* h) {
-    if (h->opt_wgs_per_cu) return h->opt_wgs_per_cu;
-    return h->tuned_wgs ? h->tuned_wgs : 2;
-}
-
-static BftClaimCtr claim_counters(bft_gpu* h, hipStream_t s, uint64_t n, uint64_t units);
-static void claims_launched(bft_gpu* h, hipStream_t s);
-template <int W, bool STAGED, int PROBE>
-static int launch_query_k(bft_gpu* h, const uint8_t* d_kmers, uint64_t n, uint64_t* d_bits64, uint32_t* d_rows, hipStream_t s, int rec) {
-    // LDS: hash table + root Bloom block (<= 64 CCs) + root CC headers: at most two workgroups fit a CU (160 KB).  With
-    // one workgroup per CU the request is padded past half the LDS so that the dispatcher cannot pair two on a CU.
-    const int res = query_residency(h);  // 1: one 1024-thread workgroup per CU, 2: two (8 wavefronts per SIMD), 3: two of 768 threads (6 per SIMD)
-    const int wgs = res == 1 ? 1 : 2;
-    const uint32_t block = res == 3 ? BFT_BLOCK6 : 1024;
-    // hash table + the root area (the root's Bloom block and CC headers, or -- with the derived root tables -- k_query's queue of deferred lanes)
-    size_t lds = BFT_LDS_HM_BYTES + ((size_t)BFT_MODULO_HASH * 8 + 15) / 16 * 16 + BFT_LDS_ROOT_MAX_CC * sizeof(BftCCX);
-    if (wgs == 1) lds = std::max<size_t>(lds, 84u << 10);
-    const uint64_t resident = 256ull * (uint64_t)wgs;  // 256 CUs x resident workgroups per CU
-    // chunks of 1024 k-mers per wavefront (query_body): the first by wavefront number, the others claimed from the stream's counter
-    const uint64_t n_chunks = (n + 1023) / 1024, wg_chunks = (n_chunks + block / 64 - 1) / (block / 64);
-    const BftClaimCtr ctr = claim_counters(h, s, n, n_chunks);
-    const dim3 grid((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(wg_chunks, resident * h->opt_grid_mult)));
-    static std::atomic<uint64_t> attr_devs{0};  // the attribute is per device: one bit per device it was set on
-    const uint64_t dev_bit = 1ull << (h->device & 63);
-    if (!(attr_devs.load(std::memory_order_acquire) & dev_bit)) {
-        HIPCK(hipFuncSetAttribute((const void*)k_query<W, 1024, STAGED, PROBE>, hipFuncAttributeMaxDynamicSharedMemorySize, 84 << 10));
-        HIPCK(hipFuncSetAttribute((const void*)k_query8<W, 1024, STAGED, PROBE>, hipFuncAttributeMaxDynamicSharedMemorySize, 84 << 10));
-        HIPCK(hipFuncSetAttribute((const void*)k_query6<W, STAGED, PROBE>, hipFuncAttributeMaxDynamicSharedMemorySize, 84 << 10));
-        attr_devs.fetch_or(dev_bit, std::memory_order_release);
-    }
-    // rec: bytes per input record (B, or 8W for the zero-padded word records of the sequence path); load_x reads that many
-    if (h->im.walk_kh && PROBE == 0)  // ("walk_hash": launch_query leaves im.walk_kh set only for this)
-        return bft_walkh_query(h->im, d_kmers, n, rec, d_bits64, d_rows, ctr, (uint32_t)h->opt_grid_mult, s);
-    if (res == 1) hipLaunchKernelGGL((k_query<W, 1024, STAGED, PROBE>), grid, dim3(1024), lds, s, h->im, d_kmers, n, rec, d_bits64, d_rows, ctr);
-    else if (res == 3) hipLaunchKernelGGL((k_query6<W, STAGED, PROBE>), grid, dim3(BFT_BLOCK6), lds, s, h->im, d_kmers, n, rec, d_bits64, d_rows, ctr);
-    else hipLaunchKernelGGL((k_query8<W, 1024, STAGED, PROBE>), grid, dim3(1024), lds, s, h->im, d_kmers, n, rec, d_bits64, d_rows, ctr);
-    HIPCK(hipGetLastError());
-    return 0;
-}
-
-template <int W, bool STAGED>
-static int launch_query_ws(bft_gpu* h, const uint8_t* d_kmers, uint64_t n, uint64_t* d_bits64, uint32_t* d_rows, hipStream_t s, int rec) {
-    if (W <= BFT_PROBE_MAX_W && h->im.probe_big && !h->im.walk_kh) return launch_query_k<W, STAGED, 1>(h, d_kmers, n, d_bits64, d_rows, s, rec);
-    return launch_query_k<W, STAGED, 0>(h, d_kmers, n, d_bits64, d_rows, s, rec);
-}
-
-template <int W>
-static int launch_query_w(bft_gpu* h, const uint8_t* d_kmers, uint64_t n, uint64_t* d_bits64, uint32_t* d_rows, hipStream_t s, int rec) {
-    const bool staged = h->root_ncc >= 1 && h->root_ncc <= BFT_LDS_ROOT_MAX_CC;
-    return staged ? launch_query_ws<W, true>(h, d_kmers, n, d_bits64, d_rows, s, rec) : launch_query_ws<W, false>(h, d_kmers, n, d_bits64, d_rows, s, rec);
-}
-
-// through_kh: plain root groups are looked up in the k-mer hash (k_query6h) -- the caller wants presence or colour sets, not rows
-static int launch_query_walk(bft_gpu* h, const uint8_t* d_kmers, uint64_t n, uint64_t* d_bits64, uint32_t* d_rows, hipStream_t s, int rec_bytes = 0, bool through_kh = false) {
-    if (n == 0) return 0;
-    const int rec = rec_bytes ? rec_bytes : h->B;
-    hipEvent_t e0, e1;
-    CK(bft_timing_begin(h, s, &e0, &e1));
-    const uint32_t keep = h->im.walk_kh;
-    if (!through_kh) h->im.walk_kh = 0;
-    int rc = 0;
-    switch (h->W) {
-    case 1: rc = launch_query_w<1>(h, d_kmers, n, d_bits64, d_rows, s, rec); break;
-    case 2: rc = launch_query_w<2>(h, d_kmers, n, d_bits64, d_rows, s, rec); break;
-    case 3: rc = launch_query_w<3>(h, d_kmers, n, d_bits64, d_rows, s, rec); break;
-    default: rc = launch_query_w<4>(h, d_kmers, n, d_bits64, d_rows, s, rec); break;
-    }
-    h->im.walk_kh = keep;
-    CK(rc);
-    claims_launched(h, s);
-    CK(bft_timing_end(h, s, e0, e1));
-    return 0;
-}
-
-// The claim counters of the handle: allocated and zeroed once, when the first image is committed (bft_gpu_build, bft_gpu_image_unpack) --
-// never on the path of a query call.
-static void ensure_claim_counters(bft_gpu* h) {
-    if (h->kh_ctr || h->kh_ctr_failed) return;
-    if (hipMalloc((void**)&h->kh_ctr, bft_gpu::KH_CTR_SLOTS * 8) != hipSuccess || hipMemset(h->kh_ctr, 0, bft_gpu::KH_CTR_SLOTS * 8) != hipSuccess ||
-        hipDeviceSynchronize() != hipSuccess) {  // (blocking: no launch of any stream can meet a counter that is not zero yet)
-        (void)hipGetLastError();
-        if (h->kh_ctr) (void)hipFree(h->kh_ctr);
-        h->kh_ctr = nullptr;
-        h->kh_ctr_failed = true;
-    }
-}
-// The claim counter of stream s (see struct bft_gpu) with the range this launch may use, or {NULL}: every round of blocks is dealt out by
-// workgroup number.  units: what the launch deals out (blocks of 256 k-mers, chunks of 1024) -- the slot's base moves on by that plus what the
-// resident workgroups can claim beyond it, so the next launch starts above anything this one can leave behind, finished or not
-// (bft_claims.h).  A handle keeps a counter for each of KH_CTR_SLOTS streams; queried on more, it hands the least recently used slot to the
-// new stream once that slot's last launch is known to be over (an event per slot), else the launch runs static rounds and is counted
-// (bft_gpu_build_time, entry 20: nothing is silent).
-static BftClaimCtr claim_counters(bft_gpu* h, hipStream_t s, uint64_t n, uint64_t units) {
-    static const bool env_off = getenv("BFT_GPU_QUERY_DYNAMIC") && atoi(getenv("BFT_GPU_QUERY_DYNAMIC")) == 0;
-    h->kh_ctr_pending = -1;  // (a launch that failed between claim_counters and claims_launched must not leave its slot behind for the next one)
-    if (!h->opt_query_dynamic || env_off || n < h->opt_query_dynamic_min || !h->kh_ctr) return BftClaimCtr{nullptr, 0};
-    {   // a launch being recorded into a graph gets static rounds: `base` is a kernel argument, frozen at capture time, and from the second replay on the
-        // counter stands above it -- every workgroup would answer its first round only (the counter cannot be reset on the device without giving up
-        // the property that nothing an unfinished launch leaves behind can hurt the next one)
-        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &st) != hipSuccess) (void)hipGetLastError();
-        else if (st != hipStreamCaptureStatusNone) return BftClaimCtr{nullptr, 0};
-    }
-    int slot = -1;
-    for (int i = 0; i < h->kh_ctr_used; i++)
-        if (h->kh_ctr_stream[i] == s) slot = i;
-    if (slot < 0 && h->kh_ctr_used < bft_gpu::KH_CTR_SLOTS) {
-        slot = h->kh_ctr_used++;
-        h->kh_ctr_stream[slot] = s;
-    }
-    if (slot < 0) {  // every slot taken: the least recently used one, if its stream has nothing of ours in flight any more
-        int lru = 0;
-        for (int i = 1; i < bft_gpu::KH_CTR_SLOTS; i++)
-            if (h->kh_ctr_tick[i] < h->kh_ctr_tick[lru]) lru = i;
-        // (a slot last used before the handle started recording events -- its stream may be gone by now, so there is nothing to ask but the device:
-        // once per such slot at most)
-        const bool over = h->kh_ctr_ev[lru] ? hipEventQuery(h->kh_ctr_ev[lru]) == hipSuccess : hipDeviceSynchronize() == hipSuccess;
-        if (over) {
-            slot = lru;
-            h->kh_ctr_stream[slot] = s;
-        } else {
-            (void)hipGetLastError();
-            h->claims_static_launches++;
-            return BftClaimCtr{nullptr, 0};
-        }
-    }
-    h->kh_ctr_tick[slot] = ++h->kh_ctr_clock;
-    h->kh_ctr_pending = slot;  // (claims_launched records the slot's event behind the launch)
-    const BftClaimCtr c{h->kh_ctr + slot, h->kh_ctr_base[slot]};
-    h->kh_ctr_base[slot] += units + ((unsigned long long)1 << 24);  // (2^24: more than the resident workgroups x the largest claim)
-    return c;
-}
-// behind a launch that was given a counter: where the slot's last use ends (only looked at when the slots run out)
-static void claims_launched(bft_gpu* h, hipStream_t s) {
-    const int slot = h->kh_ctr_pending;
-    h->kh_ctr_pending = -1;
-    if (slot < 0 || h->kh_ctr_used < bft_gpu::KH_CTR_SLOTS / 2) return;  // (no event traffic on a handle that is queried on a few streams)
-    if (!h->kh_ctr_ev[slot] && hipEventCreateWithFlags(&h->kh_ctr_ev[slot], hipEventDisableTiming) != hipSuccess) { h->kh_ctr_ev[slot] = nullptr; (void)hipGetLastError(); return; }
-    if (hipEventRecord(h->kh_ctr_ev[slot], s) != hipSuccess) (void)hipGetLastError();
-}
-
-// Presence (and, with im.emit_cs, the colour set of every found k-mer into d_out32) through the k-mer hash.
-static int launch_query_kh(bft_gpu* h, const uint8_t* d_kmers, uint64_t n, uint64_t* d_bits64, uint32_t* d_out32, hipStream_t s, int rec) {
-    hipEvent_t e0, e1;
-    CK(bft_timing_begin(h, s, &e0, &e1));
-    CK(bft_kh_query(h->im, h->opt_grid_mult, d_kmers, n, rec, d_bits64, d_out32, claim_counters(h, s, n, (n + 255) / 256), h->opt_query_chunk, s));
-    HIPCK(hipGetLastError());
-    claims_launched(h, s);
-    CK(bft_timing_end(h, s, e0, e1));
-    return 0;
-}
-
-// Which kernel a batch takes: the k-mer hash answers presence and colour sets (one cache line per k-mer); rows -- positions in the
-// sorted table, what the reference keeps in resultPresence -- come from the container walk, as does everything on an image
-// without the k-mer hash ("kmer_hash" 0, a table that could not be allocated or whose overflow list ran full: kh_wanted, kh_finish).  Same answers either way (tests/test_gpu_parity.py).
-int bft_launch_query(bft_gpu* h, const uint8_t* d_kmers, uint64_t n, uint64_t* d_bits64, uint32_t* d_rows, hipStream_t s, int rec_bytes) {
-    if (n == 0) return 0;
-    const int rec = rec_bytes ? rec_bytes : h->B;
-    const bool no_rows = d_rows == nullptr || h->im.emit_cs;  // presence or colour sets: what the k-mer hash holds
-    if (h->im.kh_lines != nullptr && no_rows && !h->opt_walk_hash) return launch_query_kh(h, d_kmers, n, d_bits64, d_rows, s, rec);
-    CK(bft_ensure_table(h));
-    // the walk looks plain root groups up in the k-mer hash when no row is asked for ("walk_hash")
-    return launch_query_walk(h, d_kmers, n, d_bits64, d_rows, s, rec, no_rows && h->opt_walk_hash);
-}
-
-// Synthetic batch for tune_residency: k-mers of the index itself (pseudo-random rows of tk), every other one with a
-// single-nucleotide change -- the mix of present k-mers and near misses that exercises the whole walk.
-template <int W>
-__global__ void k_tune_queries(const uint64_t* __restrict__ tk, uint64_t n_kmers, int k, int B, uint64_t m, uint8_t* __restrict__ out) {
-    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < m; i += (uint64_t)gridDim.x * blockDim.x) {
-        uint64_t z = (i + 0x9E3779B97F4A7C15ull) * 0xBF58476D1CE4E5B9ull;
-        z ^= z >> 31; z *= 0x94D049BB133111EBull; z ^= z >> 29;
-        const uint64_t row = z % n_kmers;
-        uint64_t t[W], x[W];
-#pragma unroll
-        for (int w = 0; w < W; w++) t[w] = tk[row * W + w];
-        bft_x_from_tform<W>(t, k, x);
-        if (i & 1) {
-            const int pos = (int)((z >> 33) % (uint64_t)k);
-            const uint64_t flip = 1 + ((z >> 20) % 3);
-#pragma unroll
-            for (int w = 0; w < W; w++)
-                if (w == (2 * pos) >> 6) x[w] ^= flip << ((2 * pos) & 63);
-        }
-        for (int b = 0; b < B; b++) {
-            uint64_t v = 0;
-#pragma unroll
-            for (int w = 0; w < W; w++)
-                if (w == (b >> 3)) v = x[w];
-            out[i * B + b] = (uint8_t)(v >> (8 * (b & 7)));
-        }
-    }
-}
-
-// bft_gpu_set_option("tune", 1): the launch shape of the container walk measured on THIS image, on a batch drawn from the index
-// (synchronises; never called implicitly -- a build or a query only ever applies default_launch_shape).
-static int tune_residency(bft_gpu* h) {
-    if (h->n_kmers < (1u << 16)) {  // small (L2-resident) indexes: always two workgroups, 4-row probes
-        h->tuned_wgs = 2;
-        h->tuned_probe = 4;
-        h->im.probe_big = probe_mode(h->opt_probe);
-        return 0;
-    }
-    const uint64_t m = 1ull << 22;
-    DevBuf q, bits;
-    CK(q.alloc(m * h->B));
-    CK(bits.alloc(((m + 63) / 64) * 8));
-    const dim3 grid(grid_for((m + 255) / 256)), block(256);
-    switch (h->W) {
-    case 1: hipLaunchKernelGGL(k_tune_queries<1>, grid, block, 0, h->stream, h->im.tk, h->n_kmers, h->k, h->B, m, q.as<uint8_t>()); break;
-    case 2: hipLaunchKernelGGL(k_tune_queries<2>, grid, block, 0, h->stream, h->im.tk, h->n_kmers, h->k, h->B, m, q.as<uint8_t>()); break;
-    case 3: hipLaunchKernelGGL(k_tune_queries<3>, grid, block, 0, h->stream, h->im.tk, h->n_kmers, h->k, h->B, m, q.as<uint8_t>()); break;
-    default: hipLaunchKernelGGL(k_tune_queries<4>, grid, block, 0, h->stream, h->im.tk, h->n_kmers, h->k, h->B, m, q.as<uint8_t>()); break;
-    }
-    HIPCK(hipGetLastError());
-    const bool timing = h->timing;
-    const uint32_t dbg = h->im.debug_stop;
-    h->timing = false;
-    h->im.debug_stop = 0;  // (only read by -DBFT_PERF_PROBE builds)
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = 0;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) rc = fail(BFT_GPU_E_HIP, "hipEventCreate failed");
-    // (residency 1 / 2 / 3) x (probe block 4 / 8 rows); options fixed by the caller are not varied
-    float best[6] = {1e30f, 1e30f, 1e30f, 1e30f, 1e30f, 1e30f};
-    for (int cfg = 0; cfg < 6 && rc == 0; cfg++) {
-        const int wgs = 1 + cfg % 3, probe = cfg >= 3 ? 8 : 4;
-        if ((h->opt_wgs_per_cu && h->opt_wgs_per_cu != wgs) || (h->opt_probe && h->opt_probe != probe) || (h->W > BFT_PROBE_MAX_W && probe == 8))
-            continue;
-        h->tuned_wgs = wgs;
-        h->im.probe_big = probe_mode(probe);
-        for (int rep = 0; rep < 2 && rc == 0; rep++) {  // the first repetition warms the caches, the second counts (large batches measure again: launch_query)
-            if (hipEventRecord(e0, h->stream) != hipSuccess) rc = fail(BFT_GPU_E_HIP, "hipEventRecord failed");
-            if (rc == 0) rc = launch_query_walk(h, q.as<uint8_t>(), m, bits.as<uint64_t>(), nullptr, h->stream);
-            if (rc == 0 && (hipEventRecord(e1, h->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess)) rc = fail(BFT_GPU_E_HIP, "k_query failed while tuning");
-            float ms = 0;
-            if (rc == 0 && hipEventElapsedTime(&ms, e0, e1) != hipSuccess) rc = fail(BFT_GPU_E_HIP, "hipEventElapsedTime failed");
-            if (rep > 0 && ms < best[cfg]) best[cfg] = ms;
-        }
-    }
-    // Residency 3 is the incumbent: on full batches and on the eight walks per k-mer of k_branching it is as fast as the better of
-    // the other two or 5-15 % faster (k = 36..63, config 5), and the 2^22-query tuning batch resolves differences of a few per
-    // cent poorly -- another arrangement has to win by more than 4 %.
-    int win = -1;
-    float win_score = 1e30f;
-    for (int cfg = 0; cfg < 6; cfg++) {
-        if (best[cfg] >= 1e29f) continue;
-        const float score = best[cfg] * (cfg % 3 == 2 ? 0.96f : 1.0f);
-        if (score < win_score) { win_score = score; win = cfg; }
-    }
-    if (win < 0) win = 1;
-    const int win_wgs = 1 + win % 3, win_probe = win >= 3 ? 8 : 4;
-    // root level: range table + direct table, or the direct table alone ("root_direct" 3).  The range table halves the L2
-    // footprint of the root level; its special prefixes (child Nodes) pay one more dependent load -- which side wins depends
-    // on how many there are, so both are timed with the residency / probe mode just chosen.
-    if (rc == 0 && h->opt_root_direct == 3 && h->rstart_ok) {
-        h->tuned_wgs = win_wgs;
-        h->im.probe_big = probe_mode(h->opt_probe ? h->opt_probe : win_probe);
-        float rs[2] = {1e30f, 1e30f};
-        for (int mode = 0; mode < 2 && rc == 0; mode++) {
-            h->im.rstart = mode ? h->d_rstart.as<uint32_t>() : nullptr;
-            h->im.rq = mode && h->rq_ok ? h->d_rq.as<uint32_t>() : nullptr;
-            for (int rep = 0; rep < 3 && rc == 0; rep++) {
-                if (hipEventRecord(e0, h->stream) != hipSuccess) rc = fail(BFT_GPU_E_HIP, "hipEventRecord failed");
-                if (rc == 0) rc = launch_query_walk(h, q.as<uint8_t>(), m, bits.as<uint64_t>(), nullptr, h->stream);
-                if (rc == 0 && (hipEventRecord(e1, h->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess)) rc = fail(BFT_GPU_E_HIP, "k_query failed while tuning");
-                float ms = 0;
-                if (rc == 0 && hipEventElapsedTime(&ms, e0, e1) != hipSuccess) rc = fail(BFT_GPU_E_HIP, "hipEventElapsedTime failed");
-                if (rep > 0 && ms < rs[mode]) rs[mode] = ms;
-            }
-        }
-        h->rstart_tune_ms[0] = rs[0];
-        h->rstart_tune_ms[1] = rs[1];
-        h->tuned_rstart = rs[1] < rs[0] ? 1 : 0;
-        h->im.rstart = h->tuned_rstart ? h->d_rstart.as<uint32_t>() : nullptr;
-        h->im.rq = h->tuned_rstart && h->rq_ok ? h->d_rq.as<uint32_t>() : nullptr;
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    h->timing = timing;
-    h->im.debug_stop = dbg;
-    h->tuned_wgs = 0;
-    h->im.probe_big = probe_mode(h->opt_probe);
-    CK(rc);
-    for (int r = 0; r < 3; r++) h->tune_ms[r] = std::min(best[r], best[r + 3]) < 1e29f ? std::min(best[r], best[r + 3]) : 0;
-    h->tuned_wgs = win_wgs;
-    h->tuned_probe = win_probe;
-    h->im.probe_big = probe_mode(h->opt_probe ? h->opt_probe : h->tuned_probe);
-    return 0;
-}
-
-template <int W, bool STAGED, int PROBE>
-static int launch_branching_k(bft_gpu* h, const uint8_t* d_kmers, uint64_t n, uint64_t* d_bits64, uint8_t* d_counts, hipStream_t s) {
-    const int res = query_residency(h);  // eight walks per k-mer: the residency measured for k_query applies
-    const int wgs = res == 1 ? 1 : 2;
-    const uint32_t block = res == 3 ? BFT_BLOCK6 : 1024;
-    // hash table + the root area (the root's Bloom block and CC headers, or -- with the derived root tables -- k_query's queue of deferred lanes)
-    size_t lds = BFT_LDS_HM_BYTES + ((size_t)BFT_MODULO_HASH * 8 + 15) / 16 * 16 + BFT_LDS_ROOT_MAX_CC * sizeof(BftCCX);
-    if (wgs == 1) lds = std::max<size_t>(lds, 84u << 10);
-    const uint64_t nblk = (n + block - 1) / block;
-    const dim3 grid((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(nblk, 256ull * (uint64_t)wgs)));
-    static std::atomic<uint64_t> attr_devs{0};
-    const uint64_t dev_bit = 1ull << (h->device & 63);
-    if (!(attr_devs.load(std::memory_order_acquire) & dev_bit)) {
-        HIPCK(hipFuncSetAttribute((const void*)k_branching<W, 1024, STAGED, PROBE>, hipFuncAttributeMaxDynamicSharedMemorySize, 84 << 10));
-        HIPCK(hipFuncSetAttribute((const void*)k_branching8<W, 1024, STAGED, PROBE>, hipFuncAttributeMaxDynamicSharedMemorySize, 84 << 10));
-        HIPCK(hipFuncSetAttribute((const void*)k_branching6<W, STAGED, PROBE>, hipFuncAttributeMaxDynamicSharedMemorySize, 84 << 10));
-        attr_devs.fetch_or(dev_bit, std::memory_order_release);
-    }
-    if (res == 1) hipLaunchKernelGGL((k_branching<W, 1024, STAGED, PROBE>), grid, dim3(1024), lds, s, h->im, d_kmers, n, h->B, d_bits64, d_counts);
-    else if (res == 3) hipLaunchKernelGGL((k_branching6<W, STAGED, PROBE>), grid, dim3(BFT_BLOCK6), lds, s, h->im, d_kmers, n, h->B, d_bits64, d_counts);
-    else hipLaunchKernelGGL((k_branching8<W, 1024, STAGED, PROBE>), grid, dim3(1024), lds, s, h->im, d_kmers, n, h->B, d_bits64, d_counts);
-    HIPCK(hipGetLastError());
-    return 0;
-}
-
-static int launch_branching(bft_gpu* h, const uint8_t* d_kmers, uint64_t n, uint64_t* d_bits64, uint8_t* d_counts, hipStream_t s) {
-    if (n == 0) return 0;
-    const bool staged = h->root_ncc >= 1 && h->root_ncc <= BFT_LDS_ROOT_MAX_CC;
-    hipEvent_t e0, e1;
-    CK(bft_timing_begin(h, s, &e0, &e1));
-    if (h->im.kh_lines != nullptr) {  // eight candidates per k-mer, each one cache line of the k-mer hash, four in flight at a time
-        CK(bft_kh_branching(h->im, d_kmers, n, h->B, d_bits64, d_counts, claim_counters(h, s, n * 8, (n + 255) / 256), h->opt_query_chunk, s));
-        claims_launched(h, s);
-        CK(bft_timing_end(h, s, e0, e1));
-        return 0;
-    }
-#define BR(WW, PP) (staged ? launch_branching_k<WW, true, PP>(h, d_kmers, n, d_bits64, d_counts, s) : launch_branching_k<WW, false, PP>(h, d_kmers, n, d_bits64, d_counts, s))
-    switch (h->W) {
-    case 1: CK(BR(1, 0)); break;
-    case 2: CK(BR(2, 0)); break;
-    case 3: CK(BR(3, 0)); break;
-    default: CK(BR(4, 0)); break;
-    }
-#undef BR
-    CK(bft_timing_end(h, s, e0, e1));
-    return 0;
-}
-
-extern "C" int bft_gpu_query_branching_dev(bft_gpu* h, const void* d_kmers, uint64_t n, void* d_branching_bits, void* d_counts, void* hip_stream) {
-    if (!h || ((!d_kmers || !d_branching_bits) && n)) return fail(BFT_GPU_E_ARG, "NULL argument");
-    ENTER(h);
-    CK(bft_ensure_built(h, false));  // (the k-mer hash answers; the walk fetches the table itself)
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
-    CK(launch_branching(h, (const uint8_t*)d_kmers, n, (uint64_t*)d_branching_bits, (uint8_t*)d_counts, s));
-    return bft_note_foreign_stream(h, s);
-}
-
-extern "C" int bft_gpu_query_branching(bft_gpu* h, const uint8_t* kmers, uint64_t n, uint8_t* branching_bits, uint8_t* counts) {
-    if (!h || ((!kmers || !branching_bits) && n)) return fail(BFT_GPU_E_ARG, "NULL argument");
-    ENTER(h);
-    CK(bft_ensure_built(h, false));  // (the k-mer hash answers; the walk fetches the table itself)
-    const uint64_t chunk = 1ull << 26;
-    const uint64_t mc = std::min(n, chunk);
-    DevBuf dk, db, dc;
-    CK(dk.alloc(mc * h->B));
-    CK(db.alloc(((mc + 63) / 64) * 8));
-    if (counts) CK(dc.alloc(mc));
-    for (uint64_t a = 0; a < n; a += chunk) {
-        const uint64_t m = std::min(chunk, n - a);
-        HIPCK(hipMemcpyAsync(dk.p, kmers + a * h->B, m * h->B, hipMemcpyHostToDevice, h->stream));
-        CK(launch_branching(h, dk.as<uint8_t>(), m, db.as<uint64_t>(), counts ? dc.as<uint8_t>() : nullptr, h->stream));
-        HIPCK(hipMemcpyAsync(branching_bits + a / 8, db.p, (m + 7) / 8, hipMemcpyDeviceToHost, h->stream));
-        if (counts) HIPCK(hipMemcpyAsync(counts + a, dc.p, m, hipMemcpyDeviceToHost, h->stream));
-        HIPCK(hipStreamSynchronize(h->stream));
-    }
-    return BFT_GPU_OK;
-}
-
-extern "C" int bft_gpu_query_presence_dev(bft_gpu* h, const void* d_kmers, uint64_t n, void* d_present_bits, void* hip_stream) {
-    if (!h || ((!d_kmers || !d_present_bits) && n)) return fail(BFT_GPU_E_ARG, "NULL argument");
-    ENTER(h);
-    CK(bft_ensure_built(h, false));  // (the k-mer hash answers; the walk fetches the table itself)
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
-    CK(bft_launch_query(h, (const uint8_t*)d_kmers, n, (uint64_t*)d_present_bits, nullptr, s));
-    return bft_note_foreign_stream(h, s);
-}
-
-// ---- small host batches through the pinned block -------------------------------------------------------------------------
-#define BFT_PIN_MAX_N 4096u                       // k-mers per call served this way
-#define BFT_PIN_IN (BFT_PIN_MAX_N * 32u)          // B <= 32 bytes per k-mer
-#define BFT_PIN_BITS_OFF BFT_PIN_IN
-#define BFT_PIN_ROWS_OFF (BFT_PIN_BITS_OFF + BFT_PIN_MAX_N / 8u)
-#define BFT_PIN_SETS_OFF (BFT_PIN_ROWS_OFF + BFT_PIN_MAX_N * 4u)
-#define BFT_PIN_BYTES (BFT_PIN_SETS_OFF + BFT_PIN_MAX_N * 4u)
-
-static int pin_block(bft_gpu* h) {
-    if (h->pin) return 0;
-    void* p = nullptr;
-    HIPCK(hipHostMalloc(&p, BFT_PIN_BYTES, hipHostMallocMapped));
-    h->pin = (uint8_t*)p;
-    return 0;
-}
-
-// presence (+ rows, + colour-set ids) of n <= BFT_PIN_MAX_N host k-mers; any output pointer may be NULL
-static int query_small(bft_gpu* h, const uint8_t* kmers, uint64_t n, uint8_t* present_bits, uint32_t* rows, uint32_t* colorsets) {
-    CK(pin_block(h));
-    uint8_t* pin = h->pin;
-    memcpy(pin, kmers, n * h->B);
-    uint32_t* prow = (uint32_t*)(pin + BFT_PIN_ROWS_OFF);
-    uint32_t* pset = (uint32_t*)(pin + BFT_PIN_SETS_OFF);
-    const bool want_rows = rows || colorsets;
-    CK(bft_launch_query(h, pin, n, (uint64_t*)(pin + BFT_PIN_BITS_OFF), want_rows ? prow : nullptr, h->stream));
-    if (colorsets) {
-        hipLaunchKernelGGL(k_row_colorsets, dim3(grid_for((n + 255) / 256)), dim3(256), 0, h->stream, prow, h->im.tcol, n, pset);
-        HIPCK(hipGetLastError());
-    }
-    HIPCK(hipStreamSynchronize(h->stream));
-    if (present_bits) memcpy(present_bits, pin + BFT_PIN_BITS_OFF, (n + 7) / 8);
-    if (rows) memcpy(rows, prow, n * 4);
-    if (colorsets) memcpy(colorsets, pset, n * 4);
-    return BFT_GPU_OK;
-}
-
-extern "C" int bft_gpu_query_presence(bft_gpu* h, const uint8_t* kmers, uint64_t n, uint8_t* present_bits) {
-    if (!h || ((!kmers || !present_bits) && n)) return fail(BFT_GPU_E_ARG, "NULL argument");
-    ENTER(h);
-    CK(bft_ensure_built(h, false));  // (the k-mer hash answers; the walk fetches the table itself)
-    if (n && n <= BFT_PIN_MAX_N) return query_small(h, kmers, n, present_bits, nullptr, nullptr);
-    const uint64_t chunk = 1ull << 26;  // multiple of 64: chunks are byte aligned in the bitmap
-    DevBuf dk, db;
-    CK(dk.alloc(std::min(n, chunk) * h->B));
-    CK(db.alloc(((std::min(n, chunk) + 63) / 64) * 8));
-    for (uint64_t a = 0; a < n; a += chunk) {
-        const uint64_t m = std::min(chunk, n - a);
-        HIPCK(hipMemcpyAsync(dk.p, kmers + a * h->B, m * h->B, hipMemcpyHostToDevice, h->stream));
-        CK(bft_launch_query(h, dk.as<uint8_t>(), m, db.as<uint64_t>(), nullptr, h->stream));
-        HIPCK(hipMemcpyAsync(present_bits + a / 8, db.p, (m + 7) / 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCK(hipStreamSynchronize(h->stream));
-    }
-    return BFT_GPU_OK;
-}
-
-// shared front half of the colour queries: rows + presence bits for one chunk
-static int query_rows(bft_gpu* h, const uint8_t* kmers, uint64_t m, DevBuf& dk, DevBuf& db, DevBuf& dr, uint8_t* present_bits) {
-    HIPCK(hipMemcpyAsync(dk.p, kmers, m * h->B, hipMemcpyHostToDevice, h->stream));
-    CK(bft_launch_query(h, dk.as<uint8_t>(), m, db.as<uint64_t>(), dr.as<uint32_t>(), h->stream));
-    if (present_bits) HIPCK(hipMemcpyAsync(present_bits, db.p, (m + 7) / 8, hipMemcpyDeviceToHost, h->stream));
-    return 0;
-}
-
-// get_annotation + get_list_id_genomes for a resident batch (src/bft.c:363-387, 622-641; src/annotation.c:2086-2250): the k-mer hash hands out
-// the colour-set id of every found k-mer (emit_cs: the same line that answers presence), the lists' lengths are scanned into offsets straight
-// from the dictionary, and the wavefronts stream the ids out.  No row, no sorted table ("compact_table" stays), no host round trip.
-static int colors_core(bft_gpu* h, const uint8_t* d_kmers, uint64_t n, uint64_t* d_bits64, uint64_t* d_offsets, uint32_t* d_ids, uint64_t ids_cap, uint64_t* d_needed,
-                       hipStream_t s, bool fill) {
-    CK(h->qc.acquire(s, bft_stream_capturing(s)));
-    if (fill && h->im.kh_lines != nullptr && !h->opt_walk_hash && bft_kh_has_kernels(h->W, h->im.kh.S) && h->im.nb_genomes < 65536u) {  // (k_colors_kh keeps list lengths in 16 bits)
-        // through the k-mer hash: lookup, offsets and ids in ONE launch (k_colors_kh; the host entry point counts first and fills per chunk: the three steps below)
-        // (a block of its own: the kernel writes its counter and states raw, which a block of bft_scan's -- qc_tmp -- must never see)
-        const size_t sb = bft_kh_colors_scratch_bytes(n);
-        CK(h->qc.grow(h->qc_kh, sb, sb / 2));
-        CK(bft_timed_launch(h, s, [&] { return bft_kh_colors(h->im, d_kmers, n, h->B, d_bits64, d_offsets, d_ids, d_ids ? ids_cap : 0, d_needed, h->qc_kh.p, s); }));
-        h->qc.release();
-        return 0;
-    }
-    const size_t tb = bft_scan::scratch_bytes(n + 1);  // (the scan's tile states)
-    CK(h->qc.grow(h->qc_cs, n * 4, n / 2));
-    CK(h->qc.grow(h->qc_tmp, tb, tb / 2));
-    uint32_t* d_cs = h->qc_cs.as<uint32_t>();
-    {   // (the k-mer hash has the colour set in the line that answers presence; the walk, on an image without the table, takes it from tcol[row])
-        h->im.emit_cs = 1;
-        const int rc = bft_launch_query(h, d_kmers, n, d_bits64, d_cs, s);
-        h->im.emit_cs = 0;
-        CK(rc);
-    }
-    const BftCsLen len{d_cs, h->im.cs_off, n};
-    CK((bft_scan::exclusive_sum<uint64_t>(len, d_offsets, n + 1, s, h->qc_tmp)));
-    if (fill) {
-        CK(bft_timed_launch(h, s, [&] {
-            hipLaunchKernelGGL(k_color_fill_cs, dim3(grid_for((n + 255) / 256)), dim3(256), 0, s, d_cs, h->im.cs_off, h->im.cs_ids, h->im.cs_w, d_offsets, n, ids_cap, d_ids, d_needed);
-            HIPCK(hipGetLastError());
-            return 0;
-        }));
-    }
-    h->qc.release();
-    return 0;
-}
-
-extern "C" int bft_gpu_query_colors_dev(bft_gpu* h, const void* d_kmers, uint64_t n, void* d_present_bits, void* d_offsets, void* d_ids, uint64_t ids_cap,
-                                        void* d_ids_needed, void* hip_stream) {
-    if (!h || !d_offsets || ((!d_kmers || !d_present_bits) && n)) return fail(BFT_GPU_E_ARG, "NULL argument");
-    ENTER(h);
-    CK(bft_ensure_built(h, false));
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
-    if (n == 0) {
-        CK(bft_zero_async(d_offsets, 8, s));  // (kernels, not memsets, wherever a caller may be capturing: bft_dev.h)
-        if (d_ids_needed) CK(bft_zero_async(d_ids_needed, 8, s));
-        return bft_note_foreign_stream(h, s);
-    }
-    CK(colors_core(h, (const uint8_t*)d_kmers, n, (uint64_t*)d_present_bits, (uint64_t*)d_offsets, (uint32_t*)d_ids, ids_cap, (uint64_t*)d_ids_needed, s, true));
-    return bft_note_foreign_stream(h, s);
-}
-
-// The host-buffer form: the resident one on staged chunks.
-extern "C" int bft_gpu_query_colors(bft_gpu* h, const uint8_t* kmers, uint64_t n, uint8_t* present_bits, uint64_t* offsets,
-                                    uint32_t* ids, uint64_t ids_cap, uint64_t* ids_needed) {
-    if (!h || !offsets || ((!kmers) && n)) return fail(BFT_GPU_E_ARG, "NULL argument");
-    ENTER(h);
-    CK(bft_ensure_built(h, false));
-    const uint64_t chunk = 1ull << 24;
-    const uint64_t mc = std::min(n, chunk);
-    DevBuf dk, db, doff, dids;
-    CK(dk.alloc(mc * h->B));
-    CK(db.alloc(((mc + 63) / 64) * 8));
-    CK(doff.alloc((mc + 1) * 8));
-    uint64_t total = 0;
-    bool overflow = false;
-    for (uint64_t a = 0; a < n; a += chunk) {
-        const uint64_t m = std::min(chunk, n - a);
-        HIPCK(hipMemcpyAsync(dk.p, kmers + a * h->B, m * h->B, hipMemcpyHostToDevice, h->stream));
-        CK(colors_core(h, dk.as<uint8_t>(), m, db.as<uint64_t>(), doff.as<uint64_t>(), nullptr, 0, nullptr, h->stream, false));
-        if (present_bits) HIPCK(hipMemcpyAsync(present_bits + a / 8, db.p, (m + 7) / 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCK(hipMemcpyAsync(offsets + a, doff.p, (m + 1) * 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCK(hipStreamSynchronize(h->stream));
-        const uint64_t cnt = offsets[a + m];
-        if (total)
-            for (uint64_t i = 0; i <= m; i++) offsets[a + i] += total;  // chunk-local -> global
-        if (!overflow && ids && total + cnt <= ids_cap) {
-            if (cnt) {
-                CK(dids.alloc(cnt * 4));
-                CK(bft_timed_launch(h, h->stream, [&] {
-                    hipLaunchKernelGGL(k_color_fill_cs, dim3(grid_for((m + 255) / 256)), dim3(256), 0, h->stream, h->qc_cs.as<uint32_t>(), h->im.cs_off, h->im.cs_ids, h->im.cs_w,
-                                       doff.as<uint64_t>(), m, cnt, dids.as<uint32_t>(), (uint64_t*)nullptr);
-                    HIPCK(hipGetLastError());
-                    return 0;
-                }));
-                HIPCK(hipMemcpyAsync(ids + total, dids.p, cnt * 4, hipMemcpyDeviceToHost, h->stream));
-                HIPCK(hipStreamSynchronize(h->stream));
-            }
-        } else
-            overflow = true;
-        total += cnt;
-    }
-    if (n == 0) offsets[0] = 0;
-    if (ids_needed) *ids_needed = total;
-    if (overflow) return fail(BFT_GPU_E_NOSPACE, "ids buffer too small");
-    return BFT_GPU_OK;
-}
-
-// Bitmap form of the colour-set dictionary (one dword-aligned row per set), used by the colour-row queries when it stays
-// below 4 GiB; derived on the first such query of an image, on the handle's stream.
-int bft_ensure_cs_bitmaps(bft_gpu* h) {
-    if (h->cs_bm_tried) return 0;
-    h->cs_bm_tried = true;
-    if (h->opt_no_cs_bitmaps) return 0;  // ("test_no_cs_bitmaps": as if the bitmaps passed 4 GiB)
-    const uint64_t rowbytes = (h->im.nb_genomes + 7) / 8, nsets = h->n_sets;
-    if (rowbytes && nsets && nsets * rowbytes <= (4ull << 30)) {
-        const uint64_t stride = (rowbytes + 3) & ~3ull;  // dword-aligned dictionary rows (k_color_rows_bm)
-        // (CS_BM_SLACK zero bytes in front of the first row and behind the last: k_color_rows_bm16 loads 16 bytes from up to 15 bytes before a row
-        // and up to its last byte)
-        CK(h->d_cs_bm.alloc_zero(nsets * stride + 2 * CS_BM_SLACK, h->stream));
-        hipLaunchKernelGGL(k_cs_bitmaps, dim3(grid_for((nsets + 255) / 256)), dim3(256), 0, h->stream, h->im.cs_off, h->im.cs_ids, h->im.cs_w, nsets, (uint32_t)stride,
-                           h->d_cs_bm.as<uint8_t>() + CS_BM_SLACK);
-        HIPCK(hipGetLastError());
-        HIPCK(hipStreamSynchronize(h->stream));  // the row kernel may run on a caller's stream
-        h->has_cs_bm = true;
-    }
-    return 0;
-}
-
-// d_rowidx: the row of every k-mer (scratch: overwritten with the colour-set ids when the bitmap dictionary is used)
-static int launch_color_rows(bft_gpu* h, uint32_t* d_rowidx, uint64_t n, uint32_t rowbytes, uint8_t* d_out, hipStream_t s, bool are_colorsets = false) {
-    CK(bft_ensure_cs_bitmaps(h));
-    hipEvent_t e0, e1;
-    CK(bft_timing_begin(h, s, &e0, &e1));
-    if (h->has_cs_bm) {
-        if (!are_colorsets)
-            hipLaunchKernelGGL(k_row_colorsets, dim3(grid_for((n + 255) / 256)), dim3(256), 0, s, d_rowidx, h->im.tcol, n, d_rowidx);  // row -> colour set, in place
-        // (16-byte rows and up, 16-byte aligned output: the 16-bytes-per-lane kernel, whose tiles are a multiple of 16 k-mers)
-        const bool wide16 = rowbytes >= 16 && ((uintptr_t)d_out & 15u) == 0;
-        // the tile (a multiple of 4 / 16 k-mers) and the magic number of the division by rowbytes: bft_color_plan.h
-        const BftColorRowsPlan plan = bft_color_rows_plan(rowbytes, wide16 ? BFT_ROWS_FORM_16 : BFT_ROWS_FORM_DWORD);
-        const uint32_t tile_rows = plan.tile_rows, div_m = plan.div_m, div_l = plan.div_l;
-        const uint64_t tiles = (n + tile_rows - 1) / tile_rows;
-        dim3 cgrid((unsigned)std::min<uint64_t>(tiles, 256ull * 8));
-        if (wide16) {
-            // the tiles are dealt out by workgroup number: a grid larger than what is resident would run its last workgroups -- with all
-            // their tiles -- behind the others (82 registers: five workgroups per CU, not eight)
-            static std::atomic<int> resident16_dev[64];  // per device: CU count and partition mode may differ between the GPUs of a process
-            std::atomic<int>& resident16 = resident16_dev[h->device & 63];
-            int r = resident16.load(std::memory_order_relaxed);
-            if (!r) {
-                int per_cu = 0, cus = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_color_rows_bm16, 256, 0) != hipSuccess || per_cu < 1) { per_cu = 4; (void)hipGetLastError(); }
-                if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus < 1) { cus = 256; (void)hipGetLastError(); }
-                r = per_cu * cus;
-                resident16.store(r, std::memory_order_relaxed);
-            }
-            cgrid = dim3((unsigned)std::min<uint64_t>((tiles + 3) / 4, (uint64_t)r));
-        }
-        if (wide16)
-            hipLaunchKernelGGL(k_color_rows_bm16, cgrid, dim3(256), 0, s, d_rowidx, h->d_cs_bm.as<uint8_t>() + CS_BM_SLACK, (rowbytes + 3) & ~3u, n, rowbytes, tile_rows, div_m,
-                               div_l, d_out);
-        else if (rowbytes >= 4)
-            hipLaunchKernelGGL(k_color_rows_bm<true>, cgrid, dim3(256), 0, s, d_rowidx, h->d_cs_bm.as<uint8_t>() + CS_BM_SLACK, (rowbytes + 3) & ~3u, n, rowbytes, tile_rows, div_m,
-                               div_l, d_out);
-        else
-            hipLaunchKernelGGL(k_color_rows_bm<false>, cgrid, dim3(256), 0, s, d_rowidx, h->d_cs_bm.as<uint8_t>() + CS_BM_SLACK, (rowbytes + 3) & ~3u, n, rowbytes, tile_rows, div_m,
-                               div_l, d_out);
-    }
-    else
-        hipLaunchKernelGGL(k_color_rows, dim3(grid_for((n + 255) / 256)), dim3(256), 0, s, d_rowidx, h->im.tcol, h->im.cs_off, h->im.cs_ids, h->im.cs_w, n, rowbytes, d_out);
-    HIPCK(hipGetLastError());
-    return bft_timing_end(h, s, e0, e1);
-}
-
-// device-resident colour rows: presence bits + CEIL(nb_genomes/8)-byte bitmap row per k-mer, no synchronisation
-extern "C" int bft_gpu_query_color_rows_dev(bft_gpu* h, const void* d_kmers, uint64_t n, void* d_present_bits, void* d_rows, void* d_scratch_rows_u32,
-                                            void* hip_stream) {
-    if (!h || ((!d_kmers || !d_present_bits || !d_rows || !d_scratch_rows_u32) && n)) return fail(BFT_GPU_E_ARG, "NULL argument");
-    ENTER(h);
-    CK(bft_ensure_built(h, false));
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
-    const uint32_t rowbytes = (h->im.nb_genomes + 7) / 8;
-    if (n == 0 || rowbytes == 0) return BFT_GPU_OK;
-    // with the bitmap dictionary the query kernel writes colour sets straight away (the k-mer hash holds them; bft_hit_out in the
-    // walk): no row -> colour set pass
-    CK(bft_ensure_cs_bitmaps(h));
-    const bool direct = h->has_cs_bm;
-    // rows of 16 bytes and up through the k-mer hash: lookup and rows in one launch (the scratch array stays unused)
-    if (direct && rowbytes >= 16 && ((uintptr_t)d_rows & 15u) == 0 && h->im.kh_lines != nullptr && !h->opt_walk_hash && bft_kh_has_kernels(h->W, h->im.kh.S)) {
-        CK(bft_timed_launch(h, s, [&] {
-            return bft_kh_color_rows(h->im, (const uint8_t*)d_kmers, n, h->B, (uint64_t*)d_present_bits, h->d_cs_bm.as<uint8_t>() + CS_BM_SLACK, (rowbytes + 3) & ~3u, rowbytes,
-                                     (uint8_t*)d_rows, h->device, s);
-        }));
-        return bft_note_foreign_stream(h, s);
-    }
-    if (!direct) CK(bft_ensure_table(h));
-    if (direct) h->im.emit_cs = 1;
-    const int rc = bft_launch_query(h, (const uint8_t*)d_kmers, n, (uint64_t*)d_present_bits, (uint32_t*)d_scratch_rows_u32, s);
-    h->im.emit_cs = 0;
-    CK(rc);
-    CK(launch_color_rows(h, (uint32_t*)d_scratch_rows_u32, n, rowbytes, (uint8_t*)d_rows, s, direct));
-    return bft_note_foreign_stream(h, s);
-}
-
-extern "C" int bft_gpu_query_color_rows(bft_gpu* h, const uint8_t* kmers, uint64_t n, uint8_t* present_bits, uint8_t* rows) {
-    if (!h || !rows || (!kmers && n)) return fail(BFT_GPU_E_ARG, "NULL argument");
-    ENTER(h);
-    CK(bft_ensure_built(h));
-    const uint32_t rowbytes = (h->im.nb_genomes + 7) / 8;
-    if (rowbytes == 0) return BFT_GPU_OK;
-    const uint64_t chunk = 1ull << 22;
-    const uint64_t mc = std::min(n, chunk);
-    DevBuf dk, db, dr, dout;
-    CK(dk.alloc(mc * h->B));
-    CK(db.alloc(((mc + 63) / 64) * 8));
-    CK(dr.alloc(mc * 4));
-    CK(dout.alloc(mc * rowbytes));
-    for (uint64_t a = 0; a < n; a += chunk) {
-        const uint64_t m = std::min(chunk, n - a);
-        CK(query_rows(h, kmers + a * h->B, m, dk, db, dr, present_bits ? present_bits + a / 8 : nullptr));
-        CK(launch_color_rows(h, dr.as<uint32_t>(), m, rowbytes, dout.as<uint8_t>(), h->stream));
-        HIPCK(hipMemcpyAsync(rows + a * rowbytes, dout.p, m * rowbytes, hipMemcpyDeviceToHost, h->stream));
-        HIPCK(hipStreamSynchronize(h->stream));
-    }
-    return BFT_GPU_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// info / timing / extraction
-// ------------------------------------------------------------------------------------------------
-// query_sequence (src/bft.c:1241-1351) for a batch of ASCII sequences
-// Sequence queries on device-resident input.  Scratch (codes, plan, colour set per position) belongs to the handle and only grows; calls on
-// different streams take turns on it.  Nothing here waits for the GPU: the positions of a chunk are counted on the device
-// (k_seq_plan + scan) and the kernels read the total from there.
-template <int W, bool STAGED, int PROBE>
-static int launch_seq_walk_k(bft_gpu* h, uint32_t ns, int canonical, const uint64_t* d_soff, hipStream_t s) {
-    size_t lds = BFT_LDS_HM_BYTES + ((size_t)BFT_MODULO_HASH * 8 + 15) / 16 * 16 + BFT_LDS_ROOT_MAX_CC * sizeof(BftCCX);
-    static std::atomic<uint64_t> attr_devs{0};
-    const uint64_t dev_bit = 1ull << (h->device & 63);
-    if (!(attr_devs.load(std::memory_order_acquire) & dev_bit)) {
-        HIPCK(hipFuncSetAttribute((const void*)k_seq_walk8<W, STAGED, PROBE>, hipFuncAttributeMaxDynamicSharedMemorySize, 84 << 10));
-        HIPCK(hipFuncSetAttribute((const void*)k_seq_walk6<W, STAGED, PROBE>, hipFuncAttributeMaxDynamicSharedMemorySize, 84 << 10));
-        attr_devs.fetch_or(dev_bit, std::memory_order_release);
-    }
-    BftImage im = h->im;
-    im.emit_cs = 1;
-    if (W != 2)
-        hipLaunchKernelGGL((k_seq_walk8<W, STAGED, PROBE>), dim3(512), dim3(1024), lds, s, im, h->sq_codes.as<uint64_t>(), h->sq_bad.as<uint32_t>(), d_soff,
-                           h->sq_poff.as<uint64_t>(), h->sq_tile.as<uint32_t>(), ns, canonical, h->sq_cs.as<uint32_t>());
-    else
-        hipLaunchKernelGGL((k_seq_walk6<W, STAGED, PROBE>), dim3(512), dim3(BFT_BLOCK6), lds, s, im, h->sq_codes.as<uint64_t>(), h->sq_bad.as<uint32_t>(), d_soff,
-                           h->sq_poff.as<uint64_t>(), h->sq_tile.as<uint32_t>(), ns, canonical, h->sq_cs.as<uint32_t>());
-    HIPCK(hipGetLastError());
-    return 0;
-}
-
-template <int W>
-static int launch_seq_walk_w(bft_gpu* h, uint32_t ns, int canonical, const uint64_t* d_soff, hipStream_t s) {
-    const bool staged = h->root_ncc >= 1 && h->root_ncc <= BFT_LDS_ROOT_MAX_CC;
-    if (h->im.kh_lines != nullptr) {
-        return bft_kh_seq(h->im, h->sq_codes.as<uint64_t>(), h->sq_bad.as<uint32_t>(), d_soff, h->sq_poff.as<uint64_t>(), h->sq_tile.as<uint32_t>(), ns, canonical,
-                          h->sq_cs.as<uint32_t>(), claim_counters(h, s, h->opt_query_dynamic_min, h->sq_units), h->opt_query_chunk, s);
-        // (claims_launched: the caller, behind the launch)
-    }
-    return staged ? launch_seq_walk_k<W, true, 0>(h, ns, canonical, d_soff, s) : launch_seq_walk_k<W, false, 0>(h, ns, canonical, d_soff, s);
-}
-
-static int query_sequences_core(bft_gpu* h, const char* d_seqs, const uint64_t* d_seq_off, uint64_t n_seqs, uint64_t total_chars, double threshold,
-                                int canonical, uint8_t* d_rows, hipStream_t s) {
-    const uint32_t G = h->im.nb_genomes, rowbytes = (G + 7) / 8;
-    if (rowbytes == 0 || n_seqs == 0) return 0;
-    CK(h->sq.acquire(s, bft_stream_capturing(s)));
-    auto need = [&](DevBuf& b, size_t bytes) { return h->sq.grow(b, bytes, bytes / 8); };
-    // sequences per chunk: 32-bit sequence numbers
-    const uint64_t chunk = 1ull << 30;
-    const uint64_t cmax = std::min(chunk, n_seqs);
-    const uint64_t n_cw = (total_chars + 31) / 32;  // code words of the blob (32 characters each)
-    const size_t scan_bytes = bft_scan::scratch_bytes(cmax + 1);  // (the scan's tile states)
-    CK(need(h->sq_codes, (n_cw + BFT_MAX_W + 2) * 8));
-    CK(need(h->sq_bad, (n_cw + BFT_MAX_W + 2) * 4));
-    CK(need(h->sq_npos, (cmax + 1) * 8));
-    CK(need(h->sq_poff, (cmax + 1) * 8));
-    CK(need(h->sq_tmp, scan_bytes));
-    CK(need(h->sq_tile, (total_chars / 64 + 2) * 4));
-    CK(need(h->sq_cs, (total_chars + 64) * 4));  // colour set of every k-mer position of a chunk (positions <= characters)
-    // (the slack words behind the codes are read by windows at the very end of the blob: keep them defined)
-    CK(bft_zero_async(h->sq_codes.as<uint64_t>() + n_cw, (BFT_MAX_W + 2) * 8, s));
-    CK(bft_zero_async(h->sq_bad.as<uint32_t>() + n_cw, (BFT_MAX_W + 2) * 4, s));
-    if (n_cw)
-        CK(bft_timed_launch(h, s, [&] {
-            hipLaunchKernelGGL(k_seq_encode, dim3(grid_for((n_cw + 255) / 256)), dim3(256), 0, s, d_seqs, total_chars, n_cw, h->sq_codes.as<uint64_t>(),
-                               h->sq_bad.as<uint32_t>());
-            HIPCK(hipGetLastError());
-            return 0;
-        }));
-    for (uint64_t a = 0; a < n_seqs; a += chunk) {
-        const uint64_t ns = std::min(chunk, n_seqs - a);
-        const uint64_t* soff = d_seq_off + a;
-        CK(bft_timed_launch(h, s, [&] {  // (the plan: positions per read, their offsets, the tile table)
-            hipLaunchKernelGGL(k_seq_plan, dim3(grid_for((ns + 256) / 256)), dim3(256), 0, s, soff, ns, h->k, h->sq_npos.as<uint64_t>());
-            CK(bft_scan::exclusive_sum_ptr<uint64_t>(h->sq_npos.as<uint64_t>(), h->sq_poff.as<uint64_t>(), ns + 1, s, h->sq_tmp));
-            hipLaunchKernelGGL(k_seq_tiles, dim3(256 * 4), dim3(256), 0, s, h->sq_poff.as<uint64_t>(), (uint32_t)ns, h->sq_tile.as<uint32_t>());
-            HIPCK(hipGetLastError());
-            return 0;
-        }));
-        h->sq_units = total_chars / 256 + 2;  // (k-mer positions <= characters: the blocks the kernel can deal out)
-        CK(bft_timed_launch(h, s, [&] {
-            switch (h->W) {
-            case 1: return launch_seq_walk_w<1>(h, (uint32_t)ns, canonical, soff, s);
-            case 2: return launch_seq_walk_w<2>(h, (uint32_t)ns, canonical, soff, s);
-            case 3: return launch_seq_walk_w<3>(h, (uint32_t)ns, canonical, soff, s);
-            default: return launch_seq_walk_w<4>(h, (uint32_t)ns, canonical, soff, s);
-            }
-        }));
-        claims_launched(h, s);
-        const uint32_t win = std::min<uint32_t>(SEQ_TALLY_G, (G + 63u) & ~63u);  // counters per wavefront: all genomes up to 2048
-        CK(bft_timed_launch(h, s, [&] {
-            hipLaunchKernelGGL(k_seq_tally, dim3((unsigned)std::min<uint64_t>((ns + SEQ_TALLY_WAVES - 1) / SEQ_TALLY_WAVES, 256ull * 16)), dim3(64 * SEQ_TALLY_WAVES),
-                               (size_t)SEQ_TALLY_WAVES * win * 4, s, h->sq_cs.as<uint32_t>(), h->sq_poff.as<uint64_t>(), (uint32_t)ns, h->im.cs_off, h->im.cs_ids, h->im.cs_w, G,
-                               rowbytes, threshold, win, d_rows + a * rowbytes);
-            HIPCK(hipGetLastError());
-            return 0;
-        }));
-    }
-    h->sq.release();
-    return 0;
-}
-
-extern "C" int bft_gpu_query_sequences_dev(bft_gpu* h, const void* d_seqs, const void* d_seq_off, uint64_t n_seqs, uint64_t total_chars, double threshold,
-                                           int canonical, void* d_rows, void* hip_stream) {
-    if (!h || ((!d_seqs || !d_seq_off || !d_rows) && n_seqs)) return fail(BFT_GPU_E_ARG, "NULL argument");
-    if (!(threshold > 0) || threshold > 1) return fail(BFT_GPU_E_ARG, "the threshold must be in (0, 1] (reference src/bft.c:1246-1247)");
-    ENTER(h);
-    CK(bft_ensure_built(h, false));  // (the k-mer hash answers; the walk fetches the table itself)
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
-    CK(query_sequences_core(h, (const char*)d_seqs, (const uint64_t*)d_seq_off, n_seqs, total_chars, threshold, canonical, (uint8_t*)d_rows, s));
-    return bft_note_foreign_stream(h, s);
-}
-
-extern "C" int bft_gpu_query_sequences(bft_gpu* h, const char* seqs, const uint64_t* seq_off, uint64_t n_seqs, double threshold, int canonical,
-                                       uint8_t* rows) {
-    if (!h || ((!seqs || !seq_off || !rows) && n_seqs)) return fail(BFT_GPU_E_ARG, "NULL argument");
-    if (!(threshold > 0) || threshold > 1) return fail(BFT_GPU_E_ARG, "the threshold must be in (0, 1] (reference src/bft.c:1246-1247)");
-    ENTER(h);
-    CK(bft_ensure_built(h, false));  // (the k-mer hash answers; the walk fetches the table itself)
-    const uint32_t G = h->im.nb_genomes, rowbytes = (G + 7) / 8;
-    if (rowbytes == 0 || n_seqs == 0) return BFT_GPU_OK;
-    // host buffers: the blob and its offsets (rebased to the first sequence) go up in pieces of at most 2^30 characters
-    uint64_t a = 0;
-    while (a < n_seqs) {
-        uint64_t b = a + 1;
-        while (b < n_seqs && seq_off[b + 1] - seq_off[a] <= (1ull << 30)) b++;
-        const uint64_t ns = b - a, nchars = seq_off[b] - seq_off[a];
-        std::vector<uint64_t> soff(ns + 1);
-        for (uint64_t i = 0; i <= ns; i++) soff[i] = seq_off[a + i] - seq_off[a];
-        DevBuf d_seq, d_soff, d_out;
-        CK(d_seq.alloc(nchars + 16));
-        CK(d_soff.alloc((ns + 1) * 8));
-        CK(d_out.alloc(ns * rowbytes));
-        HIPCK(hipMemcpyAsync(d_seq.p, seqs + seq_off[a], nchars, hipMemcpyHostToDevice, h->stream));
-        HIPCK(hipMemcpyAsync(d_soff.p, soff.data(), (ns + 1) * 8, hipMemcpyHostToDevice, h->stream));
-        CK(query_sequences_core(h, d_seq.as<char>(), d_soff.as<uint64_t>(), ns, nchars, threshold, canonical, d_out.as<uint8_t>(), h->stream));
-        HIPCK(hipMemcpyAsync(rows + a * rowbytes, d_out.p, ns * rowbytes, hipMemcpyDeviceToHost, h->stream));
-        HIPCK(hipStreamSynchronize(h->stream));
-        a = b;
-    }
-    return BFT_GPU_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2426,7 +1598,7 @@ extern "C" int bft_gpu_image_unpack(const void* d_blob, uint64_t nbytes, int dev
     }
     h->info[12] = image_bytes(h);
     h->built = true;
-    ensure_claim_counters(h);
+    h->claims.ensure();
     h->table_dropped = false;
     drop_table(h);  // ("compact_table", the default: the replica's k-mer hash was derived from the blob's sorted table, which need not stay)
     *out = h;
@@ -2471,195 +1643,6 @@ extern "C" int bft_gpu_debug_color_rows_plan(uint32_t rowbytes, int form, uint32
     return BFT_GPU_OK;
 }
 
-// ------------------------------------------------------------------------------------------------
-// test hooks (tests/test_gpu_sort_scan.py; not part of include/bft_gpu.h): the library's own sort and scan on the caller's device arrays
-// ------------------------------------------------------------------------------------------------
-// kind 0: u64 keys; 1: u64 keys + u32 values; 2: u32 keys + u32 values.  shape: bft_rs::SHAPE_*.  Stable LSD over the bits [begin_bit, end_bit).
-extern "C" int bft_gpu_test_sort(int kind, int shape, const void* d_keys, const void* d_vals, uint64_t n, unsigned begin_bit, unsigned end_bit, void* d_out_keys, void* d_out_vals,
-                                 void* hip_stream) {
-    if ((!d_keys || !d_out_keys) && n) return fail(BFT_GPU_E_ARG, "NULL argument");
-    hipStream_t s = (hipStream_t)hip_stream;
-    int dev = 0;
-    HIPCK(hipGetDevice(&dev));
-    bft_pool_set_stream(dev, s);
-    int rc = BFT_GPU_E_ARG;
-#define BFT_TS(K, V, SH) rc = bft_rs::sort_pairs<K, V, SH>((const K*)d_keys, (const V*)d_vals, n, (K*)d_out_keys, (V*)d_out_vals, begin_bit, end_bit, s)
-    if (kind == 0) {
-        rc = bft_rs::sort_keys<uint64_t>((const uint64_t*)d_keys, n, (uint64_t*)d_out_keys, begin_bit, end_bit, s);
-    } else if (kind == 1) {
-        if (shape == bft_rs::SHAPE_LIGHT) BFT_TS(uint64_t, uint32_t, bft_rs::SHAPE_LIGHT);
-        else if (shape == bft_rs::SHAPE_BACK) BFT_TS(uint64_t, uint32_t, bft_rs::SHAPE_BACK);
-        else BFT_TS(uint64_t, uint32_t, bft_rs::SHAPE_BIG);
-    } else if (kind == 2) {
-        if (shape == bft_rs::SHAPE_LIGHT) BFT_TS(uint32_t, uint32_t, bft_rs::SHAPE_LIGHT);
-        else if (shape == bft_rs::SHAPE_BACK) BFT_TS(uint32_t, uint32_t, bft_rs::SHAPE_BACK);
-        else BFT_TS(uint32_t, uint32_t, bft_rs::SHAPE_BIG);
-    }
-#undef BFT_TS
-    if (rc) return rc;
-    HIPCK(hipStreamSynchronize(s));
-    return BFT_GPU_OK;
-}
-// kind 0: exclusive sum of u32 (out[n] = the total as well); 1: exclusive sum of u64 (likewise); 2: inclusive max of u64, init 5.  *d_total: the grand total.
-// reps scans in a row share one scratch block (nothing is zeroed between them: bft_scan.h).
-extern "C" int bft_gpu_test_scan(int kind, const void* d_in, uint64_t n, void* d_out, void* d_total, int reps, void* hip_stream) {
-    if ((!d_in || !d_out) && n) return fail(BFT_GPU_E_ARG, "NULL argument");
-    hipStream_t s = (hipStream_t)hip_stream;
-    int dev = 0;
-    HIPCK(hipGetDevice(&dev));
-    bft_pool_set_stream(dev, s);
-    DevBuf scratch;
-    for (int r = 0; r < std::max(1, reps); r++) {
-        if (kind == 0) CK(bft_scan::exclusive_sum_ptr<uint32_t>((const uint32_t*)d_in, (uint32_t*)d_out, n, s, scratch, (unsigned long long*)d_total, true));
-        else if (kind == 1) CK(bft_scan::exclusive_sum_ptr<uint64_t>((const uint64_t*)d_in, (uint64_t*)d_out, n, s, scratch, (unsigned long long*)d_total, true));
-        else if (kind == 2)
-            CK((bft_scan::scan<uint64_t, bft_scan::PtrIn<uint64_t>, bft_scan::Max, true>(bft_scan::PtrIn<uint64_t>{(const uint64_t*)d_in}, (uint64_t*)d_out, n, 5ull, bft_scan::Max(), s, scratch,
-                                                                                          (unsigned long long*)d_total)));
-        else return fail(BFT_GPU_E_ARG, "bad scan kind");
-    }
-    HIPCK(hipStreamSynchronize(s));
-    return BFT_GPU_OK;
-}
-
-// Every (key, value, input) the library sorts (tests/test_gpu_sort_scan_edges.py).  kind: 0 u64 keys; 1 u64 + u32; 2 u32 + u32; 3 u32 + u64 (the
-// genome-id pass); 4 u64 keys through BftCompose (d_vals NULL: the keys as they are, else (key << param) | id[i]); 5 / 6 u64 + u8 / u16 through
-// BftPairIn (d_vals: u32 ids, narrowed); 7 u64 + BftSplit2Val through BftSplit2In (d_keys: word 0; d_vals: word 1 [n] (u64), then the ids [n]
-// (u32); param: sh, 0 = 64); 8 .. 11: u32 + KhRec<W>, W = kind - 7 (d_vals: the packed records).  The shapes each kind is built in:
-// bft_gpu_test_sort_tile != 0.  h_dbase (NULL or 512 words): the sort's last_dbase table, where it made one.
-#define BFT_TSX_KINDS(X)                                                                                        \
-    X(0, SHAPE_BIG, uint64_t, bft_rs::NoVal, (bft_rs::PtrIn<uint64_t, bft_rs::NoVal>{(const uint64_t*)d_keys, nullptr}))                 \
-    X(1, SHAPE_BIG, uint64_t, uint32_t, (bft_rs::PtrIn<uint64_t, uint32_t>{(const uint64_t*)d_keys, (const uint32_t*)d_vals}))           \
-    X(1, SHAPE_LIGHT, uint64_t, uint32_t, (bft_rs::PtrIn<uint64_t, uint32_t>{(const uint64_t*)d_keys, (const uint32_t*)d_vals}))         \
-    X(1, SHAPE_BACK, uint64_t, uint32_t, (bft_rs::PtrIn<uint64_t, uint32_t>{(const uint64_t*)d_keys, (const uint32_t*)d_vals}))          \
-    X(2, SHAPE_BIG, uint32_t, uint32_t, (bft_rs::PtrIn<uint32_t, uint32_t>{(const uint32_t*)d_keys, (const uint32_t*)d_vals}))           \
-    X(2, SHAPE_LIGHT, uint32_t, uint32_t, (bft_rs::PtrIn<uint32_t, uint32_t>{(const uint32_t*)d_keys, (const uint32_t*)d_vals}))         \
-    X(2, SHAPE_BACK, uint32_t, uint32_t, (bft_rs::PtrIn<uint32_t, uint32_t>{(const uint32_t*)d_keys, (const uint32_t*)d_vals}))          \
-    X(3, SHAPE_BIG, uint32_t, uint64_t, (bft_rs::PtrIn<uint32_t, uint64_t>{(const uint32_t*)d_keys, (const uint64_t*)d_vals}))           \
-    X(4, SHAPE_BIG, uint64_t, bft_rs::NoVal, (BftCompose{(const uint64_t*)d_keys, (const uint32_t*)d_vals, param}))                      \
-    X(5, SHAPE_BIG, uint64_t, uint8_t, (BftPairIn<uint8_t>{(const uint64_t*)d_keys, (const uint32_t*)d_vals}))                           \
-    X(6, SHAPE_BIG, uint64_t, uint16_t, (BftPairIn<uint16_t>{(const uint64_t*)d_keys, (const uint32_t*)d_vals}))                         \
-    X(7, SHAPE_BIG, uint64_t, BftSplit2Val, (BftSplit2In{(const uint64_t*)d_keys, (const uint64_t*)d_vals, (const uint32_t*)((const uint64_t*)d_vals + n), param ? param : 64u}))
-extern "C" int bft_gpu_test_sort_ex(int kind, int shape, const void* d_keys, const void* d_vals, uint64_t n, unsigned begin_bit, unsigned end_bit, void* d_out_keys, void* d_out_vals,
-                                    uint32_t param, uint32_t* h_dbase, void* hip_stream) {
-    if (n && (!d_keys || !d_out_keys || (kind != 0 && kind != 4 && (!d_vals || !d_out_vals)))) return fail(BFT_GPU_E_ARG, "NULL argument");
-    if (kind == 7 && param > 64) return fail(BFT_GPU_E_ARG, "test sort: sh");
-    hipStream_t s = (hipStream_t)hip_stream;
-    int dev = 0;
-    HIPCK(hipGetDevice(&dev));
-    bft_pool_set_stream(dev, s);
-    if (kind >= 8 && kind <= 11) return bft_kh_test_sort(kind - 7, shape, (const uint32_t*)d_keys, d_vals, n, begin_bit, end_bit, (uint32_t*)d_out_keys, d_out_vals, s, h_dbase);
-#define BFT_TSX(KIND, SH, K, V, IN)                                                                                                                               \
-    if (kind == KIND && shape == bft_rs::SH) {                                                                                                                    \
-        auto in = IN;  /* (not const: the In type of the product's own instantiations) */                                                                       \
-        return bft_rs::sort_test_run<K, V, decltype(in), bft_rs::SH>(in, n, (K*)d_out_keys, (V*)d_out_vals, begin_bit, end_bit, s, h_dbase);                     \
-    }
-    BFT_TSX_KINDS(BFT_TSX)
-#undef BFT_TSX
-    return fail(BFT_GPU_E_ARG, "test sort: kind / shape");
-}
-// entries per tile of bft_gpu_test_sort_ex(kind, shape) (the one-tile / ranged boundary); 0: that kind is not built in that shape
-extern "C" uint32_t bft_gpu_test_sort_tile(int kind, int shape) {
-    const void *d_keys = nullptr, *d_vals = nullptr;
-    const uint64_t n = 0;
-    const uint32_t param = 0;
-    if (kind >= 8 && kind <= 11) return bft_kh_test_sort_tile(kind - 7, shape);
-#define BFT_TSX(KIND, SH, K, V, IN)                                                                                                                               \
-    if (kind == KIND && shape == bft_rs::SH) {                                                                                                                    \
-        (void)IN;                                                                                                                                                 \
-        return bft_rs::tile_entries<K, V, bft_rs::SH>();                                                                                                          \
-    }
-    BFT_TSX_KINDS(BFT_TSX)
-#undef BFT_TSX
-    return 0u;
-}
-#undef BFT_TSX_KINDS
-// what the last library sort of the calling thread ran: [0] regime (0 copy, 1 one tile, 2 ranged, 3 chained, 255 nothing), [1] passes, [2] tiles,
-// [3] ranges, [4] tiles per range, [5] entries per tile, [6..7] 0; then per pass p < 8, words 8 + 4 p ..: first bit, bits, chains (0: a ranged
-// pass), look-back groups launched (1 or THREADS / 128; 0: a ranged pass).  Returns the words written.
-extern "C" int bft_gpu_test_sort_last(uint64_t* out, int n) {
-    if (!out || n < 0) return fail(BFT_GPU_E_ARG, "NULL argument");
-    const bft_rs::RunRecord& r = bft_rs::g_bft_rs_last;
-    uint64_t w[8 + 4 * bft_rs::MAXP] = {r.regime, r.P, r.tiles, r.ranges, r.tpr, r.tile, 0, 0};
-    for (int p = 0; p < bft_rs::MAXP; p++) {
-        w[8 + 4 * p] = r.bit[p];
-        w[9 + 4 * p] = r.nbits[p];
-        w[10 + 4 * p] = r.nch[p];
-        w[11 + 4 * p] = r.lbg[p];
-    }
-    const int m = std::min<int>(n, (int)(sizeof(w) / 8));
-    for (int i = 0; i < m; i++) out[i] = w[i];
-    return m;
-}
-
-// one scan of bft_gpu_test_scan_ex's kinds: 0 exclusive sum of u32; 1 of u64; 2 inclusive max of u64 from init = param; 3 exclusive sum (u64) of
-// BftPairFlags over u64 composites (d_in; gb = param), as the build numbers its k-mers and pairs; 4 exclusive sum (u32) of BftSpHead over uint2
-// (d_in), as the simple paths are numbered
-static int test_scan_one(int kind, const void* d_in, uint64_t n, void* d_out, void* d_total, bool tail, uint64_t param, hipStream_t s, DevBuf& scratch) {
-    unsigned long long* tot = (unsigned long long*)d_total;
-    switch (kind) {
-    case 0: return bft_scan::exclusive_sum_ptr<uint32_t>((const uint32_t*)d_in, (uint32_t*)d_out, n, s, scratch, tot, tail);
-    case 1: return bft_scan::exclusive_sum_ptr<uint64_t>((const uint64_t*)d_in, (uint64_t*)d_out, n, s, scratch, tot, tail);
-    case 2:
-        return bft_scan::scan<uint64_t, bft_scan::PtrIn<uint64_t>, bft_scan::Max, true>(bft_scan::PtrIn<uint64_t>{(const uint64_t*)d_in}, (uint64_t*)d_out, n, param, bft_scan::Max(), s,
-                                                                                         scratch, tot, tail);
-    case 3: return bft_scan::exclusive_sum<uint64_t>(BftPairFlags{(const uint64_t*)d_in, (uint32_t)param}, (uint64_t*)d_out, n, s, scratch, tot, tail);
-    case 4: return bft_scan::exclusive_sum<uint32_t>(BftSpHead{(const uint2*)d_in, n}, (uint32_t*)d_out, n, s, scratch, tot, tail);
-    default: return fail(BFT_GPU_E_ARG, "bad scan kind");
-    }
-}
-// one scan (kinds: test_scan_one) on a block of its own; tail: out[n] receives the total as well (else it is not written)
-extern "C" int bft_gpu_test_scan_ex(int kind, const void* d_in, uint64_t n, void* d_out, void* d_total, int tail, uint64_t param, void* hip_stream) {
-    if ((!d_in || !d_out) && n) return fail(BFT_GPU_E_ARG, "NULL argument");
-    hipStream_t s = (hipStream_t)hip_stream;
-    int dev = 0;
-    HIPCK(hipGetDevice(&dev));
-    bft_pool_set_stream(dev, s);
-    DevBuf scratch;
-    CK(test_scan_one(kind, d_in, n, d_out, d_total, tail != 0, param, s, scratch));
-    HIPCK(hipStreamSynchronize(s));
-    return BFT_GPU_OK;
-}
-// count scans one after the other on ONE scratch block, as the library's long-lived blocks are used: scan i reads d_in[0 .. sizes[i]) and writes
-// h_outs[i] (sizes[i] + 1 entries: with the total behind them) and d_totals[i] (u64)
-extern "C" int bft_gpu_test_scan_seq(int kind, const void* d_in, const uint64_t* sizes, int count, void* const* h_outs, uint64_t* d_totals, uint64_t param, void* hip_stream) {
-    if (!d_in || !sizes || !h_outs || !d_totals || count < 0) return fail(BFT_GPU_E_ARG, "NULL argument");
-    hipStream_t s = (hipStream_t)hip_stream;
-    int dev = 0;
-    HIPCK(hipGetDevice(&dev));
-    bft_pool_set_stream(dev, s);
-    DevBuf scratch;
-    for (int i = 0; i < count; i++) CK(test_scan_one(kind, d_in, sizes[i], h_outs[i], d_totals + i, true, param, s, scratch));
-    HIPCK(hipStreamSynchronize(s));
-    return BFT_GPU_OK;
-}
-// The contract of bft_scan.h: a sort that writes a scan's scratch block sets its tag to 0.  An exclusive u32 sum of d_in[0 .. n_scan) into d_out1,
-// a sort of the u64 keys d_keys[0 .. n_sort) on [0, 64) into d_sorted with the same block as its scratch, and -- only when the sort left tag == 0 --
-// the same scan again into d_out2.  info: {tag after the sort, block bytes before the sort, after it}.  BFT_GPU_E_STATE: the sort left a tag the
-// second scan would have trusted (it would have claimed tiles from the sort's words).
-extern "C" int bft_gpu_test_scan_sort_scan(const uint32_t* d_in, uint64_t n_scan, const uint64_t* d_keys, uint64_t n_sort, uint32_t* d_out1, uint32_t* d_out2, uint64_t* d_sorted,
-                                           uint64_t* info, void* hip_stream) {
-    if (!d_in || !d_keys || !d_out1 || !d_out2 || !d_sorted || !info) return fail(BFT_GPU_E_ARG, "NULL argument");
-    hipStream_t s = (hipStream_t)hip_stream;
-    int dev = 0;
-    HIPCK(hipGetDevice(&dev));
-    bft_pool_set_stream(dev, s);
-    DevBuf scratch, tk;
-    CK(tk.alloc(std::max<uint64_t>(n_sort, 1) * 8));
-    CK(bft_scan::exclusive_sum_ptr<uint32_t>(d_in, d_out1, n_scan, s, scratch, nullptr, true));
-    info[1] = scratch.bytes;
-    CK((bft_rs::sort<uint64_t, bft_rs::NoVal, bft_rs::PtrIn<uint64_t, bft_rs::NoVal>>(bft_rs::PtrIn<uint64_t, bft_rs::NoVal>{d_keys, nullptr}, n_sort, (uint64_t*)d_sorted,
-                                                                                      (bft_rs::NoVal*)nullptr, tk.as<uint64_t>(), (bft_rs::NoVal*)nullptr, 0u, 64u, s, scratch)));
-    info[0] = scratch.tag;
-    info[2] = scratch.bytes;
-    if (scratch.tag != 0) {
-        HIPCK(hipStreamSynchronize(s));
-        return fail(BFT_GPU_E_STATE, "the sort wrote the scan's scratch block and left its tag");
-    }
-    CK(bft_scan::exclusive_sum_ptr<uint32_t>(d_in, d_out2, n_scan, s, scratch, nullptr, true));
-    HIPCK(hipStreamSynchronize(s));
-    return BFT_GPU_OK;
-}
-
 extern "C" int bft_gpu_set_option(bft_gpu* h, const char* name, int64_t value) {
     if (!h || !name) return fail(BFT_GPU_E_ARG, "NULL argument");
     const std::string nm(name);
@@ -2690,7 +1673,7 @@ extern "C" int bft_gpu_set_option(bft_gpu* h, const char* name, int64_t value) {
     } else if (nm == "query_probe") {
         if (value != 0 && value != 4 && value != 8) return fail(BFT_GPU_E_ARG, "query_probe must be 0 (automatic), 4 or 8");
         h->opt_probe = (int)value;
-        h->im.probe_big = probe_mode(h->opt_probe ? h->opt_probe : h->tuned_probe);
+        h->im.probe_big = bft_probe_mode(h->opt_probe ? h->opt_probe : h->tuned_probe);
     } else if (nm == "node_hash") {  // 1 (default): levels below the root through the node prefix hash; 0: through the containers
         if (value < 0 || value > 2) return fail(BFT_GPU_E_ARG, "node_hash must be 0, 1 or 2");
         h->opt_node_hash = (int)value;
@@ -2769,7 +1752,7 @@ extern "C" int bft_gpu_set_option(bft_gpu* h, const char* name, int64_t value) {
             CK(wait_foreign_stream(h));
             HIPCK(hipStreamSynchronize(h->stream));
             CK(bft_ensure_table(h));
-            CK(tune_residency(h));
+            CK(bft_tune_residency(h));
         }
     } else if (nm == "query_dynamic") {  // 0: the k-mer hash kernels split their batch by workgroup number (what they did before the claims)
         h->opt_query_dynamic = value != 0;
@@ -2798,12 +1781,7 @@ extern "C" int bft_gpu_set_option(bft_gpu* h, const char* name, int64_t value) {
         // anywhere up to the end of the range it was given, i.e. the next launch's base (1: one below it, 2: exactly there, 3: where it started)
         if (value < 1 || value > 3) return fail(BFT_GPU_E_ARG, "test_stale_claims must be 1, 2 or 3");
         ENTER(h);
-        if (h->kh_ctr) {
-            HIPCK(hipDeviceSynchronize());
-            unsigned long long v[bft_gpu::KH_CTR_SLOTS];
-            for (int i = 0; i < bft_gpu::KH_CTR_SLOTS; i++) v[i] = value == 3 ? 0ull : h->kh_ctr_base[i] - (value == 1 && h->kh_ctr_base[i] ? 1ull : 0ull);
-            HIPCK(hipMemcpy(h->kh_ctr, v, sizeof(v), hipMemcpyHostToDevice));
-        }
+        CK(h->claims.stale((int)value));
     } else if (nm == "test_no_cs_bitmaps") {  // test hook (tests/test_gpu_setops.py): the bitmap form of the dictionary is not derived (what happens by itself
         // where it would pass 4 GiB); one that exists is released, so the id lists serve the colour rows and the set operations from here on
         ENTER(h);
@@ -2873,10 +1851,10 @@ extern "C" int bft_gpu_kernel_time(bft_gpu* h, double* ms, uint64_t* launches, i
 
 extern "C" int bft_gpu_build_time(bft_gpu* h, double* ms, int n_out) {
     if (!h || !ms) return fail(BFT_GPU_E_ARG, "NULL argument");
-    const double v[25] = {h->build_ms[0], h->build_ms[1], h->build_ms[2], h->build_ms[3], h->build_ms[4], (double)query_residency(h), h->tune_ms[0], h->tune_ms[1],
+    const double v[25] = {h->build_ms[0], h->build_ms[1], h->build_ms[2], h->build_ms[3], h->build_ms[4], (double)bft_query_residency(h), h->tune_ms[0], h->tune_ms[1],
                           h->im.probe_big ? 8.0 : 4.0, (double)h->kh_lines, h->kh_ms, (double)h->msd_max_bucket, (double)bft_test_exact_passes(), g_malloc_ms,
                           (double)(h->im.rdir ? (h->im.rstart ? 2 : 1) : 0), h->rstart_tune_ms[0], h->rstart_tune_ms[1],
-                          (double)h->nph_inserted, (double)h->nph_dropped, h->tune_ms[2], (double)h->claims_static_launches,
+                          (double)h->nph_inserted, (double)h->nph_dropped, h->tune_ms[2], (double)h->claims.static_launches,
                           (double)h->im.kh.S, (double)h->im.kh.db, (double)h->im.kh.maxd, (double)h->kh_ovf_n};
     for (int i = 0; i < n_out && i < 25; i++) ms[i] = v[i];
     return BFT_GPU_OK;
@@ -2953,34 +1931,6 @@ extern "C" int bft_gpu_colorset(bft_gpu* h, uint32_t cs, uint32_t* ids, uint32_t
     if (ids) {
         if (cap < b - a) return fail(BFT_GPU_E_NOSPACE, "ids buffer too small");
         memcpy(ids, &h->cs_ids[a], (size_t)(b - a) * 4);
-    }
-    return BFT_GPU_OK;
-}
-
-// What the reference keeps in resultPresence (include/Node.h:60-92) for a found k-mer, as indexes instead of host pointers:
-// the row of the k-mer in the sorted table (the order of bft_gpu_extract) and the id of its colour set.
-extern "C" int bft_gpu_query_rows(bft_gpu* h, const uint8_t* kmers, uint64_t n, uint8_t* present_bits, uint32_t* rows, uint32_t* colorsets) {
-    if (!h || (!kmers && n)) return fail(BFT_GPU_E_ARG, "NULL argument");
-    ENTER(h);
-    CK(bft_ensure_built(h));
-    if (n && n <= BFT_PIN_MAX_N) return query_small(h, kmers, n, present_bits, rows, colorsets);
-    const uint64_t chunk = 1ull << 24;
-    const uint64_t mc = std::min(n, chunk);
-    DevBuf dk, db, dr, dc;
-    CK(dk.alloc(mc * h->B));
-    CK(db.alloc(((mc + 63) / 64) * 8));
-    CK(dr.alloc(mc * 4));
-    if (colorsets) CK(dc.alloc(mc * 4));
-    for (uint64_t a = 0; a < n; a += chunk) {
-        const uint64_t m = std::min(chunk, n - a);
-        CK(query_rows(h, kmers + a * h->B, m, dk, db, dr, present_bits ? present_bits + a / 8 : nullptr));
-        if (rows) HIPCK(hipMemcpyAsync(rows + a, dr.p, m * 4, hipMemcpyDeviceToHost, h->stream));
-        if (colorsets) {
-            hipLaunchKernelGGL(k_row_colorsets, dim3(grid_for((m + 255) / 256)), dim3(256), 0, h->stream, dr.as<uint32_t>(), h->im.tcol, m, dc.as<uint32_t>());
-            HIPCK(hipGetLastError());
-            HIPCK(hipMemcpyAsync(colorsets + a, dc.p, m * 4, hipMemcpyDeviceToHost, h->stream));
-        }
-        HIPCK(hipStreamSynchronize(h->stream));
     }
     return BFT_GPU_OK;
 }

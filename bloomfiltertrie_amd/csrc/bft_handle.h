@@ -1,6 +1,7 @@
 // bft_handle.h -- the handle behind the C-ABI (struct bft_gpu) and the host helpers every entry point needs, for the translation units that hold
-// entry points: bft_gpu.hip (which defines the helpers), bft_run.hip (the build's run stage) and the analysis families bft_prefix.hip, bft_paths.hip, bft_components.hip, bft_pangenome.hip,
-// bft_subgraph.hip, bft_marking.hip, bft_setops.hip, bft_union.hip, bft_ingest.hip.
+// entry points: bft_gpu.hip (lifecycle, pool, log, image binding and commit, files, options and info: it defines the helpers), bft_query.hip (the k-mer and
+// sequence queries, their tuner, the claim slots), bft_run.hip (the build's run stage, the sort and scan test hooks) and the analysis families
+// bft_prefix.hip, bft_paths.hip, bft_components.hip, bft_pangenome.hip, bft_subgraph.hip, bft_marking.hip, bft_setops.hip, bft_union.hip, bft_ingest.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -64,6 +65,47 @@ struct Carver {
     void take(T*& p, size_t bytes) { p = (T*)((uintptr_t)base + off); off += (bytes + 255) & ~(size_t)255; }
 };
 
+// The claim counters of a handle.  The k-mer hash kernels and the walk claim their blocks of k-mers from a counter instead of splitting them by
+// workgroup number (k_query_kh, bft_kh.hip): one counter per stream that launches them -- launches of one stream follow each other, so a counter has one
+// user at a time; it only grows, every launch with a range of its own (bft_claims.h).  A handle keeps a counter for each of KH_CTR_SLOTS streams; queried
+// on more, it hands the least recently used slot to the new stream once that slot's last launch is known to be over (an event per slot), else the
+// launch runs static rounds and is counted (bft_gpu_build_time, entry 20: nothing is silent).  Defined in bft_query.hip.
+struct ClaimSlots {
+    static constexpr int KH_CTR_SLOTS = 32;
+    ClaimSlots() = default;
+    ClaimSlots(const ClaimSlots&) = delete;
+    ClaimSlots& operator=(const ClaimSlots&) = delete;
+    ~ClaimSlots() {
+        if (ctr) (void)hipFree(ctr);
+        for (int i = 0; i < KH_CTR_SLOTS; i++)
+            if (ev[i]) (void)hipEventDestroy(ev[i]);
+    }
+    // The counters, allocated and zeroed once, when the first image is committed (bft_commit_image, bft_gpu_image_unpack) -- never on the path of a
+    // query call.  A failure is final: every launch of the handle then runs static rounds.
+    void ensure();
+    // ctr: the counter of stream s with the range this launch may use, or {NULL}: every round of blocks is dealt out by workgroup number (not wanted --
+    // the option, the environment, a batch too small to matter: the caller's test --, no counters, s being captured, or every slot busy).  units: what
+    // the launch deals out (blocks of 256 k-mers, chunks of 1024) -- the slot's base moves on by that plus what the resident workgroups can claim beyond
+    // it, so the next launch starts above anything this one can leave behind, finished or not (bft_claims.h).  slot: for launched().
+    struct Claim { BftClaimCtr ctr; int slot; };
+    Claim take(hipStream_t s, bool wanted, uint64_t units);
+    // behind a launch that was given a counter: where the slot's last use ends (only looked at when the slots run out)
+    void launched(int slot, hipStream_t s);
+    // test hook ("test_stale_claims"): every counter as a launch that never finished can leave it -- anywhere up to the end of the range it was given,
+    // i.e. the next launch's base (mode 1: one below it, 2: exactly there, 3: where it started); synchronises the device
+    int stale(int mode);
+    uint64_t static_launches = 0;  // launches that wanted a counter and found every slot taken by streams with work still in flight
+private:
+    unsigned long long* ctr = nullptr;  // (its own hipMalloc, not a block of the cache: nothing that was released while still in flight may write here)
+    hipStream_t stream[KH_CTR_SLOTS] = {};
+    unsigned long long base[KH_CTR_SLOTS] = {};  // where the next launch's range of the slot's counter starts (bft_claims.h)
+    uint64_t tick[KH_CTR_SLOTS] = {};            // last use: a handle queried on more streams than slots recycles the least recently used
+    uint64_t clock = 0;
+    hipEvent_t ev[KH_CTR_SLOTS] = {};            // end of the slot's last launch (recorded once half of the slots are in use)
+    int used = 0;
+    bool failed = false;
+};
+
 struct bft_gpu {
     int k = 0, L = 0, W = 0, B = 0, device = 0, r1 = 0, r2 = 0;
     hipStream_t stream = nullptr;
@@ -91,9 +133,6 @@ struct bft_gpu {
         for (int i = 0; i < RING_SLOTS; i++)
             if (ring_ev[i]) (void)hipEventDestroy(ring_ev[i]);
         if (ring) (void)hipHostFree(ring);
-        if (kh_ctr) (void)hipFree(kh_ctr);
-        for (int i = 0; i < KH_CTR_SLOTS; i++)
-            if (kh_ctr_ev[i]) (void)hipEventDestroy(kh_ctr_ev[i]);
     }
 
     // pending insert log (SoA: W key arrays of log_cap entries, then genome ids)
@@ -138,7 +177,7 @@ struct bft_gpu {
     double kh_ms = 0;             // GPU time of the last fill
     hipStream_t stream2 = nullptr; // bft_gpu_build fills the k-mer hash here while the containers are assembled on `stream`
     int opt_root_direct = 3;      // "root_direct": 0 = containers, 1 = direct table, 2 = direct table + range table, 3 = 1 or 2, whichever
-                                  // measured faster on this image (tune_residency)
+                                  // measured faster on this image (bft_tune_residency)
     bool rstart_ok = false;       // d_rstart holds the range table of the current image
     int tuned_rstart = -1;        // result of that measurement (-1 = none)
     double rstart_tune_ms[2] = {0, 0};
@@ -171,36 +210,23 @@ struct bft_gpu {
     uint32_t root_ncc = 0;
     uint64_t idx_sizes[9] = {0};
     // The container walk (k_query*): how it sits on a CU and how it probes suffix groups.  0 = by rule from the shape of the index
-    // (default_launch_shape), or -- after bft_gpu_set_option("tune", 1) -- as measured on the image (tune_residency).
+    // (default_launch_shape), or -- after bft_gpu_set_option("tune", 1) -- as measured on the image (bft_tune_residency).
     int opt_wgs_per_cu = 0;   // 1 / 2 workgroups of 1024 threads per CU, 3 = two of 768
     int tuned_wgs = 0;
     int opt_probe = 0;        // suffix-group probe: 4 or 8 rows per block (BftImage::probe_big)
     int tuned_probe = 0;
     double tune_ms[3] = {0, 0, 0};  // best time of the tuning batch per residency 1 / 2 / 3
     int opt_grid_mult = 1;    // grid = resident workgroups x this
-    // The k-mer hash kernels claim their blocks of k-mers from a counter instead of splitting them by workgroup number (k_query_kh,
-    // bft_kh.hip): one counter per stream that launches them -- launches of one stream follow each other, so a counter has one user at
-    // a time; it only grows, every launch with a range of its own (bft_claims.h).  Batches too small to matter take the static split.
+    // The query kernels claim their blocks of k-mers from a counter per stream (ClaimSlots).  Batches too small to matter take the static split.
     int opt_query_dynamic = 1;
     uint64_t opt_query_dynamic_min = (uint64_t)1 << 16;  // batches below this many k-mers (lines of work for the branching kernel) keep the static split
-    uint64_t claims_static_launches = 0;  // launches that wanted a counter and found every slot taken by streams with work still in flight
     uint32_t opt_query_chunk = 4;  // largest claim, in blocks of 256 k-mers (4 = every claim: the smaller the window of the query stream the
                                    // resident workgroups read at a time, the better -- 2.61 / 2.62 / 2.65 / 2.70 ms at 4 / 16 / 32 / 64)
-    static constexpr int KH_CTR_SLOTS = 32;
-    unsigned long long* kh_ctr = nullptr;  // (its own hipMalloc, not a block of the cache: nothing that was released while still in flight may write here)
-    hipStream_t kh_ctr_stream[KH_CTR_SLOTS] = {};
-    unsigned long long kh_ctr_base[KH_CTR_SLOTS] = {};  // where the next launch's range of the slot's counter starts (bft_claims.h)
-    uint64_t kh_ctr_tick[KH_CTR_SLOTS] = {};            // last use: a handle queried on more streams than slots recycles the least recently used
-    uint64_t kh_ctr_clock = 0;
-    hipEvent_t kh_ctr_ev[KH_CTR_SLOTS] = {};            // end of the slot's last launch (recorded once half of the slots are in use)
-    int kh_ctr_pending = -1;
-    int kh_ctr_used = 0;
-    bool kh_ctr_failed = false;
+    ClaimSlots claims;
 
     // Scratch of the query families: an owner (HandleScratch) and the blocks it guards -- grown, never shrunk, one stream at a time.
     HandleScratch sq{"sequence query"};
     DevBuf sq_codes, sq_bad, sq_npos, sq_poff, sq_tmp, sq_cs, sq_tile;  // sequence queries: codes, plan, scan temporary, colour set per position
-    uint64_t sq_units = 0;           // bound on the blocks of k-mer positions the sequence kernel deals out (claim_counters)
     HandleScratch qc{"colour query"};
     DevBuf qc_cs, qc_tmp;            // resident colour-list queries: colour-set id per k-mer, the scan's temporary
     DevBuf qc_kh;                    // k_colors_kh's tile counter and states (bft_kh_colors_scratch_bytes).  A block of its own, never a part of qc_tmp: the
@@ -294,8 +320,15 @@ struct StageScope {
     ~StageScope();
 };
 
+// ---- bft_query.hip ----
+// rows per probe block of the suffix-group search ("query_probe": 4 or 8) -> BftImage::probe_big
+static inline uint32_t bft_probe_mode(int rows) { return rows == 8 ? 1u : 0u; }
+int bft_query_residency(const bft_gpu* h);  // resident walk workgroups per CU the next launch runs with: the option, else the measured / default shape, else 2
+int bft_tune_residency(bft_gpu* h);         // "tune": the launch shape of the walk measured on the current image (built, table resident; synchronises)
 // presence bits (and rows, or colour sets with im.emit_cs) of n packed k-mers on stream s, by whichever of the k-mer hash and the walk answers
 int bft_launch_query(bft_gpu* h, const uint8_t* d_kmers, uint64_t n, uint64_t* d_bits64, uint32_t* d_rows, hipStream_t s, int rec_bytes = 0);
+// (bft_run.hip) Steps 1-3 of a build: the run of h's insertion log, on h->stream; sets h->front_redone and h->msd_max_bucket
+int bft_make_run(bft_gpu* h, BftPairRun& run);
 // (bft_run.hip) Stable LSD sort of `total` entries by (keys word 0..W-1 as one big integer, then g) on the handle's stream, synchronised.  keys: SoA with stride `stride`; result in okeys (stride ostride) / og.
 int bft_sort_pairs(bft_gpu* h, const uint64_t* keys, uint64_t stride, const uint32_t* g, uint64_t total, uint64_t* okeys, uint64_t ostride, uint32_t* og,
                    bool g_already_ordered, bool is_log = false);

@@ -1,6 +1,6 @@
 // bft_kernels_build.h -- de-duplication of the sorted (k-mer, genome) pairs for the bulk build: k_iota, k_gather, k_flags, k_scatter, the
 // root-prefix bucket bounds, the on-the-fly scatters.  Device code of libbft_gpu.so, included by bft_run.hip only (one translation unit: the
-// kernels are launched from the host code there; the sort and scan inputs that go with them: bft_run.h).
+// kernels are launched from the host code there; the sort and scan inputs that go with them are defined there).
 #pragma once
 __global__ void k_iota(uint32_t* p, uint64_t n) {
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) p[i] = (uint32_t)i;
@@ -88,7 +88,7 @@ __global__ void k_msd_max(const uint32_t* __restrict__ off, uint32_t nb, uint32_
         if (m) atomicMax(max_bucket, m);
     }
 }
-// sorted composites (BftCompose, bft_run.h) and the scan of their flags (BftPairFlags) -> genome-id lists, distinct k-mers, segment offsets
+// sorted composites (BftCompose, bft_run.hip) and the scan of their flags (BftPairFlags) -> genome-id lists, distinct k-mers, segment offsets
 __global__ void k_scatter_c(const uint64_t* __restrict__ c, uint32_t gb, uint64_t n, const uint64_t* __restrict__ pos, uint32_t* __restrict__ pg,
                             uint64_t* __restrict__ tk, uint32_t* __restrict__ seg_off) {
     const uint64_t gmask = (1ull << gb) - 1ull;

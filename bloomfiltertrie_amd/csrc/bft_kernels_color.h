@@ -1,5 +1,5 @@
 // bft_kernels_color.h -- colour-set retrieval: id lists (k_color_fill_cs), bitmap dictionary and fixed-width rows (k_cs_bitmaps, k_color_rows_bm, k_color_rows_bm16, k_color_rows), k_row_colorsets
-// Device code of libbft_gpu.so, included by bft_gpu.hip only (one translation unit: the kernels are templates launched from
+// Device code of libbft_gpu.so, included by bft_query.hip only (one translation unit: the kernels are templates launched from
 // the host code there).
 #pragma once
 #include "bft_rows16.h"

@@ -1,7 +1,7 @@
 // bft_kernels_query.h -- T-form conversion into the insert log; k_query / k_query8 / k_query6 and k_branching* (presence and branching as a container walk;
 // the same queries through the k-mer hash: bft_kh.hip)
-// Device code of libbft_gpu.so, included by bft_gpu.hip only (one translation unit: the kernels are templates launched from
-// the host code there).
+// Device code of libbft_gpu.so, included by bft_query.hip (the kernels are templates launched from the host code there), by bft_walkh.hip (the walk's body
+// for k_query6h) and, for k_pack_to_tform, by bft_gpu.hip.
 #pragma once
 // ------------------------------------------------------------------------------------------------
 // device helpers

@@ -1,5 +1,5 @@
 // bft_kernels_seq.h -- sequence queries: k_seq_encode / k_seq_plan (bft_kernels_seqenc.h) / k_seq_walk (window + walk + colour set) / k_seq_tally (counters + threshold per sequence)
-// Device code of libbft_gpu.so, included by bft_gpu.hip only (one translation unit: the kernels are templates launched from
+// Device code of libbft_gpu.so, included by bft_query.hip only (one translation unit: the kernels are templates launched from
 // the host code there).
 #pragma once
 #include "bft_kernels_seqenc.h"

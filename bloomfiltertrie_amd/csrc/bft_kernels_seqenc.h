@@ -1,5 +1,5 @@
 // bft_kernels_seqenc.h -- the front of a sequence batch: k_seq_encode (ASCII -> code and "not ACGTU" streams), k_seq_plan (k-mer positions per sequence),
-// k_seq_tiles (sequence of every 64-position tile).  Device code shared by the translation units that read sequences: bft_gpu.hip (sequence queries,
+// k_seq_tiles (sequence of every 64-position tile).  Device code shared by the translation units that read sequences: bft_query.hip (sequence queries,
 // bft_kernels_seq.h) and bft_ingest.hip (insertion from sequences); each includes it once, bft_ingest.hip inside its unnamed namespace.
 #pragma once
 // ---- query_sequence (src/bft.c:1241-1351, harness src/file_io.c:1464-1574): every k-mer of every sequence ----

@@ -773,7 +773,7 @@ int bft_kh_dump(const BftImage& im, uint64_t* d_keys, uint64_t stride, uint32_t*
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// launchers (called from bft_gpu.hip).  The kernels are instantiated for the (key words, slots per line) pairs an index can have:
+// launchers (called from bft_query.hip).  The kernels are instantiated for the (key words, slots per line) pairs an index can have:
 // one-word keys (k <= 32) 10..4 slots, two-word keys 10..3, three-word keys 4..2, four-word keys 2..1.
 // ---------------------------------------------------------------------------------------------------------------------------------
 bool bft_kh_has_kernels(int W, uint32_t S) {

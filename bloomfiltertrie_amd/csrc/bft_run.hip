@@ -2,16 +2,71 @@
 // genome-id lists, the ids).  bft_make_run is the list of the roads a log can take, with their conditions and fallbacks; every road is a function
 // of its own below it.  Sorts and scans are the library's own (bft_sort.h, bft_scan.h); the buckets behind the root-prefix split are
 // bft_front.hip's; the kernels launched here are bft_kernels_build.h's.  bft_sort_pairs, the general permutation sort, is also what
-// bft_ensure_table and the sub-graph build order their records with.  See DESIGN.md "Insertion".
+// bft_ensure_table and the sub-graph build order their records with.  See DESIGN.md "Insertion".  At the end: the sort and scan test hooks, in the
+// unit that instantiates the library's sorts anyway.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "bft_handle.h"
-#include "bft_run.h"
+#include "bft_paths.h"  // BftSpHead (bft_gpu_test_scan_ex)
 #include "bft_scan.h"
+#include "bft_sort.h"
 
 #include "bft_kernels_build.h"
+
+// What the log looks like to the library's sort and scan: the input functors of bft_rs::sort / bft_scan::exclusive_sum that read it (the test hooks at
+// the end run the same instantiations).
+// ---- composite path: one-word keys whose genome ids arrive in ascending order and fit the key's spare low bits ----------------
+// c = (T << gb) | genome: ONE 8-byte array is sorted (on the T bits only: the sort is stable, so the ids keep their ascending
+// order inside a k-mer) instead of 8-byte keys + 4-byte values -- a third less traffic in each of the seven radix passes -- and the
+// de-duplication flags come out of neighbouring composites on the fly instead of through two flag arrays and two scans.
+struct BftCompose {  // input "iterator" of the sort: composite i from the insertion log
+    const uint64_t* k;
+    const uint32_t* g;
+    uint32_t gb;
+    __host__ __device__ uint64_t operator()(uint32_t i) const { return g ? (k[i] << gb) | (uint64_t)g[i] : k[i]; }  // (g == NULL: the log already holds composites)
+    __device__ uint64_t key(uint32_t i) const { return (*this)(i); }  // (as the input of bft_rs::sort)
+    __device__ bft_rs::NoVal val(uint32_t) const { return bft_rs::NoVal{}; }
+};
+// two-word keys: what the root-prefix split moves -- the top 64 bits of the T-form (left-aligned: their top 18 bits are the root prefix) as the
+// key, the bits below them and the genome id as the value (bft_front.hip: BftItem2)
+struct __attribute__((packed, aligned(4))) BftSplit2Val {
+    uint64_t lo;
+    uint32_t id;
+};
+struct BftSplit2In {
+    const uint64_t* k0;  // word 0 (most significant), word 1 of the log
+    const uint64_t* k1;
+    const uint32_t* g;
+    uint32_t sh;  // 2k - 64: the bits of word 1 that belong to the T-form's low part once the top 64 are taken (2 .. 64)
+    __device__ uint64_t key(uint32_t i) const { return sh == 64 ? k0[i] : (k0[i] << (64 - sh)) | (k1[i] >> sh); }
+    __device__ BftSplit2Val val(uint32_t i) const {
+        BftSplit2Val v;
+        v.lo = sh == 64 ? k1[i] : (k1[i] & ((1ull << sh) - 1ull));
+        v.id = g[i];
+        return v;
+    }
+};
+template <class GT>
+struct BftPairIn {  // input of the sorts that move (k-mer, id) pairs: the log's k-mers, its ids narrowed to GT
+    const uint64_t* k;
+    const uint32_t* g;
+    __device__ uint64_t key(uint32_t i) const { return k[i]; }
+    __device__ GT val(uint32_t i) const { return (GT)g[i]; }
+};
+struct BftPairFlags {  // input of the scan: (first pair of its k-mer) << 32 | (first pair of its (k-mer, genome))
+    const uint64_t* c;
+    uint32_t gb;
+    __host__ __device__ uint64_t operator()(uint32_t i) const {
+        const uint64_t a = c[i], b = i ? c[i - 1] : ~a;
+        const uint64_t head = (a >> gb) != (b >> gb), keep = a != b;
+        return (head << 32) | keep;
+    }
+};
+
+thread_local bft_rs::RunRecord bft_rs::g_bft_rs_last;  // what this thread's last library sort ran (test hooks: bft_gpu_test_sort_last)
+int bft_rs::g_bft_rs_rank_mode = -1;  // how bft_sort.h ranks: 0 LDS atomics (lane order checked on the device), 1 ballots ("sort_ballots")
 
 static int bits_for(uint64_t v) {
     int b = 1;
@@ -357,4 +412,193 @@ int bft_make_run(bft_gpu* h, BftPairRun& run) {
         if (!done) CK(general_sort(h, in, run));
     }
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// test hooks (tests/test_gpu_sort_scan.py; not part of include/bft_gpu.h): the library's own sort and scan on the caller's device arrays
+// ------------------------------------------------------------------------------------------------
+// kind 0: u64 keys; 1: u64 keys + u32 values; 2: u32 keys + u32 values.  shape: bft_rs::SHAPE_*.  Stable LSD over the bits [begin_bit, end_bit).
+extern "C" int bft_gpu_test_sort(int kind, int shape, const void* d_keys, const void* d_vals, uint64_t n, unsigned begin_bit, unsigned end_bit, void* d_out_keys, void* d_out_vals,
+                                 void* hip_stream) {
+    if ((!d_keys || !d_out_keys) && n) return bft_fail(BFT_GPU_E_ARG, "NULL argument");
+    hipStream_t s = (hipStream_t)hip_stream;
+    int dev = 0;
+    HIPCK(hipGetDevice(&dev));
+    bft_pool_set_stream(dev, s);
+    int rc = BFT_GPU_E_ARG;
+#define BFT_TS(K, V, SH) rc = bft_rs::sort_pairs<K, V, SH>((const K*)d_keys, (const V*)d_vals, n, (K*)d_out_keys, (V*)d_out_vals, begin_bit, end_bit, s)
+    if (kind == 0) {
+        rc = bft_rs::sort_keys<uint64_t>((const uint64_t*)d_keys, n, (uint64_t*)d_out_keys, begin_bit, end_bit, s);
+    } else if (kind == 1) {
+        if (shape == bft_rs::SHAPE_LIGHT) BFT_TS(uint64_t, uint32_t, bft_rs::SHAPE_LIGHT);
+        else if (shape == bft_rs::SHAPE_BACK) BFT_TS(uint64_t, uint32_t, bft_rs::SHAPE_BACK);
+        else BFT_TS(uint64_t, uint32_t, bft_rs::SHAPE_BIG);
+    } else if (kind == 2) {
+        if (shape == bft_rs::SHAPE_LIGHT) BFT_TS(uint32_t, uint32_t, bft_rs::SHAPE_LIGHT);
+        else if (shape == bft_rs::SHAPE_BACK) BFT_TS(uint32_t, uint32_t, bft_rs::SHAPE_BACK);
+        else BFT_TS(uint32_t, uint32_t, bft_rs::SHAPE_BIG);
+    }
+#undef BFT_TS
+    if (rc) return rc;
+    HIPCK(hipStreamSynchronize(s));
+    return BFT_GPU_OK;
+}
+// kind 0: exclusive sum of u32 (out[n] = the total as well); 1: exclusive sum of u64 (likewise); 2: inclusive max of u64, init 5.  *d_total: the grand total.
+// reps scans in a row share one scratch block (nothing is zeroed between them: bft_scan.h).
+extern "C" int bft_gpu_test_scan(int kind, const void* d_in, uint64_t n, void* d_out, void* d_total, int reps, void* hip_stream) {
+    if ((!d_in || !d_out) && n) return bft_fail(BFT_GPU_E_ARG, "NULL argument");
+    hipStream_t s = (hipStream_t)hip_stream;
+    int dev = 0;
+    HIPCK(hipGetDevice(&dev));
+    bft_pool_set_stream(dev, s);
+    DevBuf scratch;
+    for (int r = 0; r < std::max(1, reps); r++) {
+        if (kind == 0) CK(bft_scan::exclusive_sum_ptr<uint32_t>((const uint32_t*)d_in, (uint32_t*)d_out, n, s, scratch, (unsigned long long*)d_total, true));
+        else if (kind == 1) CK(bft_scan::exclusive_sum_ptr<uint64_t>((const uint64_t*)d_in, (uint64_t*)d_out, n, s, scratch, (unsigned long long*)d_total, true));
+        else if (kind == 2)
+            CK((bft_scan::scan<uint64_t, bft_scan::PtrIn<uint64_t>, bft_scan::Max, true>(bft_scan::PtrIn<uint64_t>{(const uint64_t*)d_in}, (uint64_t*)d_out, n, 5ull, bft_scan::Max(), s, scratch,
+                                                                                          (unsigned long long*)d_total)));
+        else return bft_fail(BFT_GPU_E_ARG, "bad scan kind");
+    }
+    HIPCK(hipStreamSynchronize(s));
+    return BFT_GPU_OK;
+}
+
+// Every (key, value, input) the library sorts (tests/test_gpu_sort_scan_edges.py).  kind: 0 u64 keys; 1 u64 + u32; 2 u32 + u32; 3 u32 + u64 (the
+// genome-id pass); 4 u64 keys through BftCompose (d_vals NULL: the keys as they are, else (key << param) | id[i]); 5 / 6 u64 + u8 / u16 through
+// BftPairIn (d_vals: u32 ids, narrowed); 7 u64 + BftSplit2Val through BftSplit2In (d_keys: word 0; d_vals: word 1 [n] (u64), then the ids [n]
+// (u32); param: sh, 0 = 64); 8 .. 11: u32 + KhRec<W>, W = kind - 7 (d_vals: the packed records).  The shapes each kind is built in:
+// bft_gpu_test_sort_tile != 0.  h_dbase (NULL or 512 words): the sort's last_dbase table, where it made one.
+#define BFT_TSX_KINDS(X)                                                                                        \
+    X(0, SHAPE_BIG, uint64_t, bft_rs::NoVal, (bft_rs::PtrIn<uint64_t, bft_rs::NoVal>{(const uint64_t*)d_keys, nullptr}))                 \
+    X(1, SHAPE_BIG, uint64_t, uint32_t, (bft_rs::PtrIn<uint64_t, uint32_t>{(const uint64_t*)d_keys, (const uint32_t*)d_vals}))           \
+    X(1, SHAPE_LIGHT, uint64_t, uint32_t, (bft_rs::PtrIn<uint64_t, uint32_t>{(const uint64_t*)d_keys, (const uint32_t*)d_vals}))         \
+    X(1, SHAPE_BACK, uint64_t, uint32_t, (bft_rs::PtrIn<uint64_t, uint32_t>{(const uint64_t*)d_keys, (const uint32_t*)d_vals}))          \
+    X(2, SHAPE_BIG, uint32_t, uint32_t, (bft_rs::PtrIn<uint32_t, uint32_t>{(const uint32_t*)d_keys, (const uint32_t*)d_vals}))           \
+    X(2, SHAPE_LIGHT, uint32_t, uint32_t, (bft_rs::PtrIn<uint32_t, uint32_t>{(const uint32_t*)d_keys, (const uint32_t*)d_vals}))         \
+    X(2, SHAPE_BACK, uint32_t, uint32_t, (bft_rs::PtrIn<uint32_t, uint32_t>{(const uint32_t*)d_keys, (const uint32_t*)d_vals}))          \
+    X(3, SHAPE_BIG, uint32_t, uint64_t, (bft_rs::PtrIn<uint32_t, uint64_t>{(const uint32_t*)d_keys, (const uint64_t*)d_vals}))           \
+    X(4, SHAPE_BIG, uint64_t, bft_rs::NoVal, (BftCompose{(const uint64_t*)d_keys, (const uint32_t*)d_vals, param}))                      \
+    X(5, SHAPE_BIG, uint64_t, uint8_t, (BftPairIn<uint8_t>{(const uint64_t*)d_keys, (const uint32_t*)d_vals}))                           \
+    X(6, SHAPE_BIG, uint64_t, uint16_t, (BftPairIn<uint16_t>{(const uint64_t*)d_keys, (const uint32_t*)d_vals}))                         \
+    X(7, SHAPE_BIG, uint64_t, BftSplit2Val, (BftSplit2In{(const uint64_t*)d_keys, (const uint64_t*)d_vals, (const uint32_t*)((const uint64_t*)d_vals + n), param ? param : 64u}))
+extern "C" int bft_gpu_test_sort_ex(int kind, int shape, const void* d_keys, const void* d_vals, uint64_t n, unsigned begin_bit, unsigned end_bit, void* d_out_keys, void* d_out_vals,
+                                    uint32_t param, uint32_t* h_dbase, void* hip_stream) {
+    if (n && (!d_keys || !d_out_keys || (kind != 0 && kind != 4 && (!d_vals || !d_out_vals)))) return bft_fail(BFT_GPU_E_ARG, "NULL argument");
+    if (kind == 7 && param > 64) return bft_fail(BFT_GPU_E_ARG, "test sort: sh");
+    hipStream_t s = (hipStream_t)hip_stream;
+    int dev = 0;
+    HIPCK(hipGetDevice(&dev));
+    bft_pool_set_stream(dev, s);
+    if (kind >= 8 && kind <= 11) return bft_kh_test_sort(kind - 7, shape, (const uint32_t*)d_keys, d_vals, n, begin_bit, end_bit, (uint32_t*)d_out_keys, d_out_vals, s, h_dbase);
+#define BFT_TSX(KIND, SH, K, V, IN)                                                                                                                               \
+    if (kind == KIND && shape == bft_rs::SH) {                                                                                                                    \
+        auto in = IN;  /* (not const: the In type of the product's own instantiations) */                                                                       \
+        return bft_rs::sort_test_run<K, V, decltype(in), bft_rs::SH>(in, n, (K*)d_out_keys, (V*)d_out_vals, begin_bit, end_bit, s, h_dbase);                     \
+    }
+    BFT_TSX_KINDS(BFT_TSX)
+#undef BFT_TSX
+    return bft_fail(BFT_GPU_E_ARG, "test sort: kind / shape");
+}
+// entries per tile of bft_gpu_test_sort_ex(kind, shape) (the one-tile / ranged boundary); 0: that kind is not built in that shape
+extern "C" uint32_t bft_gpu_test_sort_tile(int kind, int shape) {
+    const void *d_keys = nullptr, *d_vals = nullptr;
+    const uint64_t n = 0;
+    const uint32_t param = 0;
+    if (kind >= 8 && kind <= 11) return bft_kh_test_sort_tile(kind - 7, shape);
+#define BFT_TSX(KIND, SH, K, V, IN)                                                                                                                               \
+    if (kind == KIND && shape == bft_rs::SH) {                                                                                                                    \
+        (void)IN;                                                                                                                                                 \
+        return bft_rs::tile_entries<K, V, bft_rs::SH>();                                                                                                          \
+    }
+    BFT_TSX_KINDS(BFT_TSX)
+#undef BFT_TSX
+    return 0u;
+}
+#undef BFT_TSX_KINDS
+// what the last library sort of the calling thread ran: [0] regime (0 copy, 1 one tile, 2 ranged, 3 chained, 255 nothing), [1] passes, [2] tiles,
+// [3] ranges, [4] tiles per range, [5] entries per tile, [6..7] 0; then per pass p < 8, words 8 + 4 p ..: first bit, bits, chains (0: a ranged
+// pass), look-back groups launched (1 or THREADS / 128; 0: a ranged pass).  Returns the words written.
+extern "C" int bft_gpu_test_sort_last(uint64_t* out, int n) {
+    if (!out || n < 0) return bft_fail(BFT_GPU_E_ARG, "NULL argument");
+    const bft_rs::RunRecord& r = bft_rs::g_bft_rs_last;
+    uint64_t w[8 + 4 * bft_rs::MAXP] = {r.regime, r.P, r.tiles, r.ranges, r.tpr, r.tile, 0, 0};
+    for (int p = 0; p < bft_rs::MAXP; p++) {
+        w[8 + 4 * p] = r.bit[p];
+        w[9 + 4 * p] = r.nbits[p];
+        w[10 + 4 * p] = r.nch[p];
+        w[11 + 4 * p] = r.lbg[p];
+    }
+    const int m = std::min<int>(n, (int)(sizeof(w) / 8));
+    for (int i = 0; i < m; i++) out[i] = w[i];
+    return m;
+}
+
+// one scan of bft_gpu_test_scan_ex's kinds: 0 exclusive sum of u32; 1 of u64; 2 inclusive max of u64 from init = param; 3 exclusive sum (u64) of
+// BftPairFlags over u64 composites (d_in; gb = param), as the build numbers its k-mers and pairs; 4 exclusive sum (u32) of BftSpHead over uint2
+// (d_in), as the simple paths are numbered
+static int test_scan_one(int kind, const void* d_in, uint64_t n, void* d_out, void* d_total, bool tail, uint64_t param, hipStream_t s, DevBuf& scratch) {
+    unsigned long long* tot = (unsigned long long*)d_total;
+    switch (kind) {
+    case 0: return bft_scan::exclusive_sum_ptr<uint32_t>((const uint32_t*)d_in, (uint32_t*)d_out, n, s, scratch, tot, tail);
+    case 1: return bft_scan::exclusive_sum_ptr<uint64_t>((const uint64_t*)d_in, (uint64_t*)d_out, n, s, scratch, tot, tail);
+    case 2:
+        return bft_scan::scan<uint64_t, bft_scan::PtrIn<uint64_t>, bft_scan::Max, true>(bft_scan::PtrIn<uint64_t>{(const uint64_t*)d_in}, (uint64_t*)d_out, n, param, bft_scan::Max(), s,
+                                                                                         scratch, tot, tail);
+    case 3: return bft_scan::exclusive_sum<uint64_t>(BftPairFlags{(const uint64_t*)d_in, (uint32_t)param}, (uint64_t*)d_out, n, s, scratch, tot, tail);
+    case 4: return bft_scan::exclusive_sum<uint32_t>(BftSpHead{(const uint2*)d_in, n}, (uint32_t*)d_out, n, s, scratch, tot, tail);
+    default: return bft_fail(BFT_GPU_E_ARG, "bad scan kind");
+    }
+}
+// one scan (kinds: test_scan_one) on a block of its own; tail: out[n] receives the total as well (else it is not written)
+extern "C" int bft_gpu_test_scan_ex(int kind, const void* d_in, uint64_t n, void* d_out, void* d_total, int tail, uint64_t param, void* hip_stream) {
+    if ((!d_in || !d_out) && n) return bft_fail(BFT_GPU_E_ARG, "NULL argument");
+    hipStream_t s = (hipStream_t)hip_stream;
+    int dev = 0;
+    HIPCK(hipGetDevice(&dev));
+    bft_pool_set_stream(dev, s);
+    DevBuf scratch;
+    CK(test_scan_one(kind, d_in, n, d_out, d_total, tail != 0, param, s, scratch));
+    HIPCK(hipStreamSynchronize(s));
+    return BFT_GPU_OK;
+}
+// count scans one after the other on ONE scratch block, as the library's long-lived blocks are used: scan i reads d_in[0 .. sizes[i]) and writes
+// h_outs[i] (sizes[i] + 1 entries: with the total behind them) and d_totals[i] (u64)
+extern "C" int bft_gpu_test_scan_seq(int kind, const void* d_in, const uint64_t* sizes, int count, void* const* h_outs, uint64_t* d_totals, uint64_t param, void* hip_stream) {
+    if (!d_in || !sizes || !h_outs || !d_totals || count < 0) return bft_fail(BFT_GPU_E_ARG, "NULL argument");
+    hipStream_t s = (hipStream_t)hip_stream;
+    int dev = 0;
+    HIPCK(hipGetDevice(&dev));
+    bft_pool_set_stream(dev, s);
+    DevBuf scratch;
+    for (int i = 0; i < count; i++) CK(test_scan_one(kind, d_in, sizes[i], h_outs[i], d_totals + i, true, param, s, scratch));
+    HIPCK(hipStreamSynchronize(s));
+    return BFT_GPU_OK;
+}
+// The contract of bft_scan.h: a sort that writes a scan's scratch block sets its tag to 0.  An exclusive u32 sum of d_in[0 .. n_scan) into d_out1,
+// a sort of the u64 keys d_keys[0 .. n_sort) on [0, 64) into d_sorted with the same block as its scratch, and -- only when the sort left tag == 0 --
+// the same scan again into d_out2.  info: {tag after the sort, block bytes before the sort, after it}.  BFT_GPU_E_STATE: the sort left a tag the
+// second scan would have trusted (it would have claimed tiles from the sort's words).
+extern "C" int bft_gpu_test_scan_sort_scan(const uint32_t* d_in, uint64_t n_scan, const uint64_t* d_keys, uint64_t n_sort, uint32_t* d_out1, uint32_t* d_out2, uint64_t* d_sorted,
+                                           uint64_t* info, void* hip_stream) {
+    if (!d_in || !d_keys || !d_out1 || !d_out2 || !d_sorted || !info) return bft_fail(BFT_GPU_E_ARG, "NULL argument");
+    hipStream_t s = (hipStream_t)hip_stream;
+    int dev = 0;
+    HIPCK(hipGetDevice(&dev));
+    bft_pool_set_stream(dev, s);
+    DevBuf scratch, tk;
+    CK(tk.alloc(std::max<uint64_t>(n_sort, 1) * 8));
+    CK(bft_scan::exclusive_sum_ptr<uint32_t>(d_in, d_out1, n_scan, s, scratch, nullptr, true));
+    info[1] = scratch.bytes;
+    CK((bft_rs::sort<uint64_t, bft_rs::NoVal, bft_rs::PtrIn<uint64_t, bft_rs::NoVal>>(bft_rs::PtrIn<uint64_t, bft_rs::NoVal>{d_keys, nullptr}, n_sort, (uint64_t*)d_sorted,
+                                                                                      (bft_rs::NoVal*)nullptr, tk.as<uint64_t>(), (bft_rs::NoVal*)nullptr, 0u, 64u, s, scratch)));
+    info[0] = scratch.tag;
+    info[2] = scratch.bytes;
+    if (scratch.tag != 0) {
+        HIPCK(hipStreamSynchronize(s));
+        return bft_fail(BFT_GPU_E_STATE, "the sort wrote the scan's scratch block and left its tag");
+    }
+    CK(bft_scan::exclusive_sum_ptr<uint32_t>(d_in, d_out2, n_scan, s, scratch, nullptr, true));
+    HIPCK(hipStreamSynchronize(s));
+    return BFT_GPU_OK;
 }

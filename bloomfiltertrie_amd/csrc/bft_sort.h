@@ -870,7 +870,7 @@ static inline int cu_count() {
 }
 
 // 0: ranks from LDS atomics (the device passed the lane-order check), 1: from ballots.  force >= 0 sets it ("sort_ballots" option, tests).
-extern int g_bft_rs_rank_mode;  // (one per process: bft_gpu.hip; -1 = not checked yet)
+extern int g_bft_rs_rank_mode;  // (one per process: bft_run.hip; -1 = not checked yet)
 static inline int rank_mode(hipStream_t s, int force = -1) {
     int& mode = g_bft_rs_rank_mode;
     if (force >= 0) { mode = force; return mode; }
@@ -896,7 +896,7 @@ struct RunRecord {
     uint32_t bit[MAXP] = {}, nbits[MAXP] = {};
     uint32_t nch[MAXP] = {}, lbg[MAXP] = {};  // chained passes: chains, look-back groups launched (1 or GMAX); 0 for a ranged pass
 };
-extern thread_local RunRecord g_bft_rs_last;  // (bft_gpu.hip)
+extern thread_local RunRecord g_bft_rs_last;  // (bft_run.hip)
 
 // scratch of one sort call (u32 words)
 struct Layout {

@@ -337,7 +337,7 @@ BFT_HD int bft_first_cc_blk(const uint8_t* blk, uint32_t wb, uint32_t h1, uint32
 
 // Where the walk reads the hash table, and the root node's Bloom block and CC headers, from.
 // Host tests and non-staged kernels read the image in global memory; k_query stages them in LDS
-// (BftRootLds in bft_gpu.hip) because every query of a batch goes through them.
+// (BftRootLds, bft_kernels_query.h) because every query of a batch goes through them.
 struct BftRootGlobal {
     const BftImage& im;
     BFT_HD explicit BftRootGlobal(const BftImage& i) : im(i) {}

@@ -762,3 +762,67 @@ def test_recorded_id_list_call_that_would_grow_the_scratch_is_refused():
     assert (bits.cpu().numpy()[: len(eb)] == eb).all() and (offs.cpu().numpy().view(np.uint64) == eoff).all()
     assert int(need.item()) == len(eids) and (ids.cpu().numpy().view(np.uint32)[: len(eids)] == eids).all()
     t.close()
+
+
+# ---- 2f: the tuner gives back what it borrows ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("k", [27, 63])
+def test_tune_leaves_the_handle_as_it_found_it(k):
+    """set_option("tune", 1) measures candidate launch shapes of the container walk on the image (an index of at least 2^16 k-mers: below that
+    the tuner returns before it measures).  It does not time itself (kernel_time's launch count stands still over the tune), it leaves timing on
+    (a query after it is counted as one before it was), it respects the options the caller fixed (query_wgs_per_cu, query_probe), and the
+    answers of presence, rows, branching and sequence queries are the same before and after -- through the walk and, at the end, through the
+    k-mer hash with walk_hash."""
+    g = S.random_genome(75000, 300 + k)
+    km = S.distinct(S.kmers_of(g, k))
+    t = BFT(k)
+    t.insert_kmers(km, 0)
+    t.insert_kmers(km[::2], 1)
+    t.insert_kmers(km[::3], 2)
+    t.build()
+    assert t.info()["kmers"] >= 65536
+    t.set_option("kmer_hash", 0)  # the walk answers
+    t.set_option("timing", 1)
+    q = np.ascontiguousarray(np.concatenate([km[:5000], S.snp_mutants(km[5000:10000], k, 7)]))
+    reads = [bytes(S._ASCII[g[a:a + 200]]).decode() for a in range(1000, 71000, 7000)]
+    assert len(reads) == 10
+
+    def answers():
+        bits, rows, sets = t.query_rows(q)
+        br, cnt = t.query_branching(q[:2000], with_counts=True)
+        return t.query_presence(q), bits, rows, sets, br, cnt, t.query_sequences(reads, 0.5)
+
+    def same(a, b, what):
+        for i, (x, y) in enumerate(zip(a[:-1], b[:-1])):
+            assert (x == y).all(), (what, i)
+        assert a[-1] == b[-1], what
+
+    ref = answers()
+    assert S.from_bits(ref[0], len(q))[:5000].all() and (ref[0] == ref[1]).all()
+    _, l0 = t.kernel_time(reset=False)
+    t.query_presence(q)
+    _, l1 = t.kernel_time(reset=False)
+    per_call = l1 - l0
+    assert per_call >= 1
+    t.set_option("query_wgs_per_cu", 1)
+    if k == 27:
+        t.set_option("query_probe", 8)
+    t.set_option("tune", 1)
+    _, l2 = t.kernel_time(reset=False)
+    assert l2 == l1  # the tuner does not time itself
+    bt = t.build_time()
+    assert bt["query_wgs_per_cu"] == 1.0
+    if k == 27:
+        assert bt["query_probe_rows"] == 8.0
+    t.query_presence(q)
+    _, l3 = t.kernel_time(reset=False)
+    assert l3 - l2 == per_call  # timing is still on
+    same(answers(), ref, "after a tune with the shape fixed by options")
+    t.set_option("query_wgs_per_cu", 0)
+    t.set_option("query_probe", 0)
+    t.set_option("tune", 1)
+    assert t.build_time()["query_wgs_per_cu"] in (1.0, 2.0, 3.0)
+    same(answers(), ref, "after a free tune")
+    t.set_option("kmer_hash", 1)
+    t.set_option("walk_hash", 1)
+    same(answers(), ref, "through the k-mer hash and walk_hash")
+    t.close()
