@@ -1,6 +1,6 @@
 """Connected components on the GPU (bft_gpu_components / _dev, BFT.components): against ground truth computed in Python from the inserted k-mer
 strings and their genome sets -- a dict and a union-find for small indexes, scipy.sparse.csgraph for large ones; the product's extract only gives
-the rows that number the components.  Key widths W = 1..4; the whole graph and sub-graphs of one, two and all ids and of an id past the last
+the rows that number the components.  Key widths W = 1, 2 and 4 (KS has no three-word key, k = 65..96; tests/test_gpu_graph_edges.py runs W = 3 and the other key shapes); the whole graph and sub-graphs of one, two and all ids and of an id past the last
 genome; hand-made graphs (a lone k-mer, a homopolymer self-loop, a circular genome, two unrelated genomes, a bridge, an inner deletion that splits
 the induced sub-graph); a 2 Mbp genome (one chain) and a dense random index; index states; argument handling and caps; the device form on a user
 stream interleaved with other queries on one handle; the largest component fed back through bft_gpu_subgraph."""

@@ -1,6 +1,6 @@
 """Pan-genome k-mer classes on the GPU (bft_gpu_kmers_by_count / _dev, bft_gpu_pangenome_stats / _dev, BFT.kmers_by_count, BFT.pangenome_stats): against
 ground truth computed in Python from the inserted k-mer strings and their genome sets; the product's extract() only gives the row order.  Every
-comparison is over all k-mers of the index.  Key widths W = 1..4; the classes core, dispensable, singleton and other ranges, empty ones included; packed
+comparison is over all k-mers of the index.  Key widths W = 1, 2 and 4 (KS has no three-word key, k = 65..96; tests/test_gpu_graph_edges.py runs W = 3 and the other key shapes); the classes core, dispensable, singleton and other ranges, empty ones included; packed
 k-mers, ASCII with its NULs and stride, rows; the statistics; hand-made indexes (one genome, disjoint genomes, a genome without k-mers, 300 genomes
 with 2-byte dictionary ids, more genomes than the dictionary pass keeps counters for in LDS, one colour set owning over 90 % of a few million rows,
 the empty index); index states; caps; the device forms on a user stream interleaved with other queries on one handle; a class fed back through

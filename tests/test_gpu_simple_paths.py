@@ -1,5 +1,5 @@
 """Simple paths on the GPU (bft_gpu_simple_paths / _dev, BFT.simple_paths): against ground truth computed in Python from the inserted k-mer
-strings and their genome sets (the product's extract only orders the paths by row), at key widths W = 1..4; hand-made graphs (a circular
+strings and their genome sets (the product's extract only orders the paths by row), at key widths W = 1, 2 and 4 (KS has no three-word key, k = 65..96; tests/test_gpu_graph_edges.py runs W = 3 and the other key shapes); hand-made graphs (a circular
 genome, a homopolymer self-loop, a lone k-mer, a k-mer with two successors); thresholds 0, 1, 2, N and N + 1; index states (compact_table,
 kmer_hash 0, pending insertions, merges, a .bft round trip) that all give the same paths; caps and NOSPACE; the device form on a user stream,
 interleaved with colour and prefix queries on one handle; the handle's answers unchanged afterwards."""

@@ -1,5 +1,5 @@
 """Sub-graphs on the GPU (bft_gpu_subgraph / _dev, BFT.subgraph): the stored subset of a shuffled batch with duplicates and absent mutants,
-against ground truth -- numpy / Python sets over the inserted k-mers, not the product's own extract -- at key widths W = 1..4; the same
+against ground truth -- numpy / Python sets over the inserted k-mers, not the product's own extract -- at key widths W = 1, 2 and 4 (KS has no three-word key, k = 65..96; tests/test_gpu_graph_edges.py runs W = 3 and the other key shapes); the same
 image as a fresh build of the subset; the k-mer hash against its host restatement; the colour-less form; source states (compact_table,
 kmer_hash 0, pending insertions, merges) left unchanged; empty and all-absent batches; a sub-graph that outlives its source, takes
 insertions, merges and .bft round trips; prefix matches fed to subgraph_dev on one stream; kernel timing."""
