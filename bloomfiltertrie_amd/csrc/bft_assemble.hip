@@ -1148,29 +1148,81 @@ __device__ __forceinline__ bool same_list(const uint32_t* __restrict__ seg_off, 
     return true;
 }
 
-// a new colour set starts where the (signature-sorted) list differs from its predecessor.  exact = 0: by the 64-bit signature and the
-// length alone (two gathers of a whole list per k-mer saved: 2.0 ms of config 3's 8); k_cs_verify then compares EVERY k-mer's list
-// with the dictionary entry it was given, and a mismatch -- two different lists with one signature -- sends the caller back here with
-// exact = 1: the lists themselves are compared.
-__global__ void k_cs_heads(const uint64_t* __restrict__ sig_s, const uint32_t* __restrict__ order, const uint32_t* __restrict__ seg_off,
-                           const uint32_t* __restrict__ pg, uint32_t nk, int exact, uint32_t* __restrict__ head, uint32_t* __restrict__ len) {
+// ---- the exact pass (k_cs_key2 .. k_cs_assign): only when k_cs_verify found two different lists with one signature, or a caller asks ----
+// The lists are sorted on (signature, second key, k-mer number) and equal lists found by comparing the lists themselves: never by a key.
+
+// second key of a list (one thread per list: this pass is no hot path).  how 0: a sum of terms mixed independently of bft_cs_sig.h's, so that
+// the lists of one signature fall apart by it; 1: bft_cs_sig.h's signature itself (the signatures are the weak hook's lengths); 2: the length
+// (weak hook 2: neither key tells lists apart, and k_cs_canon has to)
+__global__ void k_cs_key2(const uint32_t* __restrict__ seg_off, const uint32_t* __restrict__ pg, uint32_t nk, int how, uint64_t* __restrict__ key2) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nk; i += gridDim.x * blockDim.x) {
-        const uint32_t a = order[i];
-        uint32_t h = 1;
-        if (i > 0 && sig_s[i] == sig_s[i - 1]) {
-            const uint32_t b = order[i - 1];
-            if (exact ? same_list(seg_off, pg, a, b) : (seg_off[a + 1] - seg_off[a] == seg_off[b + 1] - seg_off[b])) h = 0;
-        }
-        head[i] = h;
-        len[i] = h ? seg_off[a + 1] - seg_off[a] : 0;
+        const uint32_t a = seg_off[i], b = seg_off[i + 1];
+        uint64_t sum = 0;
+        if (how == 0) for (uint32_t e = a; e < b; e++) sum += bft_mix64(((uint64_t)pg[e] + 1) * 0xD6E8FEB86659FD93ULL);
+        if (how == 1) for (uint32_t e = a; e < b; e++) sum += bft_cs_term(pg[e]);
+        key2[i] = how == 2 ? (uint64_t)(b - a) : how == 1 ? bft_cs_finish(sum, b - a, 0) : bft_mix64(sum + (uint64_t)(b - a) * 0xA24BAED4963EE407ULL);
     }
 }
 
-// tcol of every k-mer (position i of the signature order) and, for the first k-mer of every run of equal lists, the
+__global__ void k_cs_gather64(const uint64_t* __restrict__ src, const uint32_t* __restrict__ idx, uint32_t n, uint64_t* __restrict__ out) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) out[i] = src[idx[i]];
+}
+
+// a stretch of equal lists starts where the list differs from its predecessor in the sorted order: by either key or, the keys equal, by the
+// lists themselves
+__global__ void k_cs_heads(const uint64_t* __restrict__ sig_s, const uint64_t* __restrict__ key2_s, const uint32_t* __restrict__ order,
+                           const uint32_t* __restrict__ seg_off, const uint32_t* __restrict__ pg, uint32_t nk, uint32_t* __restrict__ head0) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nk; i += gridDim.x * blockDim.x)
+        head0[i] = (i > 0 && sig_s[i] == sig_s[i - 1] && key2_s[i] == key2_s[i - 1] && same_list(seg_off, pg, order[i], order[i - 1])) ? 0u : 1u;
+}
+
+// position of the r-th stretch's first list (r0_ex: exclusive sum of head0)
+__global__ void k_cs_headpos(const uint32_t* __restrict__ head0, const uint32_t* __restrict__ r0_ex, uint32_t nk, uint32_t* __restrict__ headpos) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nk; i += gridDim.x * blockDim.x)
+        if (head0[i]) headpos[r0_ex[i]] = i;
+}
+
+// Two different lists with BOTH keys equal may alternate -- A B A B is four stretches of two sets --: the first list of every stretch looks for
+// its list among the earlier stretches of the same two keys and takes the earliest one's place (canon: position of the list that stands for
+// the set; head: this list does).  With the second key independent of the first such a run has one stretch; under weak hook 2 it has many,
+// and the test cases are sized for that.
+__global__ void k_cs_canon(const uint64_t* __restrict__ sig_s, const uint64_t* __restrict__ key2_s, const uint32_t* __restrict__ order,
+                           const uint32_t* __restrict__ head0, const uint32_t* __restrict__ r0_ex, const uint32_t* __restrict__ headpos,
+                           const uint32_t* __restrict__ seg_off, const uint32_t* __restrict__ pg, uint32_t nk, uint32_t* __restrict__ canon,
+                           uint32_t* __restrict__ head, uint32_t* __restrict__ len) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nk; i += gridDim.x * blockDim.x) {
+        uint32_t h = 0, l = 0;
+        if (head0[i]) {
+            const uint32_t a = order[i];
+            const uint64_t s1 = sig_s[i], s2 = key2_s[i];
+            uint32_t m = i;
+            for (uint32_t r = r0_ex[i]; r-- > 0;) {
+                const uint32_t j = headpos[r];
+                if (sig_s[j] != s1 || key2_s[j] != s2) break;
+                if (same_list(seg_off, pg, a, order[j])) m = j;
+            }
+            canon[i] = m;
+            h = m == i;
+            l = h ? seg_off[a + 1] - seg_off[a] : 0;
+        }
+        head[i] = h;
+        len[i] = l;
+    }
+}
+
+// the other lists of a stretch: what its first list found
+__global__ void k_cs_spread(const uint32_t* __restrict__ head0, const uint32_t* __restrict__ r0_ex, const uint32_t* __restrict__ headpos, uint32_t nk,
+                            uint32_t* __restrict__ canon) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nk; i += gridDim.x * blockDim.x)
+        if (!head0[i]) canon[i] = canon[headpos[r0_ex[i] - 1]];  // (position 0 is always a first list: r0_ex[i] >= 1 here)
+}
+
+// tcol of every k-mer (position i of the sorted order; csid_ex: exclusive sum of head) and, for the list that stands for a set, the
 // dictionary entry: the lanes of a wavefront copy that list together, 64 ids at a time
-__global__ __launch_bounds__(ABLK) void k_cs_assign(const uint32_t* __restrict__ order, const uint32_t* __restrict__ head, const uint32_t* __restrict__ csid_ex,
-                                                    const uint32_t* __restrict__ off_ex, const uint32_t* __restrict__ seg_off, const uint32_t* __restrict__ pg,
-                                                    uint32_t nk, uint32_t* __restrict__ tcol, uint32_t* __restrict__ cs_off, uint32_t* __restrict__ cs_ids) {
+__global__ __launch_bounds__(ABLK) void k_cs_assign(const uint32_t* __restrict__ order, const uint32_t* __restrict__ head, const uint32_t* __restrict__ canon,
+                                                    const uint32_t* __restrict__ csid_ex, const uint32_t* __restrict__ off_ex, const uint32_t* __restrict__ seg_off,
+                                                    const uint32_t* __restrict__ pg, uint32_t nk, uint32_t* __restrict__ tcol, uint32_t* __restrict__ cs_off,
+                                                    uint32_t* __restrict__ cs_ids) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t nblk = (nk + ABLK - 1) / ABLK;
     for (uint32_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
@@ -1179,7 +1231,7 @@ __global__ __launch_bounds__(ABLK) void k_cs_assign(const uint32_t* __restrict__
         if (i < nk) {
             const uint32_t a = order[i];
             hd = head[i];
-            const uint32_t cs = csid_ex[i] + hd - 1;
+            const uint32_t cs = csid_ex[canon[i]];  // (canon[i] is a position whose head is 1: the sets in front of it number it)
             tcol[a] = cs;
             if (hd) {
                 src = seg_off[a];
@@ -1375,9 +1427,9 @@ __global__ void k_cs_hash_tcol(const uint32_t* __restrict__ slot_of, const CsSlo
 
 }  // namespace
 
-static bool g_weak_signature = false;
-static unsigned long long g_exact_passes = 0;
-void bft_test_weak_signature(bool on) { g_weak_signature = on; }
+static int g_weak_signature = 0;
+static unsigned long long g_exact_passes = 0, g_hash_attempts = 0;
+void bft_test_weak_signature(int how) { g_weak_signature = how; }
 unsigned long long bft_test_exact_passes(void) { return g_exact_passes; }
 
 int bft_assemble_gpu(const uint64_t* d_tk, uint64_t n, int k, const uint32_t* d_hashmod, hipStream_t s, BftDeviceIndex& out, const BftAssembleHook* hook) {
@@ -1432,8 +1484,11 @@ int bft_flatten_gpu(const BftCC* d_ccs, uint64_t n_ccs, const uint64_t* d_f2w, c
 // Interning of the colour sets (sorted genome-id list of each distinct k-mer, CSR seg_off/pg) into a dictionary: a 64-bit signature
 // per list, equal signatures found through a hash table (k_cs_hash_*), sets numbered in the order of their signatures, then a
 // verification pass that compares EVERY k-mer's list with the dictionary entry it was given.  A mismatch -- two different lists with
-// one signature -- sends the build through the sorted path, where runs of equal lists are found by comparing the lists themselves.
-// Two different sets can therefore never share an id, and two equal sets always do.
+// one signature -- sends the build through the exact pass: the lists sorted on (signature, a second key, k-mer number), equal lists found by
+// comparing the lists themselves, with their predecessor and, where both keys tie, with the earlier lists of the tie.
+// Two different sets can therefore never share an id, and two equal sets always do, on either path (tests/test_gpu_intern_edges.py).
+// Numbering: the sets in the order of (signature, second key, first k-mer that holds the set).  The hash path stands only when no two sets share
+// a signature, where that is the order of the signatures alone; the same lists take the same path, so an image is a function of its lists.
 int bft_intern_colors_gpu(const uint32_t* d_seg_off, const uint32_t* d_pg, uint64_t nk, uint64_t np, hipStream_t s, DevBuf& d_tcol,
                           DevBuf& d_cs_off, DevBuf& d_cs_ids, uint64_t& n_sets, uint64_t& n_ids, uint64_t distinct_hint, BftInternTail* tail, bool exact) {
     n_sets = 0;
@@ -1468,6 +1523,7 @@ int bft_intern_colors_gpu(const uint32_t* d_seg_off, const uint32_t* d_pg, uint6
             if (attempt) {
                 while (n_slots < 2 * nk) n_slots <<= 1;
             }
+            g_hash_attempts++;
             CK(tab.alloc_zero(n_slots * sizeof(CsSlot), s));
             HIPCK(hipMemsetAsync(cnt.p, 0, 12, s));
             hipLaunchKernelGGL(k_cs_hash_insert, grid, block, 0, s, sig.as<uint64_t>(), (uint32_t)nk, tab.as<CsSlot>(), (uint32_t)(n_slots - 1), slot_of.as<uint32_t>(),
@@ -1534,39 +1590,107 @@ int bft_intern_colors_gpu(const uint32_t* d_seg_off, const uint32_t* d_pg, uint6
     }
     if (done) return 0;
 
-    // ---- by a sort of every k-mer's signature: equal lists next to each other, runs found by comparison ----
-    DevBuf sig_s, order, head, len, csid, off, tmp;
+    // ---- the exact pass: every k-mer's list sorted on (signature, second key, k-mer number), equal lists found by comparing the lists ----
+    // Both sorts are stable and over all 64 bits, the second key's first: the distinct sets end up numbered by (signature, second key, first
+    // k-mer that holds the set).  Where no two sets share a signature that is the order of the signatures, the hash path's numbering; where
+    // two do, k_cs_verify has sent every build of these lists here, so the numbering is still a function of the lists alone.
+    g_exact_passes++;
+    DevBuf key2, key2_s, ord1, sig_g, sig_s, order, head0, r0, headpos, canon, head, len, csid, off;
+    CK(key2.alloc(nk * 8));
+    CK(key2_s.alloc(nk * 8));
+    CK(ord1.alloc(nk * 4));
+    CK(sig_g.alloc(nk * 8));
     CK(sig_s.alloc(nk * 8));
     CK(order.alloc(nk * 4));
+    CK(head0.alloc(nk * 4));
+    CK(r0.alloc(nk * 4));
+    CK(headpos.alloc(nk * 4));
+    CK(canon.alloc(nk * 4));
     CK(head.alloc(nk * 4));
     CK(len.alloc(nk * 4));
     CK(csid.alloc(nk * 4));
     CK(off.alloc(nk * 4));
-    // Equal lists only have to end up next to each other: the low 48 bits of the signature order them (6 radix passes instead
-    // of 8).  Two different lists that agree on those bits could at worst split a run of equal lists, i.e. cost a duplicate
-    // dictionary entry (expected once in ~10^14 / n_sets^2 builds); k_cs_heads still compares whole signatures and lists.
-    CK((bft_rs::sort_pairs<uint64_t, uint32_t, bft_rs::SHAPE_LIGHT>(sig.as<uint64_t>(), iota.as<uint32_t>(), nk, sig_s.as<uint64_t>(), order.as<uint32_t>(), 0, 48, s)));
-    for (int exact = 1; exact < 2; exact++) {
-        g_exact_passes++;
-        hipLaunchKernelGGL(k_cs_heads, grid, block, 0, s, sig_s.as<uint64_t>(), order.as<uint32_t>(), d_seg_off, d_pg, (uint32_t)nk, exact, head.as<uint32_t>(), len.as<uint32_t>());
-        CK(scan.run(head.as<uint32_t>(), csid.as<uint32_t>(), nk, &n_sets));
-        CK(scan.run(len.as<uint32_t>(), off.as<uint32_t>(), nk, &n_ids));
-        CK(d_cs_off.alloc((n_sets + 1) * 4));
-        CK(d_cs_ids.alloc(n_ids * 4));
-        {
-            const uint32_t t32 = (uint32_t)n_ids;
-            HIPCK(hipMemcpyAsync(d_cs_off.as<uint32_t>() + n_sets, &t32, 4, hipMemcpyHostToDevice, s));
-        }
-        hipLaunchKernelGGL(k_cs_assign, grid, block, 0, s, order.as<uint32_t>(), head.as<uint32_t>(), csid.as<uint32_t>(), off.as<uint32_t>(), d_seg_off, d_pg,
-                           (uint32_t)nk, d_tcol.as<uint32_t>(), d_cs_off.as<uint32_t>(), d_cs_ids.as<uint32_t>());
-        HIPCK(hipMemsetAsync(bad.p, 0, 4, s));
-        hipLaunchKernelGGL(k_cs_verify, grid, block, 0, s, d_tcol.as<uint32_t>(), d_cs_off.as<uint32_t>(), d_cs_ids.as<uint32_t>(), d_seg_off, d_pg, (uint32_t)nk,
-                           bad.as<uint32_t>());
-        HIPCK(hipMemcpyAsync(&nbad, bad.p, 4, hipMemcpyDeviceToHost, s));
-        HIPCK(hipGetLastError());
-        HIPCK(hipStreamSynchronize(s));
+    const uint32_t n32 = (uint32_t)nk;
+    hipLaunchKernelGGL(k_cs_key2, grid, block, 0, s, d_seg_off, d_pg, n32, g_weak_signature, key2.as<uint64_t>());
+    CK((bft_rs::sort_pairs<uint64_t, uint32_t, bft_rs::SHAPE_LIGHT>(key2.as<uint64_t>(), iota.as<uint32_t>(), nk, key2_s.as<uint64_t>(), ord1.as<uint32_t>(), 0, 64, s)));
+    hipLaunchKernelGGL(k_cs_gather64, grid, block, 0, s, sig.as<uint64_t>(), ord1.as<uint32_t>(), n32, sig_g.as<uint64_t>());
+    CK((bft_rs::sort_pairs<uint64_t, uint32_t, bft_rs::SHAPE_LIGHT>(sig_g.as<uint64_t>(), ord1.as<uint32_t>(), nk, sig_s.as<uint64_t>(), order.as<uint32_t>(), 0, 64, s)));
+    hipLaunchKernelGGL(k_cs_gather64, grid, block, 0, s, key2.as<uint64_t>(), order.as<uint32_t>(), n32, key2_s.as<uint64_t>());  // (the second key in the final order)
+    hipLaunchKernelGGL(k_cs_heads, grid, block, 0, s, sig_s.as<uint64_t>(), key2_s.as<uint64_t>(), order.as<uint32_t>(), d_seg_off, d_pg, n32, head0.as<uint32_t>());
+    CK(scan.run(head0.as<uint32_t>(), r0.as<uint32_t>(), nk, nullptr));
+    hipLaunchKernelGGL(k_cs_headpos, grid, block, 0, s, head0.as<uint32_t>(), r0.as<uint32_t>(), n32, headpos.as<uint32_t>());
+    hipLaunchKernelGGL(k_cs_canon, grid, block, 0, s, sig_s.as<uint64_t>(), key2_s.as<uint64_t>(), order.as<uint32_t>(), head0.as<uint32_t>(), r0.as<uint32_t>(),
+                       headpos.as<uint32_t>(), d_seg_off, d_pg, n32, canon.as<uint32_t>(), head.as<uint32_t>(), len.as<uint32_t>());
+    hipLaunchKernelGGL(k_cs_spread, grid, block, 0, s, head0.as<uint32_t>(), r0.as<uint32_t>(), headpos.as<uint32_t>(), n32, canon.as<uint32_t>());
+    CK(scan.run(head.as<uint32_t>(), csid.as<uint32_t>(), nk, &n_sets));
+    CK(scan.run(len.as<uint32_t>(), off.as<uint32_t>(), nk, &n_ids));
+    CK(d_cs_off.alloc((n_sets + 1) * 4));
+    CK(d_cs_ids.alloc(n_ids * 4));
+    {
+        const uint32_t t32 = (uint32_t)n_ids;
+        HIPCK(hipMemcpyAsync(d_cs_off.as<uint32_t>() + n_sets, &t32, 4, hipMemcpyHostToDevice, s));
     }
+    hipLaunchKernelGGL(k_cs_assign, grid, block, 0, s, order.as<uint32_t>(), head.as<uint32_t>(), canon.as<uint32_t>(), csid.as<uint32_t>(), off.as<uint32_t>(), d_seg_off,
+                       d_pg, n32, d_tcol.as<uint32_t>(), d_cs_off.as<uint32_t>(), d_cs_ids.as<uint32_t>());
+    HIPCK(hipMemsetAsync(bad.p, 0, 4, s));
+    hipLaunchKernelGGL(k_cs_verify, grid, block, 0, s, d_tcol.as<uint32_t>(), d_cs_off.as<uint32_t>(), d_cs_ids.as<uint32_t>(), d_seg_off, d_pg, n32, bad.as<uint32_t>());
+    HIPCK(hipMemcpyAsync(&nbad, bad.p, 4, hipMemcpyDeviceToHost, s));
+    HIPCK(hipGetLastError());
+    HIPCK(hipStreamSynchronize(s));
     if (nbad) return bft_fail(BFT_GPU_E_LIMIT, "colour-set interning self-check failed");
     (void)np;
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// test hook (tests/test_gpu_intern_edges.py; not part of include/bft_gpu.h): the interning on the caller's CSR lists (device arrays: d_seg_off
+// [nk + 1], d_ids [np], ids ascending inside a list).  mode 0: the hash path, everything on the stream; 1: the tail deferred to a side stream
+// of the hook's own with narrow_w 1 / 2 / 4, its verdict waited for and, on collisions, the exact call made -- as bft_commit_image does; 2: exact
+// at once.  Out: tcol [nk], cs_off [n_sets + 1], cs_ids [n_ids]; d_narrow (mode 1, narrow_w < 4, no collision: what the tail narrowed, n_ids *
+// narrow_w bytes; untouched otherwise).  counts: {n_sets, n_ids, exact passes this call took, lists the tail reported as collided, hash tables
+// tried}.  A capacity (in entries) too small: nothing is copied, counts are set, BFT_GPU_E_NOSPACE.
+// ------------------------------------------------------------------------------------------------
+extern "C" int bft_gpu_test_intern(const uint32_t* d_seg_off, const uint32_t* d_ids, uint64_t nk, uint64_t np, int mode, uint32_t narrow_w, uint64_t distinct_hint,
+                                   uint32_t* d_tcol, uint32_t* d_cs_off, uint64_t cs_off_cap, uint32_t* d_cs_ids, uint64_t cs_ids_cap, void* d_narrow, uint64_t* counts,
+                                   void* hip_stream) {
+    if (!d_seg_off || !counts || (nk && (!d_tcol || !d_cs_off)) || (np && (!d_ids || !d_cs_ids))) return bft_fail(BFT_GPU_E_ARG, "NULL argument");
+    if (mode < 0 || mode > 2 || (narrow_w != 1 && narrow_w != 2 && narrow_w != 4)) return bft_fail(BFT_GPU_E_ARG, "bad mode or id width");
+    if (nk >= 0x7FFFFFFFull || np > 0xFFFFFFFFull) return bft_fail(BFT_GPU_E_LIMIT, "too many lists or ids");
+    hipStream_t s = (hipStream_t)hip_stream;
+    int dev = 0;
+    HIPCK(hipGetDevice(&dev));
+    bft_pool_set_stream(dev, s);
+    struct Side {  // (declared before the tail: the tail's destructor still synchronises with it)
+        hipStream_t st = nullptr;
+        ~Side() { if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); } }
+    } side;
+    const unsigned long long exact0 = g_exact_passes, attempts0 = g_hash_attempts;
+    DevBuf tcol, cs_off, cs_ids;
+    uint64_t n_sets = 0, n_ids = 0;
+    uint32_t collisions = 0;
+    bool narrowed = false;
+    BftInternTail tail;
+    if (mode == 1) {
+        HIPCK(hipStreamCreateWithFlags(&side.st, hipStreamNonBlocking));
+        tail.side = side.st;
+        tail.narrow_w = narrow_w;
+        CK(bft_intern_colors_gpu(d_seg_off, d_ids, nk, np, s, tcol, cs_off, cs_ids, n_sets, n_ids, distinct_hint, &tail));
+        CK(tail.wait(&collisions));
+        if (collisions) CK(bft_intern_colors_gpu(d_seg_off, d_ids, nk, np, s, tcol, cs_off, cs_ids, n_sets, n_ids, 0, nullptr, true));
+        else narrowed = narrow_w < 4 && tail.narrow.p && n_ids;
+    } else {
+        CK(bft_intern_colors_gpu(d_seg_off, d_ids, nk, np, s, tcol, cs_off, cs_ids, n_sets, n_ids, distinct_hint, nullptr, mode == 2));
+    }
+    counts[0] = n_sets;
+    counts[1] = n_ids;
+    counts[2] = g_exact_passes - exact0;
+    counts[3] = collisions;
+    counts[4] = g_hash_attempts - attempts0;
+    if (n_sets + 1 > cs_off_cap || n_ids > cs_ids_cap) return bft_fail(BFT_GPU_E_NOSPACE, "dictionary does not fit the caller's arrays");
+    if (nk) HIPCK(hipMemcpyAsync(d_tcol, tcol.p, nk * 4, hipMemcpyDeviceToDevice, s));
+    if (nk) HIPCK(hipMemcpyAsync(d_cs_off, cs_off.p, (n_sets + 1) * 4, hipMemcpyDeviceToDevice, s));
+    if (n_ids) HIPCK(hipMemcpyAsync(d_cs_ids, cs_ids.p, n_ids * 4, hipMemcpyDeviceToDevice, s));
+    if (narrowed && d_narrow) HIPCK(hipMemcpyAsync(d_narrow, tail.narrow.p, n_ids * narrow_w, hipMemcpyDeviceToDevice, s));
+    HIPCK(hipStreamSynchronize(s));
+    return BFT_GPU_OK;
 }

@@ -139,7 +139,7 @@ int bft_assemble_gpu(const uint64_t* d_tk, uint64_t n, int k, const uint32_t* d_
 struct BftCC;
 int bft_flatten_gpu(const BftCC* d_ccs, uint64_t n_ccs, const uint64_t* d_f2w, const uint64_t* d_clus, const uint64_t* d_child, uint32_t flat_min,
                     hipStream_t s, DevBuf& ccx, DevBuf& f18, DevBuf& fent, uint64_t& n_f18, uint64_t& n_fent);
-void bft_test_weak_signature(bool on);            // test hook: every list's signature = its length (collisions galore)
+void bft_test_weak_signature(int how);            // test hook: 1 every list's signature = its length (collisions galore); 2 the exact pass's second key as well
 unsigned long long bft_test_exact_passes(void);   // how many times the interning had to fall back to comparing the lists
 // The interning's tail -- the dictionary entries copied out of their representatives' lists, then EVERY k-mer's list compared with the entry it was
 // given -- is a third of its time (1.2 of 3.4 ms on config 3) and nothing of the build needs its result before the commit: with `side` set it is

@@ -1772,7 +1772,8 @@ extern "C" int bft_gpu_set_option(bft_gpu* h, const char* name, int64_t value) {
         if (value > 2) return fail(BFT_GPU_E_ARG, "test_front_rank_mode must be 0, 1 or 2");
         bft_test_front_rank_mode((int)value);
     } else if (nm == "test_weak_signature") {  // test hook (tests/test_gpu_build.py): colour-set signatures that collide, see bft_intern_colors_gpu
-        bft_test_weak_signature(value != 0);
+        if (value < 0 || value > 2) return fail(BFT_GPU_E_ARG, "test_weak_signature must be 0, 1 or 2");  // (2: the exact pass's second key is the length too)
+        bft_test_weak_signature((int)value);
     } else if (nm == "inject_build_failure") {  // test hook (tests/test_gpu_build.py): exercises the all-or-nothing build
         h->inject_build_failure = value != 0;
     } else if (nm == "timing") {
