@@ -206,6 +206,7 @@ int bft_count_pairs(const uint32_t* d_tcol, uint64_t n, const uint32_t* d_cs_off
 struct BftPairRun { DevBuf tk, seg_off, ids; uint64_t nk = 0, np = 0; };
 uint32_t bft_front_bucket_capacity(void);
 void bft_test_front_rank_mode(int mode);   // test hook: k_bucket_sort's mode (0 atomics + check, 1 ballots only, 2 the check always fails)
+void bft_test_front_wave_cap(uint32_t cap);  // test hook: the largest bucket of the wavefront kernel (0 by rule -- bft_front_plan.h --, 512, 1024)
 // d_vals (vw bytes per id): d_c holds whole T-form k-mers grouped by the bits from split_bit - gb up, the ids beside them
 int bft_front_buckets(uint64_t* d_c, uint64_t n, const uint32_t* d_boff, uint32_t nb, uint32_t gb, uint32_t split_bit, hipStream_t s, BftPairRun& run,
                       const uint32_t* d_max_bucket, uint32_t* max_bucket, bool* done, uint32_t* n_redone, const void* d_vals = nullptr, uint32_t vw = 0);

@@ -26,11 +26,9 @@
 #include "bft_dev.h"
 #include "bft_scan.h"
 #include "bft_sort.h"
+#include <mutex>
+#include "bft_front_plan.h"             // FB_BLOCK, FB_WAVES, FB_EMAX, FB_CAP, FB2_*: the sizes the selection rules share with the kernels
 
-#define FB_BLOCK 256
-#define FB_WAVES (FB_BLOCK / 64)
-#define FB_EMAX 16                      // composites per thread
-#define FB_CAP (FB_BLOCK * FB_EMAX)     // largest bucket sorted in LDS (4096 composites = 32 KB)
 #define FB_DBITS 9                      // digit width: four passes over the 36 bits a k = 27 bucket sorts on, five over k = 31's 44 (8-bit digits: five
                                         // and six; 3.7 -> 3.0 ms and 4.3 -> 3.8 ms on config 3 -- the ranks come from LDS atomics, whose cost does
                                         // not grow with the digit as the ballots' does; wider digits cost LDS, i.e. workgroups per CU)
@@ -590,12 +588,12 @@ __device__ __forceinline__ void radix_passes2(uint64_t (&khi)[EMAX], uint64_t (&
 // the non-empty buckets by size class (lists[c * nb ..], n_lists[c]): up to 64 items (class 5: k_bucket2_tiny), up to 512 / 1024 / 2048 -- a wavefront each, 8 / 16 / 32 items per lane --,
 // up to 4096 / 8192 -- a workgroup each --, so that the sort kernels walk real buckets only (those of a pan-genome are a few per cent of the 2^18 root
 // prefixes); the empty ones get their zero counts here
-#define FB2_CLASSES 6
+// (the classes are bft_front2_class's, bft_front_plan.h: the launcher's rules and this kernel read one definition)
 __global__ void k_bucket2_lists(const uint32_t* __restrict__ boff, uint32_t nb, uint32_t* __restrict__ lists, uint32_t* __restrict__ n_lists, uint64_t* __restrict__ counts) {
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63u;
     const uint32_t n = b < nb ? boff[b + 1] - boff[b] : 0u;
     if (b < nb && n == 0) counts[b] = 0;
-    const int cls = n == 0 ? -1 : n <= 64u ? 5 : n <= 512u ? 0 : n <= 1024u ? 1 : n <= 2048u ? 2 : n <= 4096u ? 3 : 4;
+    const int cls = bft_front2_class(n);
     __shared__ uint32_t s_cnt[FB2_CLASSES], s_base[FB2_CLASSES];
     if (threadIdx.x < FB2_CLASSES) s_cnt[threadIdx.x] = 0;
     __syncthreads();
@@ -1020,6 +1018,53 @@ __global__ __launch_bounds__(FB_BLOCK) void k_bucket2_emit(const uint64_t* __res
 uint32_t bft_front_bucket_capacity(void) { return FB_CAP; }
 static int g_rank_mode = 0;                 // k_bucket_sort's mode ("test_front_rank_mode")
 void bft_test_front_rank_mode(int mode) { g_rank_mode = mode; }
+static uint32_t g_wave_cap = 0;             // bft_front_wave_cap's `forced` ("test_front_wave_cap"): 0 by rule, 512 or 1024
+void bft_test_front_wave_cap(uint32_t cap) { g_wave_cap = cap; }
+
+// What the last front-end call of this process launched, for bft_gpu_debug_front_last: every field but the largest bucket and its size class is
+// written where the kernel is launched (FrontLog), not taken from the plan.  {words, the largest bucket, declined, then one word: the largest bucket of
+// the wavefront kernel launched, its composites per lane, composites per thread of the workgroup kernel launched (0: none), 0, 0; two words: PACK of the
+// wavefront kernels launched, the size class of the largest bucket (bft_front2_class, the function k_bucket2_lists sorts the buckets by), items per
+// lane / thread of the kernel launched for that class (0: none), class 3 launched, class 4 launched}.  Reading it clears it.
+struct FrontLog {
+    uint32_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t items[FB2_CLASSES] = {0, 0, 0, 0, 0, 0};  // two words: items per lane / thread of the kernel launched on each class's list
+};
+static std::mutex g_last_mu;  // (handles may build on several threads)
+static uint32_t g_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+static void front_log_commit(const FrontLog& l) {
+    std::lock_guard<std::mutex> lock(g_last_mu);
+    std::copy(l.v, l.v + 8, g_last);
+}
+extern "C" int bft_gpu_debug_front_last(uint32_t out[8]) {
+    if (!out) return bft_fail(BFT_GPU_E_ARG, "front last: NULL argument");
+    std::lock_guard<std::mutex> lock(g_last_mu);
+    for (int i = 0; i < 8; i++) { out[i] = g_last[i]; g_last[i] = 0; }
+    return BFT_GPU_OK;
+}
+
+// The selection rules (bft_front_plan.h) without a handle or a device.  words 1: out = {wave_cap, composites per lane of the wavefront kernel,
+// composites per thread of the workgroup kernel (0: none is launched), declines, FB_CAP, owner of a bucket of `bucket` composites (0 nobody: empty
+// or the call declines, 1 the wavefront kernel, 2 the workgroup kernel), 0, 0}.  words 2: out = {PACK, class 3 launched, class 4 launched, declines,
+// FB2_CAP, size class of a bucket of `bucket` items (0xFFFFFFFF: empty), items per lane / thread of that class's kernel (0: empty), owner (0 nobody,
+// 1 k_bucket2_sort_wave, 2 k_bucket2_sort, 3 k_bucket2_tiny)}.
+extern "C" int bft_gpu_debug_front_plan(int words, uint64_t n, uint32_t nb, uint32_t max_bucket, uint32_t max_gid, uint32_t wave_cap, uint32_t bucket, uint32_t out[8]) {
+    if (!out || (words != 1 && words != 2) || (wave_cap != 0 && wave_cap != 512 && wave_cap != 1024) || bucket > max_bucket) return bft_fail(BFT_GPU_E_ARG, "front plan: argument");
+    for (int i = 0; i < 8; i++) out[i] = 0;
+    if (words == 1) {
+        const BftFrontPlan p = bft_front_plan(n, nb, max_bucket, wave_cap);
+        out[0] = p.wave_cap; out[1] = p.wave_ew; out[2] = p.wg_e; out[3] = p.declines; out[4] = FB_CAP;
+        out[5] = (bucket == 0 || p.declines) ? 0u : bucket <= p.wave_cap ? 1u : 2u;
+    } else {
+        const BftFront2Plan p = bft_front2_plan(max_bucket, max_gid);
+        const int cls = bft_front2_class(bucket);
+        out[0] = p.pack; out[1] = p.class3; out[2] = p.class4; out[3] = p.declines; out[4] = FB2_CAP;
+        out[5] = (uint32_t)cls;
+        out[6] = cls < 0 ? 0u : bft_front2_class_items(cls);
+        out[7] = (cls < 0 || p.declines) ? 0u : cls == FB2_TINY ? 3u : cls <= 2 ? 1u : 2u;
+    }
+    return BFT_GPU_OK;
+}
 
 int bft_front_buckets(uint64_t* d_c, uint64_t n, const uint32_t* d_boff, uint32_t nb, uint32_t gb, uint32_t split_bit, hipStream_t s, BftPairRun& run,
                       const uint32_t* d_max_bucket, uint32_t* max_bucket, bool* done, uint32_t* n_redone, const void* d_vals, uint32_t vw) {
@@ -1041,22 +1086,40 @@ int bft_front_buckets(uint64_t* d_c, uint64_t n, const uint32_t* d_boff, uint32_
     hipLaunchKernelGGL(k_front_publish, dim3(1), dim3(1), 0, s, (const uint64_t*)nullptr, d_max_bucket, pin.p, pin.p + PIN_SLOTS, ticket);
     // the small buckets a wavefront each, the others a workgroup each (one after the other: on two streams the two kernels --
     // both latency-bound, different LDS footprints -- got in each other's way: 8.6 ms instead of 2.0 + 0.8)
-    const uint32_t wave_cap = n / std::max(nb, 1u) <= 192u ? 512u : 1024u;
+    const uint32_t wave_cap = bft_front_wave_cap(n, nb, g_wave_cap);
     const dim3 wgrid(std::min<uint32_t>((nb + FB_WAVES - 1) / FB_WAVES, 256u * 16u));
-    if (wave_cap == 512u) hipLaunchKernelGGL(k_bucket_sort_wave<8>, wgrid, block, 0, s, d_c, d_boff, nb, gb, split_bit, counts.as<uint64_t>(), d_vals, vw, g_rank_mode, redone.as<uint32_t>(), redo.as<uint32_t>());
-    else hipLaunchKernelGGL(k_bucket_sort_wave<16>, wgrid, block, 0, s, d_c, d_boff, nb, gb, split_bit, counts.as<uint64_t>(), d_vals, vw, g_rank_mode, redone.as<uint32_t>(), redo.as<uint32_t>());
+    FrontLog log;
+    log.v[0] = 1;
+    if (wave_cap == 512u) {
+        hipLaunchKernelGGL(k_bucket_sort_wave<8>, wgrid, block, 0, s, d_c, d_boff, nb, gb, split_bit, counts.as<uint64_t>(), d_vals, vw, g_rank_mode, redone.as<uint32_t>(), redo.as<uint32_t>());
+        log.v[3] = 64u * 8u; log.v[4] = 8;
+    } else {
+        hipLaunchKernelGGL(k_bucket_sort_wave<16>, wgrid, block, 0, s, d_c, d_boff, nb, gb, split_bit, counts.as<uint64_t>(), d_vals, vw, g_rank_mode, redone.as<uint32_t>(), redo.as<uint32_t>());
+        log.v[3] = 64u * 16u; log.v[4] = 16;
+    }
     CK(bft_pin_wait_for(pin, s, ticket));
     const uint32_t mx = (uint32_t)pin.p[0];
     *max_bucket = mx;
     bft_trace_mark("root-prefix split done (largest bucket known)");
-    if (mx > FB_CAP) return 0;
-#define FB_LAUNCH(E) hipLaunchKernelGGL((k_bucket_sort<E, false>), grid, block, 0, s, d_c, d_boff, nb, gb, split_bit, counts.as<uint64_t>(), d_vals, vw, g_rank_mode, redone.as<uint32_t>(), redo.as<uint32_t>(), wave_cap)
-    if (mx <= wave_cap) {}
-    else if (mx <= 256u * 6u) FB_LAUNCH(6);
-    else if (mx <= 256u * 9u) FB_LAUNCH(9);
-    else if (mx <= 256u * 12u) FB_LAUNCH(12);
-    else FB_LAUNCH(16);
+    const BftFrontPlan plan = bft_front_plan(n, nb, mx, g_wave_cap);  // (plan.wave_cap == wave_cap: the same rule on the same arguments)
+    log.v[1] = mx;
+    if (plan.declines) {
+        log.v[2] = 1;
+        front_log_commit(log);
+        return 0;
+    }
+#define FB_LAUNCH(E)                                                                                                                                                                \
+    do {                                                                                                                                                                           \
+        hipLaunchKernelGGL((k_bucket_sort<E, false>), grid, block, 0, s, d_c, d_boff, nb, gb, split_bit, counts.as<uint64_t>(), d_vals, vw, g_rank_mode, redone.as<uint32_t>(), \
+                           redo.as<uint32_t>(), wave_cap);                                                                                                                         \
+        log.v[5] = E;                                                                                                                                                              \
+    } while (0)
+    if (plan.wg_e == 6) FB_LAUNCH(6);
+    else if (plan.wg_e == 9) FB_LAUNCH(9);
+    else if (plan.wg_e == 12) FB_LAUNCH(12);
+    else if (plan.wg_e == 16) FB_LAUNCH(16);
 #undef FB_LAUNCH
+    front_log_commit(log);
     // the fallback launch: the buckets whose order check failed (none, on every run so far), or all of them ("test_front_rank_mode" 1)
     hipLaunchKernelGGL((k_bucket_sort<FB_EMAX, true>), dim3(g_rank_mode ? grid.x : 64u), block, 0, s, d_c, d_boff, nb, gb, split_bit, counts.as<uint64_t>(), d_vals, vw, g_rank_mode,
                        redone.as<uint32_t>(), redo.as<uint32_t>(), 0u);
@@ -1082,13 +1145,13 @@ int bft_front_buckets(uint64_t* d_c, uint64_t n, const uint32_t* d_boff, uint32_
     return 0;
 }
 
-uint32_t bft_front2_bucket_capacity(void) { return FB_BLOCK * 32; }
+uint32_t bft_front2_bucket_capacity(void) { return FB2_CAP; }
 
 // the two-word front end behind the split (items grouped by the top 18 bits of hk): see k_bucket2_sort
 int bft_front2_buckets(uint64_t* d_hk, void* d_items, uint64_t n, const uint32_t* d_boff, uint32_t nb, int k, hipStream_t s, BftPairRun& run,
                        const uint32_t* d_max_bucket, uint32_t* max_bucket, bool* done, uint32_t* n_redone, uint32_t max_gid) {
     *done = false;
-    const bool pack = max_gid < (1u << 18);  // (ids that fit the 18 free bits above hk's 46: k_bucket2_sort_wave)
+    const bool pack = bft_front2_pack(max_gid);  // (ids that fit the 18 free bits above hk's 46: k_bucket2_sort_wave)
     BftItem2* d_it = (BftItem2*)d_items;
     PinBlock pin;  // [0] the largest bucket, [1] k-mers << 32 | pairs, [2] buckets that failed, [3] buckets sorted again
     if (!pin.p) return bft_fail(BFT_GPU_E_HIP, "hipHostMalloc (front end counts)");
@@ -1109,24 +1172,46 @@ int bft_front2_buckets(uint64_t* d_hk, void* d_items, uint64_t n, const uint32_t
     const uint32_t sh = (uint32_t)(2 * k - 64);
 #define FB2_WAVE(EW_, CLS, GRID)                                                                                                                                                \
     do {                                                                                                                                                                       \
-        if (pack) hipLaunchKernelGGL((k_bucket2_sort_wave<EW_, true>), dim3(GRID), block, 0, s, d_hk, d_it, d_boff, lists.as<uint32_t>() + (size_t)CLS * nb, n_lists.as<uint32_t>() + CLS, sh, \
-                                     counts.as<uint64_t>(), g_rank_mode, redone.as<uint32_t>(), redo.as<uint32_t>());                                                          \
-        else hipLaunchKernelGGL((k_bucket2_sort_wave<EW_, false>), dim3(GRID), block, 0, s, d_hk, d_it, d_boff, lists.as<uint32_t>() + (size_t)CLS * nb, n_lists.as<uint32_t>() + CLS, sh,   \
-                                counts.as<uint64_t>(), g_rank_mode, redone.as<uint32_t>(), redo.as<uint32_t>());                                                               \
+        if (pack) {                                                                                                                                                            \
+            hipLaunchKernelGGL((k_bucket2_sort_wave<EW_, true>), dim3(GRID), block, 0, s, d_hk, d_it, d_boff, lists.as<uint32_t>() + (size_t)CLS * nb, n_lists.as<uint32_t>() + CLS, sh, \
+                               counts.as<uint64_t>(), g_rank_mode, redone.as<uint32_t>(), redo.as<uint32_t>());                                                                \
+            log.v[3] = 1;                                                                                                                                                      \
+        } else {                                                                                                                                                               \
+            hipLaunchKernelGGL((k_bucket2_sort_wave<EW_, false>), dim3(GRID), block, 0, s, d_hk, d_it, d_boff, lists.as<uint32_t>() + (size_t)CLS * nb, n_lists.as<uint32_t>() + CLS, sh, \
+                               counts.as<uint64_t>(), g_rank_mode, redone.as<uint32_t>(), redo.as<uint32_t>());                                                                \
+            log.v[3] = 0;                                                                                                                                                      \
+        }                                                                                                                                                                      \
+        log.items[CLS] = EW_;                                                                                                                                                  \
     } while (0)
 #define FB2_LAUNCH(EM, CLS, GRID)                                                                                                                                           \
-    hipLaunchKernelGGL((k_bucket2_sort<EM, false>), dim3(GRID), block, 0, s, d_hk, d_it, d_boff, lists.as<uint32_t>() + (size_t)CLS * nb, n_lists.as<uint32_t>() + CLS, sh, counts.as<uint64_t>(), \
-                       g_rank_mode, redone.as<uint32_t>(), redo.as<uint32_t>(), fail.as<uint32_t>())
-    hipLaunchKernelGGL(k_bucket2_tiny, dim3(256u * 8u), block, 0, s, d_hk, d_it, d_boff, lists.as<uint32_t>() + (size_t)5 * nb, n_lists.as<uint32_t>() + 5, counts.as<uint64_t>());
+    do {                                                                                                                                                                   \
+        hipLaunchKernelGGL((k_bucket2_sort<EM, false>), dim3(GRID), block, 0, s, d_hk, d_it, d_boff, lists.as<uint32_t>() + (size_t)CLS * nb, n_lists.as<uint32_t>() + CLS, sh, \
+                           counts.as<uint64_t>(), g_rank_mode, redone.as<uint32_t>(), redo.as<uint32_t>(), fail.as<uint32_t>());                                             \
+        log.items[CLS] = EM;                                                                                                                                               \
+        log.v[3 + CLS] = 1; /* (v[6], v[7]: classes 3 and 4) */                                                                                                            \
+    } while (0)
+    FrontLog log;
+    log.v[0] = 2;
+    hipLaunchKernelGGL(k_bucket2_tiny, dim3(256u * 8u), block, 0, s, d_hk, d_it, d_boff, lists.as<uint32_t>() + (size_t)FB2_TINY * nb, n_lists.as<uint32_t>() + FB2_TINY, counts.as<uint64_t>());
+    log.items[FB2_TINY] = 1;
     FB2_WAVE(8, 0, 256u * 8u);
     FB2_WAVE(16, 1, 256u * 4u);
     FB2_WAVE(32, 2, 256u * 2u);
     CK(bft_pin_wait_for(pin, s, ticket));
     const uint32_t mx = (uint32_t)pin.p[0];
     *max_bucket = mx;
-    if (mx > FB_BLOCK * 32) return 0;
-    if (mx > 2048u) FB2_LAUNCH(16, 3, 256u * 4u);
-    if (mx > 4096u) FB2_LAUNCH(32, 4, 256u * 2u);
+    const BftFront2Plan plan = bft_front2_plan(mx, max_gid);
+    log.v[1] = mx;
+    if (plan.declines) {
+        log.v[2] = 1;
+        front_log_commit(log);
+        return 0;
+    }
+    if (plan.class3) FB2_LAUNCH(16, 3, 256u * 4u);
+    if (plan.class4) FB2_LAUNCH(32, 4, 256u * 2u);
+    log.v[4] = (uint32_t)bft_front2_class(mx);
+    log.v[5] = mx ? log.items[bft_front2_class(mx)] : 0u;
+    front_log_commit(log);
 #undef FB2_WAVE
 #undef FB2_LAUNCH
     // the fallback launch: the buckets whose order check failed (none, on every run so far), or all of them ("test_front_rank_mode" 1): the list is `redo`

@@ -1771,6 +1771,9 @@ extern "C" int bft_gpu_set_option(bft_gpu* h, const char* name, int64_t value) {
     } else if (nm == "test_front_rank_mode") {  // test hook (tests/test_gpu_build.py): how the root-prefix buckets rank their digits, see k_bucket_sort
         if (value > 2) return fail(BFT_GPU_E_ARG, "test_front_rank_mode must be 0, 1 or 2");
         bft_test_front_rank_mode((int)value);
+    } else if (nm == "test_front_wave_cap") {  // test hook (tests/test_gpu_front_edges.py): the one-word buckets a wavefront sorts, see bft_front_wave_cap
+        if (value != 0 && value != 512 && value != 1024) return fail(BFT_GPU_E_ARG, "test_front_wave_cap must be 0, 512 or 1024");
+        bft_test_front_wave_cap((uint32_t)value);
     } else if (nm == "test_weak_signature") {  // test hook (tests/test_gpu_build.py): colour-set signatures that collide, see bft_intern_colors_gpu
         if (value < 0 || value > 2) return fail(BFT_GPU_E_ARG, "test_weak_signature must be 0, 1 or 2");  // (2: the exact pass's second key is the length too)
         bft_test_weak_signature((int)value);

@@ -185,9 +185,10 @@ struct bft_gpu {
     uint32_t opt_flat_min = BFT_TRESH_SUF_PREF;  // CCs with at least this many prefixes get the flat form ("flat_min")
     bool has_cs_bm = false, cs_bm_tried = false;
     bool opt_no_cs_bitmaps = false; // test hook ("test_no_cs_bitmaps"): bft_ensure_cs_bitmaps declines, the id lists serve every consumer of the dictionary
-    bool opt_no_composite = false;  // test hook ("build_composite" 0): the general sort + flag-array path also for ordered one-word keys
+    bool opt_no_composite = false;  // test hook ("build_composite" 0): the general sort + flag-array path also for ordered one- and two-word keys
     uint32_t front_redone = 0;      // root-prefix buckets of the last build whose order check failed (bft_front.hip)
     int opt_msd = 1;                // "build_msd": root-prefix buckets + bucket sorts for 2^20 pairs and more (1), always (2: test hook), never (0)
+    uint32_t run_road[4] = {0, 0, 0, 0};  // the last build's sort, for bft_gpu_debug_run_road: {1 + road, id bits gb, id bytes beside the keys, split tried}
     uint32_t msd_max_bucket = 0;    // largest root-prefix bucket of the last build's sort (0: one device-wide sort)
     BftImage im;
     std::vector<uint32_t> hashmod;

@@ -165,7 +165,7 @@ bool pairs_fit(const bft_gpu* h, int gb) { return ordered_w1(h) && (h->max_gid_s
 // (not at k = 32: a limit from the time of the library sort, which mis-sorted the bit range [46, 64) the split would sort -- found by
 // tools/stress_parity.py, k = 32 with build_msd = 2; bft_rs sorts that very range for two-word keys, but k = 32 stays on its tested path)
 bool pairs_split_ok(const bft_gpu* h, int gb) { return bucket_holds_id(h, gb) && 2 * h->k < 64; }
-bool ordered_w2(const bft_gpu* h) { return h->W == 2 && h->log_g_sorted; }
+bool ordered_w2(const bft_gpu* h) { return h->W == 2 && h->log_g_sorted && !h->opt_no_composite; }  // ("build_composite" 0: the general road, as for one word)
 
 // ---- what the roads share ------------------------------------------------------------------------------------------------------------------
 // the run's arrays for nk k-mers of W words and np pairs
@@ -401,17 +401,34 @@ int bft_make_run(bft_gpu* h, BftPairRun& run) {
     if (in.total == 0) return 0;
     const bool split = split_wanted(h, in.total);
     bool done = false;
+    const uint32_t vw = h->max_gid_seen < 256 ? 1u : h->max_gid_seen < 65536 ? 2u : 4u;  // (what pairs_split / pairs_sort narrow the ids to)
     if (composite_fits(h, in.gb)) {
+        const uint32_t road[4] = {1u, (uint32_t)in.gb, 0u, split};
+        std::copy(road, road + 4, h->run_road);
         if (split) CK(composite_split(h, in, run, done));
         if (!done) CK(composite_sort(h, in, run));
     } else if (pairs_fit(h, in.gb)) {
+        const uint32_t road[4] = {2u, (uint32_t)in.gb, vw, split && pairs_split_ok(h, in.gb)};
+        std::copy(road, road + 4, h->run_road);
         if (split && pairs_split_ok(h, in.gb)) CK(pairs_split(h, in, run, done));
         if (!done) CK(pairs_sort(h, in, run));
     } else {
+        const uint32_t road[4] = {3u, (uint32_t)in.gb, 4u, split && ordered_w2(h)};
+        std::copy(road, road + 4, h->run_road);
         if (split && ordered_w2(h)) CK(two_word_split(h, in, run, done));
         if (!done) CK(general_sort(h, in, run));
     }
     return 0;
+}
+
+// Test hook (tests/test_gpu_front_edges.py): the road the last build's sort took.  out = {0 composites T << gb | id, 1 (k-mer, id) pairs of ordered
+// one-word keys, 2 whatever is left (two-word keys, ids out of order, "build_composite" 0); gb, the bits of an id; the bytes of an id beside the keys
+// (0: composites); 1 when the root-prefix split was tried}.  BFT_GPU_E_ARG for NULL or a handle that has not sorted yet.
+extern "C" int bft_gpu_debug_run_road(bft_gpu* h, uint32_t out[4]) {
+    if (!h || !out || h->run_road[0] == 0) return bft_fail(BFT_GPU_E_ARG, "run road: NULL argument or no build yet");
+    out[0] = h->run_road[0] - 1;
+    for (int i = 1; i < 4; i++) out[i] = h->run_road[i];
+    return BFT_GPU_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

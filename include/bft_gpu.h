@@ -251,12 +251,13 @@ int bft_gpu_footprint(bft_gpu* h, uint64_t* out, int n_out);
  *   and they stay until the next build or until the option is set again.  No effect on a handle without a k-mer hash ("kmer_hash" 0).  0: the table stays.)
  * Build: "build_composite" (1, default: one-word keys whose genome ids arrive ascending take the root-prefix front end -- as 8-byte composites
  *   k-mer << bits | genome where that fits 63 bits, as (k-mer, id) pairs whose composite is formed inside a bucket otherwise; 0: the general key + value
- *   sort -- same image either way, a test hook), "composite_log" (1, default: where a one-word key leaves 7 bits or more for the id, k <= 28, the
+ *   sort, also for the two-word keys (33 <= k <= 64) whose ascending ids would take the front end -- same image either way, a test hook), "composite_log" (1, default: where a one-word key leaves 7 bits or more for the id, k <= 28, the
  *   insertion log itself holds those composites -- 8 bytes per pending pair instead of 12, and the root-prefix split reads them as they are;
  *   an id beyond the room, ids that do not ascend or "build_composite" 0 turn the log back into k-mers + ids; 0: always k-mers + ids --
  *   same image, a test hook; only while the log is empty), "build_msd"(1, default: root-prefix buckets + bucket sorts from 2^20 pairs on; 0: one
  *   device-wide sort; 2: buckets at any size -- same image, test hooks), "test_front_rank_mode" (process-wide test hook: how a bucket ranks its digits:
- *   0, default = LDS atomics + order check + ballot fallback, 1 = ballots only, 2 = the check always fails), "sort_ballots" (process-wide: how the library's own
+ *   0, default = LDS atomics + order check + ballot fallback, 1 = ballots only, 2 = the check always fails), "test_front_wave_cap" (process-wide test hook:
+ *   the largest one-word bucket that a single wavefront sorts: 0, default = 512 or 1024 by the mean bucket, 512 / 1024 = that value; same image), "sort_ballots" (process-wide: how the library's own
  *   radix sort -- csrc/bft_sort.h -- ranks the keys of a wavefront: 0, default = one LDS atomic per key once the device has shown that it serves the lanes of such an
  *   instruction in lane order, 1 = wavefront ballots, stable by construction; same image), "reserve_pairs" (room in the insertion log for this many pending (k-mer, genome)
  *   pairs, so that a series of insert calls never re-allocates it), "flush_pairs" (the log is merged into the index before it holds this many pairs:
@@ -280,6 +281,26 @@ int bft_gpu_debug_color_rows_plan(uint32_t rowbytes, int form, uint32_t out[3]);
  * 2048 chunks of whole tiles of 256 candidates, one chunk per workgroup.  out[0] = the chunk size, out[1], out[2] = [begin, end) of chunk
  * `chunk` (both C for a chunk behind the last candidate).  BFT_GPU_E_ARG for a NULL out or chunk >= 2048.  No handle, no device. */
 int bft_gpu_debug_prefix_plan(uint64_t C, uint32_t chunk, uint64_t out[3]);
+/* Test hook: which kernels the build's front end behind the root-prefix split picks (csrc/bft_front_plan.h) for n pairs in nb buckets, the largest
+ * of max_bucket pairs, the largest genome id max_gid, "test_front_wave_cap" = wave_cap (0, 512 or 1024), and who sorts a bucket of `bucket` pairs.
+ * words 1 (k <= 32): out = {the wavefront kernel's largest bucket, its pairs per lane (8 / 16), the workgroup kernel's pairs per thread (6, 9, 12,
+ * 16; 0: not launched), 1 when the call declines (the build then sorts device-wide), the capacity 4096, the owner of `bucket` (0 nobody, 1 the
+ * wavefront kernel, 2 the workgroup kernel), 0, 0}.  words 2 (33 <= k <= 64): out = {1 when the ids fit 18 bits (the packed kernels), 1 when the
+ * kernel of the buckets beyond 2048 is launched, the same beyond 4096, 1 when the call declines, the capacity 8192, the size class of `bucket`
+ * (5: up to 64; 0, 1, 2: up to 512, 1024, 2048; 3, 4: up to 4096, 8192; 0xFFFFFFFF: empty), pairs per lane or thread of the class's kernel, its
+ * owner (0 nobody, 1 the wavefront kernel, 2 the workgroup kernel, 3 the kernel of the tiny buckets)}.  BFT_GPU_E_ARG for a NULL out, other words,
+ * another wave_cap or bucket > max_bucket.  No handle, no device. */
+int bft_gpu_debug_front_plan(int words, uint64_t n, uint32_t nb, uint32_t max_bucket, uint32_t max_gid, uint32_t wave_cap, uint32_t bucket, uint32_t out[8]);
+/* Test hook: what the front end launched in its last call of this process (any handle; written where each kernel is launched): out = {words, the
+ * largest bucket, 1 when it declined, then words 1: the largest bucket of the wavefront kernel launched, its pairs per lane, the pairs per thread of the
+ * workgroup kernel launched (0: none), 0, 0; words 2: 1 when the packed wavefront kernels were launched (ids within 18 bits), the size class of the largest
+ * bucket, pairs per lane or thread of the kernel launched on that class's list (0: none), 1 when the kernel of the buckets beyond 2048 was launched, the
+ * same beyond 4096}.  Reading clears it: all 0 until the front end runs again.  BFT_GPU_E_ARG for a NULL out. */
+int bft_gpu_debug_front_last(uint32_t out[8]);
+/* Test hook: the road the sort of h's last build took: out = {0: composites k-mer << gb | id of up to 63 bits, 1: (k-mer, id) pairs of one-word keys
+ * whose ids ascend, 2: whatever is left (two-word keys, ids out of order, "build_composite" 0); gb, the bits of a genome id; the bytes of an id beside
+ * the keys (0 on road 0; 1, 2 or 4 on road 1; 4 on road 2); 1 when the root-prefix split was tried}.  BFT_GPU_E_ARG for NULL or before the first build. */
+int bft_gpu_debug_run_road(bft_gpu* h, uint32_t out[4]);
 
 /* HIP-event timing of the query kernels launched through this handle since the last reset:
  * *ms = summed kernel time, *launches = number of launches.  Timing is off by default (no event on the launch path); the
