@@ -79,6 +79,7 @@ SIGNATURES = {
     "bft_gpu_combine_colors_dev": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_int, C.c_int, _P, _P, _P, _P]),
     "bft_gpu_combine_colorsets": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_int, _P, _P]),
     "bft_gpu_combine_colorsets_dev": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_int, _P, _P, _P]),
+    "bft_gpu_debug_setops_plan": (C.c_int, [C.POINTER(C.c_uint64)]),
     "bft_gpu_marks_begin": (C.c_int, [_P]),
     "bft_gpu_marks_end": (C.c_int, [_P]),
     "bft_gpu_marks_set": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint8, C.POINTER(C.c_uint64)]),

@@ -1,4 +1,5 @@
 // bft_setops.h -- colour-set algebra over groups of k-mers (bft_setops.hip): what the kernels of bft_gpu_combine_colors / bft_gpu_combine_colorsets share.
+// The class bounds below and the kernels' grids reach the tests through bft_gpu_debug_setops_plan: no test repeats a literal of this file.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

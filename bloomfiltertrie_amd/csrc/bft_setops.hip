@@ -27,6 +27,7 @@ namespace {
 
 constexpr int SO_THREADS = 256;
 constexpr int SO_SPLIT_BLOCKS = 512;
+constexpr int SO_FINISH_BLOCKS = 64;
 
 __device__ __forceinline__ void so_range(const uint64_t* __restrict__ off, uint64_t g, uint64_t n, uint64_t& a, uint64_t& e) {
     a = off[g];
@@ -297,7 +298,7 @@ int bft_so_reduce(const BftSoDict& d, const BftSoBatch& b, const BftSoScratch& p
         if (narrow) hipLaunchKernelGGL(k_so_split<true>, dim3(SO_SPLIT_BLOCKS), blk, 0, s, d, b, (const unsigned long long*)p.nsplit, (const uint32_t*)p.split);
         else hipLaunchKernelGGL(k_so_split<false>, dim3(SO_SPLIT_BLOCKS), blk, 0, s, d, b, (const unsigned long long*)p.nsplit, (const uint32_t*)p.split);
         break;
-    default: hipLaunchKernelGGL(k_so_finish, dim3(64), blk, 0, s, d, b, (const unsigned long long*)p.nsplit, (const uint32_t*)p.split); break;
+    default: hipLaunchKernelGGL(k_so_finish, dim3(SO_FINISH_BLOCKS), blk, 0, s, d, b, (const unsigned long long*)p.nsplit, (const uint32_t*)p.split); break;
     }
     HIPCK(hipGetLastError());
     return 0;
@@ -318,6 +319,18 @@ int bft_so_count(const BftSoDict& d, const uint32_t* R, uint64_t ng, uint32_t* d
     hipLaunchKernelGGL(k_so_count, so_grid(ng * L), dim3(SO_THREADS), 0, s, R, d.nw, ng, L, d_counts);
     HIPCK(hipGetLastError());
     return 0;
+}
+
+// Test hook: the constants that decide a group's class and every kernel's grid (tests/test_setops_cases_host.py derives its cases from them).
+extern "C" int bft_gpu_debug_setops_plan(uint64_t out[6]) {
+    if (!out) return bft_fail(BFT_GPU_E_ARG, "NULL argument");
+    out[0] = BFT_SO_SMALL;
+    out[1] = BFT_SO_WAVE_MAX;
+    out[2] = BFT_SO_CHUNK;
+    out[3] = (uint64_t)SO_SPLIT_BLOCKS * (SO_THREADS / 64);
+    out[4] = (uint64_t)SO_FINISH_BLOCKS * SO_THREADS;
+    out[5] = (uint64_t)bft_grid_for(~0ull) * SO_THREADS;  // (so_grid of a batch beyond the cap)
+    return BFT_GPU_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -509,6 +509,10 @@ int bft_gpu_combine_colorsets(bft_gpu* h, const uint32_t* colorsets, uint64_t nb
                               uint32_t* counts);
 int bft_gpu_combine_colorsets_dev(bft_gpu* h, const void* d_colorsets, uint64_t nb, const void* d_group_off, uint64_t nb_groups, int op, void* d_rows,
                                   void* d_counts, void* hip_stream);
+/* Test hook: out[0] = the largest group that takes a lane per (group, word), out[1] = the largest group one wavefront reduces (larger ones are split),
+ * out[2] = members per step of a split group, out[3] = wavefronts of the split kernel's grid, out[4] = lanes of the grid that finishes the split groups,
+ * out[5] = lanes of the capped grid of every other kernel.  BFT_GPU_E_ARG for a NULL out.  No handle, no device. */
+int bft_gpu_debug_setops_plan(uint64_t out[6]);
 
 /* Vertex marking: set_marking / unset_marking / set_flag_kmer / get_flag_kmer (reference include/bft.h:143-146, src/bft.c:686-765) for batches, and
  * what the reference's traversals do with the marks (BFS / DFS / BFS_subgraph / DFS_subgraph, src/snippets.c:605-812) as ONE call, bft_gpu_marks_reach.

@@ -17,7 +17,7 @@ from bloomfiltertrie_amd.bft import BFT
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNELS = {"k_so_plan", "k_so_small", "k_so_wave", "k_so_split", "k_so_finish", "k_so_emit", "k_so_count"}
-ABI = ("bft_gpu_combine_colors", "bft_gpu_combine_colors_dev", "bft_gpu_combine_colorsets", "bft_gpu_combine_colorsets_dev")
+ABI = ("bft_gpu_combine_colors", "bft_gpu_combine_colors_dev", "bft_gpu_combine_colorsets", "bft_gpu_combine_colorsets_dev", "bft_gpu_debug_setops_plan")
 OPS = ("intersection_annotations", "union_annotations", "sym_difference_annotations")
 
 PROGRAM = r"""
