@@ -1,13 +1,12 @@
 // bft_handle.h -- the handle behind the C-ABI (struct bft_gpu) and the host helpers every entry point needs, for the translation units that hold
-// entry points: bft_gpu.hip (lifecycle, pool, log, image binding and commit, files, options and info: it defines the helpers), bft_query.hip (the k-mer and
+// entry points: bft_gpu.hip (lifecycle, pool, log, build and commit, files, the blob, options and info: it defines the helpers), bft_derive.hip (what the
+// handle derives from a committed image, bft_derive.h: root tables, k-mer hash, node prefix hash, launch shape, compact table), bft_query.hip (the k-mer and
 // sequence queries, their tuner, the claim slots), bft_run.hip (the build's run stage, the sort and scan test hooks) and the analysis families
 // bft_prefix.hip, bft_paths.hip, bft_components.hip, bft_pangenome.hip, bft_subgraph.hip, bft_marking.hip, bft_setops.hip, bft_union.hip, bft_ingest.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <cstring>
-#include <thread>
-
+#include "bft_derive.h"  // bft_rederive, bft_ensure_table / bft_drop_table, the k-mer hash fill of a build (KhFill)
 #include "bft_dev.h"
 #include "bft_image.h"
 #include "bft_ingest.h"
@@ -300,8 +299,8 @@ int bft_log_commit(bft_gpu* h, uint64_t n, uint32_t id_genome, hipStream_t s);
 // image on the handle's stream (synchronises once); has_cs_bm stays false where it would pass 4 GiB or "test_no_cs_bitmaps" is set.
 #define CS_BM_SLACK 32u  // zero bytes in front of and behind the bitmap dictionary
 int bft_ensure_cs_bitmaps(bft_gpu* h);
-int bft_ensure_table(bft_gpu* h);  // "compact_table": the sorted table and the colour set per row, back from the k-mer hash (synchronises)
-void bft_drop_table(bft_gpu* h);   // "compact_table": dropped again where the option and the k-mer hash allow it (nothing may still be reading it)
+// Before image arrays are released, rewritten or re-derived: the queries the caller still has in flight must have drained.
+int bft_wait_foreign_stream(bft_gpu* h);
 
 // Timed launches ("timing"): a pair of pooled events around the kernel (no event is created on the launch path once the pool is warm).
 int bft_timing_begin(bft_gpu* h, hipStream_t s, hipEvent_t* e0, hipEvent_t* e1);
@@ -334,30 +333,6 @@ int bft_make_run(bft_gpu* h, BftPairRun& run);
 int bft_sort_pairs(bft_gpu* h, const uint64_t* keys, uint64_t stride, const uint32_t* g, uint64_t total, uint64_t* okeys, uint64_t ostride, uint32_t* og,
                    bool g_already_ordered, bool is_log = false);
 
-// The build of the k-mer hash for a table (tk, tcol) that is complete on the device, started on the handle's second stream: the build
-// assembles the containers on `stream` meanwhile.  The build sorts and gathers and starves what runs beside it of memory bandwidth and
-// latency (k_prefix_flags over the whole table: 0.2 ms alone, 2.8 ms beside it; the root's single-workgroup k_assign_cc: 0.8 -> 3.5 ms),
-// so it starts behind those (`after`: an event of the assembly stream) and overlaps the chain of small kernels and read-back counts that
-// follows.  kh_finish waits for it.  Any failure just leaves the image without the table.
-struct KhFill {
-    DevBuf buf, status, ovf_k, ovf_v;
-    BftKhScratch scratch;
-    BftKhGeo geo;
-    uint64_t lines_cap = 0, lines_used = 0;
-    uint32_t ovf_n = 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr, ew = nullptr;
-    hipStream_t s2 = nullptr;
-    bool started = false, prepared = false;
-    std::thread prep;  // kh_prepare_async
-    KhFill() { memset(&geo, 0, sizeof(geo)); }
-    ~KhFill() {  // (a build that fails half-way: the fill must be over before its buffers go back to the cache)
-        if (prep.joinable()) prep.join();
-        if (started && s2) (void)hipStreamSynchronize(s2);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        if (ew) (void)hipEventDestroy(ew);
-    }
-};
 // What only bft_gpu_build carries into the commit: the run's genome-id lists (the input of the interning: its deferred tail reads them, and the exact
 // interning runs on them again where two lists shared a signature), the k-mer hash fill it prepared, and that tail.  (In this order: the fill and
 // the tail are waited for by their destructors before the lists they read go back to the cache.)
