@@ -51,6 +51,7 @@ SIGNATURES = {
     "bft_gpu_debug_prefix_plan": (C.c_int, [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]),
     "bft_gpu_debug_front_last": (C.c_int, [C.POINTER(C.c_uint32)]),
     "bft_gpu_debug_run_road": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    "bft_gpu_debug_run_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32)]),
     "bft_gpu_debug_front_plan": (C.c_int, [C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "bft_gpu_query_color_rows_dev": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, _P]),
     "bft_gpu_info": (C.c_int, [_P, C.POINTER(C.c_uint64), C.c_int]),

@@ -22,6 +22,7 @@
 #include "bft_handle.h"
 #include "bft_hash.h"
 #include "bft_index.h"
+#include "bft_run_plan.h"
 #include "bft_sort.h"
 #include "bft_walk.h"
 
@@ -388,10 +389,8 @@ extern "C" int bft_gpu_add_genome(bft_gpu* h, const char* name, uint32_t* id_gen
 // ------------------------------------------------------------------------------------------------
 // insertion log
 // ------------------------------------------------------------------------------------------------
-static uint32_t log_comp_bits(const bft_gpu* h) {  // id bits of a composite log, 0: this handle logs k-mers + ids
-    const int room = 63 - 2 * h->k;
-    return (h->W == 1 && h->opt_comp_log && !h->opt_no_composite && room >= 7) ? (uint32_t)std::min(room, 24) : 0u;
-}
+// (the log's format follows bft_run_plan.h, like the road the build takes with it)
+static uint32_t log_comp_bits(const bft_gpu* h) { return bft_run_log_comp_bits(h->k, h->W, h->opt_comp_log != 0, !h->opt_no_composite); }
 // a log of composites back into T-form k-mers and their ids (in place + the id array)
 __global__ void k_log_decompose(uint64_t* __restrict__ log_k, uint64_t n, uint32_t cgb, uint32_t* __restrict__ log_g) {
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
@@ -447,7 +446,7 @@ static int log_reserve(bft_gpu* h, uint64_t need) {
 int bft_log_prepare(bft_gpu* h, uint64_t n, uint32_t id_genome) {
     if (h->log_n && h->log_n + n > h->opt_flush_pairs) CK(bft_gpu_build(h));
     CK(log_reserve(h, h->log_n + n));
-    if (h->log_comp && (id_genome >> h->log_gb) != 0) CK(log_decompose(h));  // (an id the composites have no room for)
+    if (h->log_comp && !bft_run_log_holds_id(h->log_gb, id_genome)) CK(log_decompose(h));  // (an id the composites have no room for)
     return 0;
 }
 // n rows for id_genome were written behind the log's end
@@ -786,7 +785,7 @@ extern "C" int bft_gpu_build(bft_gpu* h) {
     ENTER(h);
     if (h->built && h->log_n == 0) return BFT_GPU_OK;
     CK(bft_wait_foreign_stream(h));  // batches still being packed into the log on a caller's stream (bft_gpu_insert_kmers_dev_async)
-    if (h->log_comp && (!h->log_g_sorted || h->opt_no_composite)) CK(log_decompose(h));  // (only the composite path below takes a log of composites)
+    if (h->log_comp && !bft_run_log_stays_composite(h->log_g_sorted, !h->opt_no_composite)) CK(log_decompose(h));  // (only the composite path below takes a log of composites)
     if (h->built) CK(bft_ensure_table(h));  // ("compact_table": the merge reads the index's sorted table)
     const double t0 = bft_now_ms();
     bft_trace_mark(nullptr);

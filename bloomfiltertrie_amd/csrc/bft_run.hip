@@ -1,6 +1,7 @@
 // bft_run.hip -- steps 1-3 of the bulk build: the insertion log becomes a run (BftPairRun: sorted distinct T-form k-mers, the offsets of their
-// genome-id lists, the ids).  bft_make_run is the list of the roads a log can take, with their conditions and fallbacks; every road is a function
-// of its own below it.  Sorts and scans are the library's own (bft_sort.h, bft_scan.h); the buckets behind the root-prefix split are
+// genome-id lists, the ids).  bft_make_run is the list of the roads a log can take, with their fallbacks; every road is a function of its own
+// below it, and the conditions that choose among them are plain host functions in bft_run_plan.h (bft_run_road; bft_gpu_debug_run_plan hands them
+// to the tests).  Sorts and scans are the library's own (bft_sort.h, bft_scan.h); the buckets behind the root-prefix split are
 // bft_front.hip's; the kernels launched here are bft_kernels_build.h's.  bft_sort_pairs, the general permutation sort, is also what
 // bft_ensure_table and the sub-graph build order their records with.  See DESIGN.md "Insertion".  At the end: the sort and scan test hooks, in the
 // unit that instantiates the library's sorts anyway.
@@ -10,6 +11,7 @@
 
 #include "bft_handle.h"
 #include "bft_paths.h"  // BftSpHead (bft_gpu_test_scan_ex)
+#include "bft_run_plan.h"
 #include "bft_scan.h"
 #include "bft_sort.h"
 
@@ -68,11 +70,7 @@ struct BftPairFlags {  // input of the scan: (first pair of its k-mer) << 32 | (
 thread_local bft_rs::RunRecord bft_rs::g_bft_rs_last;  // what this thread's last library sort ran (test hooks: bft_gpu_test_sort_last)
 int bft_rs::g_bft_rs_rank_mode = -1;  // how bft_sort.h ranks: 0 LDS atomics (lane order checked on the device), 1 ballots ("sort_ballots")
 
-static int bits_for(uint64_t v) {
-    int b = 1;
-    while (b < 64 && (v >> b)) b++;
-    return b;
-}
+static int bits_for(uint64_t v) { return bft_run_id_bits(v); }
 
 int bft_sort_pairs(bft_gpu* h, const uint64_t* keys, uint64_t stride, const uint32_t* g, uint64_t total, uint64_t* okeys, uint64_t ostride, uint32_t* og,
                    bool g_already_ordered, bool is_log) {
@@ -125,7 +123,7 @@ int bft_sort_pairs(bft_gpu* h, const uint64_t* keys, uint64_t stride, const uint
     // (one pass over the permutation for every word and the id, instead of a pass each; the ids of the LOG come out of the table of its insert calls)
     DevBuf lbe, lbg;
     uint32_t nlb = 0;
-    if (is_log && !h->lb_end.empty() && h->lb_end.size() <= (1u << 16) && h->lb_end.back() == total) {
+    if (is_log && !h->lb_end.empty() && h->lb_end.size() <= BFT_RUN_CALL_TABLE_MAX && h->lb_end.back() == total) {
         nlb = (uint32_t)h->lb_end.size();
         CK(lbe.alloc(nlb * 8));
         CK(lbg.alloc(nlb * 4));
@@ -147,25 +145,9 @@ struct LogIn {
     int gb;  // bits of a genome id (a log of composites: their id field as logged)
 };
 
-// ---- which road: every condition once ------------------------------------------------------------------------------------------------------
-constexpr int SPLIT_TOP = 18;  // the root-prefix split sorts on the top 18 bits of the T-form (all of them below k = 9)
-unsigned split_top(const bft_gpu* h) { return (unsigned)std::min(SPLIT_TOP, 2 * h->k); }
-// one-word keys whose ids arrived ascending: the stable sorts keep the ids in order inside a k-mer ("build_composite" 0: the general road anyway)
-bool ordered_w1(const bft_gpu* h) { return h->W == 1 && h->log_g_sorted && !h->opt_no_composite; }
-// (composites of up to 63 bits: a limit from the time of the library sort -- rocPRIM's radix sort mis-sorts the bit range [2, 64), found by
-// test_any_k_against_ground_truth[31-0] -- kept: the paths behind it are the tested ones for such k)
-bool composite_fits(const bft_gpu* h, int gb) { return ordered_w1(h) && 2 * h->k + gb <= 63; }
-// "build_msd": the root-prefix split + bucket sorts for 2^20 pairs and more (1), always (2), never (0)
-bool split_wanted(const bft_gpu* h, uint64_t total) { return h->opt_msd && (total >= (1u << 20) || h->opt_msd == 2); }
-// inside a root-prefix bucket the prefix is implied: the bits below it and the id make a composite of one word
-bool bucket_holds_id(const bft_gpu* h, int gb) { return (2 * h->k - (int)split_top(h)) + gb <= 64; }
-// ordered one-word keys whose composite does not fit travel as (k-mer, id) pairs, where that beats the general road: ids narrowed to one or
-// two bytes, or buckets that hold the id
-bool pairs_fit(const bft_gpu* h, int gb) { return ordered_w1(h) && (h->max_gid_seen < 65536 || bucket_holds_id(h, gb)); }
-// (not at k = 32: a limit from the time of the library sort, which mis-sorted the bit range [46, 64) the split would sort -- found by
-// tools/stress_parity.py, k = 32 with build_msd = 2; bft_rs sorts that very range for two-word keys, but k = 32 stays on its tested path)
-bool pairs_split_ok(const bft_gpu* h, int gb) { return bucket_holds_id(h, gb) && 2 * h->k < 64; }
-bool ordered_w2(const bft_gpu* h) { return h->W == 2 && h->log_g_sorted && !h->opt_no_composite; }  // ("build_composite" 0: the general road, as for one word)
+// ---- which road: every condition once, in bft_run_plan.h (plain values in; bft_make_run hands it the handle's) -----------------------------------
+constexpr int SPLIT_TOP = BFT_RUN_SPLIT_TOP;
+unsigned split_top(const bft_gpu* h) { return bft_run_split_top(h->k); }
 
 // ---- what the roads share ------------------------------------------------------------------------------------------------------------------
 // the run's arrays for nk k-mers of W words and np pairs
@@ -319,15 +301,17 @@ int split_dedupe_w1(bft_gpu* h, const LogIn& in, BftPairRun& run, bool& done) {
 }
 // 2s. the root-prefix split with the ids beside the keys, then the buckets -- where the composite does fit, the bucket's number being implied
 int pairs_split(bft_gpu* h, const LogIn& in, BftPairRun& run, bool& done) {
-    if (h->max_gid_seen < 256) return split_dedupe_w1<uint8_t>(h, in, run, done);
-    if (h->max_gid_seen < 65536) return split_dedupe_w1<uint16_t>(h, in, run, done);
+    const uint32_t vw = bft_run_id_width(h->max_gid_seen);
+    if (vw == 1) return split_dedupe_w1<uint8_t>(h, in, run, done);
+    if (vw == 2) return split_dedupe_w1<uint16_t>(h, in, run, done);
     return split_dedupe_w1<uint32_t>(h, in, run, done);
 }
 // 2n + 3'. one key + value sort over every bit with the ids narrowed to one or two bytes (the values are a third of
 // the sort's traffic at four), flags on the fly, one scan
 int pairs_sort(bft_gpu* h, const LogIn& in, BftPairRun& run) {
-    if (h->max_gid_seen < 256) return sort_dedupe_w1_narrow<uint8_t>(h, in, run);
-    if (h->max_gid_seen < 65536) return sort_dedupe_w1_narrow<uint16_t>(h, in, run);
+    const uint32_t vw = bft_run_id_width(h->max_gid_seen);
+    if (vw == 1) return sort_dedupe_w1_narrow<uint8_t>(h, in, run);
+    if (vw == 2) return sort_dedupe_w1_narrow<uint16_t>(h, in, run);
     return sort_dedupe_w1_narrow<uint32_t>(h, in, run);
 }
 
@@ -399,26 +383,43 @@ int bft_make_run(bft_gpu* h, BftPairRun& run) {
     h->msd_max_bucket = 0;
     const LogIn in{h->log_k.as<uint64_t>(), h->log_g.as<uint32_t>(), h->log_cap, h->log_n, h->log_comp ? (int)h->log_gb : bits_for(h->max_gid_seen)};
     if (in.total == 0) return 0;
-    const bool split = split_wanted(h, in.total);
+    const BftRunRoad road = bft_run_road(h->k, h->W, h->log_g_sorted, !h->opt_no_composite, h->opt_msd, h->max_gid_seen, in.gb, in.total);
+    std::copy(road.v, road.v + 4, h->run_road);
+    const bool split = road.v[3] != 0;
     bool done = false;
-    const uint32_t vw = h->max_gid_seen < 256 ? 1u : h->max_gid_seen < 65536 ? 2u : 4u;  // (what pairs_split / pairs_sort narrow the ids to)
-    if (composite_fits(h, in.gb)) {
-        const uint32_t road[4] = {1u, (uint32_t)in.gb, 0u, split};
-        std::copy(road, road + 4, h->run_road);
+    if (road.v[0] == 1u) {
         if (split) CK(composite_split(h, in, run, done));
         if (!done) CK(composite_sort(h, in, run));
-    } else if (pairs_fit(h, in.gb)) {
-        const uint32_t road[4] = {2u, (uint32_t)in.gb, vw, split && pairs_split_ok(h, in.gb)};
-        std::copy(road, road + 4, h->run_road);
-        if (split && pairs_split_ok(h, in.gb)) CK(pairs_split(h, in, run, done));
+    } else if (road.v[0] == 2u) {
+        if (split) CK(pairs_split(h, in, run, done));
         if (!done) CK(pairs_sort(h, in, run));
     } else {
-        const uint32_t road[4] = {3u, (uint32_t)in.gb, 4u, split && ordered_w2(h)};
-        std::copy(road, road + 4, h->run_road);
-        if (split && ordered_w2(h)) CK(two_word_split(h, in, run, done));
+        if (split) CK(two_word_split(h, in, run, done));
         if (!done) CK(general_sort(h, in, run));
     }
     return 0;
+}
+
+// Test hook (tests/test_run_cases_host.py): the rules of bft_run_plan.h without a handle or a device, for a log of `total` pairs of k-mers of length k
+// whose ids ascend (ids_ordered) or not, under "build_composite", "build_msd" and "composite_log"; max_gid: the largest id the handle has seen,
+// log_max_gid: the largest id of this log (they differ behind an earlier build).  out = {what bft_gpu_debug_run_road reports [0..3]; the id bits of a
+// composite log of such a handle (0: k-mers + ids are logged); 1 when the log is still one of composites at build time; the threads of a capped
+// bft_grid_for grid of 256-thread workgroups; the largest table of insert calls the multi-word sort reads ids from}.
+extern "C" int bft_gpu_debug_run_plan(int k, int ids_ordered, int build_composite, int build_msd, int composite_log, uint32_t max_gid, uint32_t log_max_gid, uint64_t total,
+                                      uint32_t out[8]) {
+    if (!out || k < 9 || k > 126 || build_msd < 0 || build_msd > 2 || log_max_gid > max_gid || total == 0) return bft_fail(BFT_GPU_E_ARG, "run plan: argument");
+    const int W = (2 * k + 63) / 64;
+    const bool ordered = ids_ordered != 0, composite = build_composite != 0;
+    const uint32_t log_gb = bft_run_log_comp_bits(k, W, composite_log != 0, composite);
+    const bool comp = log_gb != 0 && bft_run_log_holds_id(log_gb, log_max_gid) && bft_run_log_stays_composite(ordered, composite);
+    const BftRunRoad road = bft_run_road(k, W, ordered, composite, build_msd, max_gid, comp ? (int)log_gb : bft_run_id_bits(max_gid), total);
+    out[0] = road.v[0] - 1;
+    for (int i = 1; i < 4; i++) out[i] = road.v[i];
+    out[4] = log_gb;
+    out[5] = comp;
+    out[6] = (uint32_t)bft_grid_for(~0ull) * 256u;
+    out[7] = BFT_RUN_CALL_TABLE_MAX;
+    return BFT_GPU_OK;
 }
 
 // Test hook (tests/test_gpu_front_edges.py): the road the last build's sort took.  out = {0 composites T << gb | id, 1 (k-mer, id) pairs of ordered

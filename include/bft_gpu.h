@@ -301,6 +301,15 @@ int bft_gpu_debug_front_last(uint32_t out[8]);
  * whose ids ascend, 2: whatever is left (two-word keys, ids out of order, "build_composite" 0); gb, the bits of a genome id; the bytes of an id beside
  * the keys (0 on road 0; 1, 2 or 4 on road 1; 4 on road 2); 1 when the root-prefix split was tried}.  BFT_GPU_E_ARG for NULL or before the first build. */
 int bft_gpu_debug_run_road(bft_gpu* h, uint32_t out[4]);
+/* Test hook: the rules behind that road (csrc/bft_run_plan.h) for a log of `total` pairs of k-mers of length k whose genome ids ascend over the insert
+ * calls (ids_ordered 1) or not, under "build_composite", "build_msd" and "composite_log" as given; max_gid: the largest id the handle has seen,
+ * log_max_gid <= max_gid: the largest id of this log (they differ behind an earlier build).  out = {the four words bft_gpu_debug_run_road would report;
+ * the id bits of a composite log of such a handle (0: it logs k-mers + ids); 1 when the log still holds composites at build time; the threads of a
+ * capped launch grid (2048 workgroups of 256): a kernel of the run stage takes a second pass beyond that many pairs; the largest table of insert
+ * calls the sort of multi-word keys reads a pair's id from (65536 entries: beyond it, from the log's id array)}.  BFT_GPU_E_ARG for a NULL out, k
+ * outside 9..126, another build_msd, log_max_gid > max_gid or total 0.  No handle, no device. */
+int bft_gpu_debug_run_plan(int k, int ids_ordered, int build_composite, int build_msd, int composite_log, uint32_t max_gid, uint32_t log_max_gid, uint64_t total,
+                           uint32_t out[8]);
 
 /* HIP-event timing of the query kernels launched through this handle since the last reset:
  * *ms = summed kernel time, *launches = number of launches.  Timing is off by default (no event on the launch path); the
