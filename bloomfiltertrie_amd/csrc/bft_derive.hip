@@ -16,10 +16,11 @@
 #include "bft_sort.h"
 #include "bft_walk.h"
 
-static uint64_t image_bytes(const bft_gpu* h) {
-    return h->d_nodes.bytes + h->d_bfT.bytes + h->d_ccs.bytes + h->d_f2w.bytes + h->d_clus.bytes + h->d_child.bytes + h->d_tk.bytes + h->d_tcol.bytes +
-           h->d_uck.bytes + h->d_ucrow.bytes + h->d_cs_off.bytes + h->d_cs_ids.bytes + h->d_hashmod.bytes + h->d_cs_bm.bytes + h->d_ccx.bytes +
-           h->d_f18.bytes + h->d_fent.bytes + h->d_rdir.bytes + h->d_rstart.bytes + h->d_rq.bytes + h->d_nph.bytes + h->d_kh.bytes + h->d_rspec.bytes + h->d_kh_ovf_k.bytes + h->d_kh_ovf_v.bytes;
+// what the image holds of the device's memory: every stored and derived array (bft_stored.h) and the hash table of the Bloom filters
+static uint64_t image_bytes(bft_gpu* h) {
+    const BftStoredRows st = bft_stored_rows(h);
+    const BftDerivedRows dv = bft_derived_rows(h);
+    return bft_rows_resident(st.row, 0, BFT_N_STORED) + bft_rows_resident(dv.row, 0, BFT_N_DERIVED) + h->d_hashmod.bytes;
 }
 
 // Points h->im at the device arrays of the handle (cannot fail).

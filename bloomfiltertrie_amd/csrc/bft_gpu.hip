@@ -1,5 +1,6 @@
 // bft_gpu.hip -- the C-ABI of include/bft_gpu.h: handle (bft_handle.h), device-memory cache, insertion log, bulk build (its run stage: bft_run.hip) and
-// commit, .bft files, image replication, options and info.  What the handle derives from a committed image -- root tables, k-mer hash, node prefix hash,
+// commit, options and info.  The image read out and in -- files, the replication blob, the read-outs, the width of the dictionary's ids -- is
+// bft_image_io.hip; what the handle derives from a committed image -- root tables, k-mer hash, node prefix hash,
 // launch shape, compact table -- is bft_derive.hip; the k-mer and sequence queries, their tuner and the claim slots are bft_query.hip; prefixes,
 // sub-graphs, paths, components and the other analysis families sit beside their kernels.  Device code from
 //   bft_kernels_query.h  k_pack_to_tform (packed 2-bit k-mers -> T-form words: the per-level rev[]/rotation work of
@@ -13,12 +14,10 @@
 #include <cstring>
 #include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/bft_gpu.h"
 #include "bft_color_plan.h"
-#include "bft_file.h"
 #include "bft_handle.h"
 #include "bft_hash.h"
 #include "bft_index.h"
@@ -414,7 +413,7 @@ static int log_decompose(bft_gpu* h) {
     h->log_comp = false;
     return 0;
 }
-static int log_reserve(bft_gpu* h, uint64_t need) {
+int bft_log_reserve(bft_gpu* h, uint64_t need) {
     if (h->log_n == 0 && h->log_cap == 0) {  // an empty log: its format is decided here
         h->log_gb = log_comp_bits(h);
         h->log_comp = h->log_gb != 0;
@@ -445,7 +444,7 @@ static int log_reserve(bft_gpu* h, uint64_t need) {
 
 int bft_log_prepare(bft_gpu* h, uint64_t n, uint32_t id_genome) {
     if (h->log_n && h->log_n + n > h->opt_flush_pairs) CK(bft_gpu_build(h));
-    CK(log_reserve(h, h->log_n + n));
+    CK(bft_log_reserve(h, h->log_n + n));
     if (h->log_comp && !bft_run_log_holds_id(h->log_gb, id_genome)) CK(log_decompose(h));  // (an id the composites have no room for)
     return 0;
 }
@@ -547,69 +546,6 @@ extern "C" int bft_gpu_insert_kmers(bft_gpu* h, const uint8_t* kmers, uint64_t n
 // ------------------------------------------------------------------------------------------------
 // bulk build
 // ------------------------------------------------------------------------------------------------
-template <class T>
-static int upload(DevBuf& d, const std::vector<T>& v) {
-    CK(d.alloc(v.size() * sizeof(T)));
-    if (!v.empty()) HIPCK(hipMemcpy(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return 0;
-}
-
-// The genome ids of the dictionary stay resident in the narrowest width that holds every id (a pan-genome of 100 genomes: one byte
-// instead of four -- 484 MB -> 121 MB on config 3, 8 of the image's 49 bytes per k-mer); the build and the merge work on 32-bit ids.
-template <class T>
-__global__ void k_narrow_ids(const uint32_t* __restrict__ in, uint64_t n, T* __restrict__ out) {
-    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) out[i] = (T)in[i];
-}
-template <class T>
-__global__ void k_widen_ids(const T* __restrict__ in, uint64_t n, uint32_t* __restrict__ out) {
-    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) out[i] = (uint32_t)in[i];
-}
-static uint32_t id_width(uint32_t max_gid) { return max_gid < 256u ? 1u : (max_gid < 65536u ? 2u : 4u); }
-// ids32 (n u32) -> out in width w; w == 4: the buffers are swapped
-static int narrow_ids(DevBuf& ids32, uint64_t n, uint32_t w, hipStream_t s, DevBuf& out) {
-    if (w == 4) { out.swap(ids32); return 0; }
-    CK(out.alloc(n * w));
-    const dim3 grid(bft_grid_for((n + 255) / 256)), block(256);
-    if (n) {
-        if (w == 1) hipLaunchKernelGGL(k_narrow_ids<uint8_t>, grid, block, 0, s, ids32.as<uint32_t>(), n, out.as<uint8_t>());
-        else hipLaunchKernelGGL(k_narrow_ids<uint16_t>, grid, block, 0, s, ids32.as<uint32_t>(), n, out.as<uint16_t>());
-        HIPCK(hipGetLastError());
-        HIPCK(hipStreamSynchronize(s));
-    }
-    return 0;
-}
-// the resident dictionary as u32 (a transient of the merge); w == 4: `src` itself
-static int widen_ids(const DevBuf& src, uint64_t n, uint32_t w, hipStream_t s, DevBuf& tmp, const uint32_t** out) {
-    if (w == 4) { *out = src.as<uint32_t>(); return 0; }
-    CK(tmp.alloc(n * 4));
-    const dim3 grid(bft_grid_for((n + 255) / 256)), block(256);
-    if (n) {
-        if (w == 1) hipLaunchKernelGGL(k_widen_ids<uint8_t>, grid, block, 0, s, src.as<uint8_t>(), n, tmp.as<uint32_t>());
-        else hipLaunchKernelGGL(k_widen_ids<uint16_t>, grid, block, 0, s, src.as<uint16_t>(), n, tmp.as<uint32_t>());
-        HIPCK(hipGetLastError());
-    }
-    *out = tmp.as<uint32_t>();
-    return 0;
-}
-
-// The colour-set dictionary lives in HBM; only bft_gpu_colorset and bft_gpu_write_bft need it on the host.
-static int host_colorsets(bft_gpu* h) {
-    if (h->cs_on_host) return 0;
-    h->cs_off.assign(h->n_sets + 1, 0);
-    h->cs_ids.assign(h->n_ids, 0);
-    HIPCK(hipMemcpy(h->cs_off.data(), h->d_cs_off.p, (h->n_sets + 1) * 4, hipMemcpyDeviceToHost));
-    if (h->n_ids) {
-        if (h->cs_w == 4) HIPCK(hipMemcpy(h->cs_ids.data(), h->d_cs_ids.p, h->n_ids * 4, hipMemcpyDeviceToHost));
-        else {
-            std::vector<uint8_t> raw(h->n_ids * h->cs_w);
-            HIPCK(hipMemcpy(raw.data(), h->d_cs_ids.p, raw.size(), hipMemcpyDeviceToHost));
-            for (uint64_t i = 0; i < h->n_ids; i++) h->cs_ids[i] = h->cs_w == 1 ? raw[i] : ((const uint16_t*)raw.data())[i];
-        }
-    }
-    h->cs_on_host = true;
-    return 0;
-}
-
 StageScope::StageScope(bft_gpu* hh, hipStream_t s) : h(hh) {
     t_stages_on = h->opt_build_stages;
     t_stage_marks.clear();
@@ -639,7 +575,6 @@ StageScope::~StageScope() {
 int bft_commit_image(bft_gpu* h, BftRunOut& img, uint64_t np, double t0, double t1, BftBuildSide* side) {
     // (a caller that neither interned nor prepared the k-mer hash: nothing prepared, nothing pending)
     if (!side) { BftBuildSide none; return bft_commit_image(h, img, np, t0, t1, &none); }
-    const int W = h->W;
     KhFill& khf = side->khf;
     BftInternTail& tail = side->tail;
     const uint64_t nk = img.n;
@@ -680,14 +615,14 @@ int bft_commit_image(bft_gpu* h, BftRunOut& img, uint64_t np, double t0, double 
         side->lists.seg_off.release();
         side->lists.ids.release();
     }
-    const uint32_t new_cs_w = id_width(h->max_gid_seen);
+    const uint32_t new_cs_w = bft_id_width(h->max_gid_seen);
     DevBuf n_cs_ids_w;
     bool narrowed_here = false;
     if (!kh_redo && tail.narrow.p && tail.narrow_w == new_cs_w) {  // (done by the interning's tail on the side stream)
         n_cs_ids_w.swap(tail.narrow);
         img.cs_ids.release();
     } else {
-        CK(narrow_ids(img.cs_ids, img.n_ids, new_cs_w, h->stream, n_cs_ids_w));
+        CK(bft_narrow_ids(img.cs_ids, img.n_ids, new_cs_w, h->stream, n_cs_ids_w));
         narrowed_here = new_cs_w < 4;
     }
     CK(bft_wait_foreign_stream(h));  // queries a caller still has in flight on its own stream read the arrays released below
@@ -703,9 +638,12 @@ int bft_commit_image(bft_gpu* h, BftRunOut& img, uint64_t np, double t0, double 
     }
 
     // ---- commit: nothing above touched the handle; from here on nothing can fail before the image is whole ----
-    h->d_tcol.swap(img.tcol);
-    h->d_cs_off.swap(img.cs_off);
-    h->d_cs_ids.swap(n_cs_ids_w);
+    {   // the stored arrays (bft_stored.h), in their order: the containers of the assembly, the table and the dictionary of img, the narrowed ids
+        DevBuf* const fresh[BFT_N_STORED] = {&idx.nodes, &idx.bfT, &idx.ccs, &idx.f2w, &idx.clus, &idx.child, &idx.uck, &idx.ucrow,
+                                             &img.tk, &img.tcol, &img.cs_off, &n_cs_ids_w};
+        const BftStoredRows st = bft_stored_rows(h);
+        for (int i = 0; i < BFT_N_STORED; i++) st.row[i].buf->swap(*fresh[i]);
+    }
     h->cs_w = new_cs_w;
     h->n_sets = img.n_sets;
     h->n_ids = img.n_ids;
@@ -720,15 +658,6 @@ int bft_commit_image(bft_gpu* h, BftRunOut& img, uint64_t np, double t0, double 
     h->log_k.release();
     h->log_g.release();
     h->log_cap = 0;
-    h->d_nodes.swap(idx.nodes);
-    h->d_bfT.swap(idx.bfT);
-    h->d_ccs.swap(idx.ccs);
-    h->d_f2w.swap(idx.f2w);
-    h->d_clus.swap(idx.clus);
-    h->d_child.swap(idx.child);
-    h->d_uck.swap(idx.uck);
-    h->d_ucrow.swap(idx.ucrow);
-    h->d_tk.swap(img.tk);
     h->table_dropped = false;
     h->n_pairs = np;
     h->log_n = 0;
@@ -737,9 +666,7 @@ int bft_commit_image(bft_gpu* h, BftRunOut& img, uint64_t np, double t0, double 
     h->log_comp = false;
     h->log_g_sorted = true;
     h->n_kmers = nk;
-    h->idx_sizes[0] = idx.n_nodes * sizeof(BftNode); h->idx_sizes[1] = idx.n_bf8 * 8; h->idx_sizes[2] = idx.n_ccs * sizeof(BftCC);
-    h->idx_sizes[3] = idx.n_f2w * 8; h->idx_sizes[4] = idx.n_clus * 8; h->idx_sizes[5] = idx.n_child * 8;
-    h->idx_sizes[6] = idx.n_uc * (uint64_t)W * 8; h->idx_sizes[7] = idx.n_uc * 4; h->idx_sizes[8] = nk * (uint64_t)W * 8;
+    bft_set_idx_sizes(h, idx, nk);
     h->root_ncc = (uint32_t)idx.root_ncc;
     bft_point_image(h, std::max<uint32_t>((uint32_t)h->genomes.size(), h->any_insert ? h->max_gid_seen + 1 : 0));
     BftImage& im = h->im;
@@ -816,7 +743,7 @@ extern "C" int bft_gpu_build(bft_gpu* h) {
     // (the interning's tail -- dictionary copy + verification of every list -- goes to the second stream, idle until the k-mer hash build starts
     // behind the first level's table passes; its verdict is collected before the commit.  A merge reads the dictionary at once: not deferred.)
     side.tail.side = merging ? nullptr : h->stream2;
-    side.tail.narrow_w = id_width(h->max_gid_seen);  // (the tail also leaves the dictionary in the width the image keeps)
+    side.tail.narrow_w = bft_id_width(h->max_gid_seen);  // (the tail also leaves the dictionary in the width the image keeps)
     CK(bft_intern_colors_gpu(run.seg_off.as<uint32_t>(), run.ids.as<uint32_t>(), run.nk, run.np, h->stream, img.tcol, img.cs_off, img.cs_ids, img.n_sets, img.n_ids, 0, &side.tail));
     bft_trace_mark("colour sets interned");
     bft_stage("colour sets (rest)", 0, h->stream);
@@ -829,7 +756,7 @@ extern "C" int bft_gpu_build(bft_gpu* h) {
     if (merging) {
         DevBuf wide;
         const uint32_t* old_ids = nullptr;
-        CK(widen_ids(h->d_cs_ids, h->n_ids, h->cs_w, h->stream, wide, &old_ids));
+        CK(bft_dict_ids32(h, 0u, h->stream, nullptr, wide, &old_ids));  // (the resident dictionary as u32: a transient of the merge)
         const BftRun old_run{h->d_tk.as<uint64_t>(), h->d_tcol.as<uint32_t>(), h->n_kmers, h->d_cs_off.as<uint32_t>(), old_ids, h->n_sets};
         const BftRun new_run{img.tk.as<uint64_t>(), img.tcol.as<uint32_t>(), img.n, img.cs_off.as<uint32_t>(), img.cs_ids.as<uint32_t>(), img.n_sets};
         BftRunOut mo;
@@ -846,286 +773,6 @@ int bft_ensure_built(bft_gpu* h, bool need_table) {
     if (!h->built || h->log_n) CK(bft_gpu_build(h));
     if (need_table) CK(bft_ensure_table(h));
     return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// .bft files
-// ------------------------------------------------------------------------------------------------
-extern "C" int bft_gpu_load_bft(const char* path, int device, bft_gpu** out) {
-    if (!path || !out) return fail(BFT_GPU_E_ARG, "NULL argument");
-    *out = nullptr;
-    DeviceScope ds_;
-    const double t_load0 = bft_now_ms();
-    BftFileContent fc;
-    std::string err;
-    try {  // sizes come from an untrusted file: an allocation failure is an I/O error of this call, not the end of the process
-        if (!bft_file_read(path, fc, err)) return fail(BFT_GPU_E_IO, err);
-    } catch (const std::bad_alloc&) {
-        return fail(BFT_GPU_E_IO, "out of host memory while reading the .bft file (corrupt size field?)");
-    } catch (const std::exception& e) {
-        return fail(BFT_GPU_E_IO, std::string("malformed .bft file: ") + e.what());
-    }
-    bft_gpu* h = nullptr;
-    CK(bft_gpu_create_seeded(fc.k, device, fc.r1, fc.r2, &h));
-    int rc = 0;
-    for (const std::string& g : fc.genomes) h->genomes.push_back(g);
-    const size_t B = (size_t)h->B;
-    {   // the log for every pair of the file at once (it would otherwise grow by doubling: a copy and a synchronisation per step)
-        uint64_t pairs = 0;
-        for (const auto& v : fc.per_genome) pairs += v.size() / B;
-        if (pairs && pairs <= h->opt_flush_pairs && hipSetDevice(device) == hipSuccess) {
-            bft_pool_set_stream(device, h->stream);
-            (void)log_reserve(h, pairs);  // (a failure here only means the log grows as usual)
-        }
-    }
-    static const bool io_trace = getenv("BFT_GPU_TRACE_IO") != nullptr;
-    const double t_io0 = bft_now_ms();
-    if (io_trace) fprintf(stderr, "[bft_gpu io] %8.1f ms load: file decoded, handle created, log reserved\n", t_io0 - t_load0);
-    for (size_t g = 0; g < fc.per_genome.size() && rc == 0; g++)
-        if (!fc.per_genome[g].empty()) rc = bft_gpu_insert_kmers(h, fc.per_genome[g].data(), fc.per_genome[g].size() / B, (uint32_t)g);
-    if (io_trace) fprintf(stderr, "[bft_gpu io] %8.1f ms load: every genome's k-mers inserted (host batches)\n", bft_now_ms() - t_io0);
-    if (rc == 0) rc = bft_gpu_build(h);
-    if (io_trace) fprintf(stderr, "[bft_gpu io] %8.1f ms load: index built\n", bft_now_ms() - t_io0);
-    bft_dispose_async(fc);  // (the decoded k-mers of every genome)
-    if (rc != 0) {
-        const std::string keep = g_err;
-        bft_gpu_free(h);
-        return fail(rc, keep);
-    }
-    *out = h;
-    return BFT_GPU_OK;
-}
-
-template <class T, class A>
-static int download(const DevBuf& d, uint64_t bytes, std::vector<T, A>& v) {
-    v.resize(bytes / sizeof(T));
-    if (bytes) HIPCK(hipMemcpy(v.data(), d.p, bytes, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-extern "C" int bft_gpu_write_bft(bft_gpu* h, const char* path) {
-    if (!h || !path) return fail(BFT_GPU_E_ARG, "NULL argument");
-    if (!bft_reference_k(h->k)) return fail(BFT_GPU_E_ARG, "the .bft format requires k % 9 == 0 (reference src/main.c:61-63)");
-    ENTER(h);
-    static const bool io_trace = getenv("BFT_GPU_TRACE_IO") != nullptr;
-    const double t_io0 = bft_now_ms();
-    CK(bft_ensure_built(h));
-    if (io_trace) fprintf(stderr, "[bft_gpu io] %8.1f ms write: index built, sorted table resident\n", bft_now_ms() - t_io0);
-    BftHostImage hi;
-    hi.k = h->k;
-    hi.r1 = h->r1;
-    hi.r2 = h->r2;
-    hi.genomes = h->genomes;
-    while (hi.genomes.size() < h->im.nb_genomes) hi.genomes.push_back("genome_" + std::to_string(hi.genomes.size()));
-    CK(download(h->d_nodes, h->idx_sizes[0], hi.nodes));
-    CK(download(h->d_ccs, h->idx_sizes[2], hi.ccs));
-    CK(download(h->d_f2w, h->idx_sizes[3], hi.f2w));
-    CK(download(h->d_clus, h->idx_sizes[4], hi.clus));
-    CK(download(h->d_child, h->idx_sizes[5], hi.child));
-    CK(download(h->d_ucrow, h->idx_sizes[7], hi.ucrow));
-    CK(download(h->d_tk, h->idx_sizes[8], hi.tk));
-    CK(download(h->d_tcol, h->n_kmers * 4, hi.tcol));
-    {   // the dictionary: offsets as they are, the ids widened to 32 bits (resident in 1, 2 or 4 bytes) by a few host threads
-        CK(download(h->d_cs_off, (h->n_sets + 1) * 4, hi.cs_off));
-        hi.cs_ids.resize(h->n_ids);
-        if (h->cs_w == 4) {
-            if (h->n_ids) HIPCK(hipMemcpy(hi.cs_ids.data(), h->d_cs_ids.p, h->n_ids * 4, hipMemcpyDeviceToHost));
-        } else if (h->n_ids) {
-            BftBigVec<uint8_t> raw;
-            raw.resize(h->n_ids * h->cs_w);
-            HIPCK(hipMemcpy(raw.data(), h->d_cs_ids.p, raw.size(), hipMemcpyDeviceToHost));
-            const unsigned nt = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-            const uint64_t per = (h->n_ids + nt - 1) / nt;
-            const uint32_t w = h->cs_w;
-            uint32_t* dst = hi.cs_ids.data();
-            auto widen = [&raw, dst, w](uint64_t a, uint64_t b) {
-                if (w == 1) for (uint64_t i = a; i < b; i++) dst[i] = raw[i];
-                else { const uint16_t* r16 = (const uint16_t*)raw.data(); for (uint64_t i = a; i < b; i++) dst[i] = r16[i]; }
-            };
-            std::vector<std::thread> th;
-            for (unsigned t = 1; t < nt; t++) {
-                const uint64_t a = std::min<uint64_t>(h->n_ids, t * per), b = std::min<uint64_t>(h->n_ids, a + per);
-                if (a >= b) break;
-                try { th.emplace_back(widen, a, b); } catch (...) { widen(a, b); }
-            }
-            widen(0, std::min<uint64_t>(h->n_ids, per));
-            for (std::thread& x : th) x.join();
-        }
-    }
-    if (io_trace) fprintf(stderr, "[bft_gpu io] %8.1f ms write: image arrays on the host\n", bft_now_ms() - t_io0);
-    std::string err;
-    try {
-        if (!bft_file_write(path, hi, err)) return fail(BFT_GPU_E_IO, err);
-    } catch (const std::bad_alloc&) {
-        return fail(BFT_GPU_E_LIMIT, "out of host memory while serialising the index");
-    } catch (const std::exception& e) {
-        return fail(BFT_GPU_E_IO, std::string("write_BFT: ") + e.what());
-    }
-    if (io_trace) fprintf(stderr, "[bft_gpu io] %8.1f ms write: file written and closed\n", bft_now_ms() - t_io0);
-    bft_dispose_async(hi);  // (the host copy of the image: gigabytes of vectors)
-    return BFT_GPU_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// image replication (one contiguous device blob: header, then 256-byte aligned sections)
-// ------------------------------------------------------------------------------------------------
-namespace {
-constexpr uint64_t BLOB_MAGIC = 0x3430555047544642ull;  // "BFTGPU04"
-constexpr int BLOB_HDR_WORDS = 64, BLOB_SECTIONS = 13;
-enum { H_MAGIC, H_TOTAL, H_K, H_R1, H_R2, H_NKMERS, H_NPAIRS, H_NSETS, H_NIDS, H_ROOTNCC, H_MAXGID, H_ANYINS, H_NBGEN, H_NNAMES,
-       H_CSW, H_STOREANY, H_INFO = 16, H_IDX = 32, H_SEC = 41 };
-
-struct BlobPlan {
-    uint64_t hdr[BLOB_HDR_WORDS];
-    uint64_t off[BLOB_SECTIONS];
-    const void* src[BLOB_SECTIONS];
-    std::string names;
-};
-
-inline uint64_t align256(uint64_t v) { return (v + 255ull) & ~255ull; }
-
-void plan_blob(bft_gpu* h, BlobPlan& p) {
-    memset(p.hdr, 0, sizeof(p.hdr));
-    p.names.clear();
-    for (const std::string& g : h->genomes) { p.names += g; p.names.push_back('\0'); }
-    const uint64_t sz[BLOB_SECTIONS] = {h->idx_sizes[0], h->idx_sizes[1], h->idx_sizes[2], h->idx_sizes[3], h->idx_sizes[4], h->idx_sizes[5], h->idx_sizes[6],
-                                        h->idx_sizes[7], h->idx_sizes[8], h->n_kmers * 4, (h->n_sets + 1) * 4, h->n_ids * (uint64_t)h->cs_w,
-                                        p.names.size()};
-    const void* src[BLOB_SECTIONS] = {h->d_nodes.p, h->d_bfT.p, h->d_ccs.p, h->d_f2w.p, h->d_clus.p, h->d_child.p, h->d_uck.p, h->d_ucrow.p,
-                                      h->d_tk.p, h->d_tcol.p, h->d_cs_off.p, h->d_cs_ids.p, nullptr};
-    uint64_t o = BLOB_HDR_WORDS * 8;
-    for (int i = 0; i < BLOB_SECTIONS; i++) {
-        p.off[i] = o;
-        p.src[i] = src[i];
-        p.hdr[H_SEC + i] = sz[i];
-        o = align256(o + sz[i]);
-    }
-    uint64_t* H = p.hdr;
-    H[H_MAGIC] = BLOB_MAGIC; H[H_TOTAL] = o; H[H_K] = h->k; H[H_R1] = h->r1; H[H_R2] = h->r2; H[H_NKMERS] = h->n_kmers; H[H_NPAIRS] = h->n_pairs;
-    H[H_NSETS] = h->n_sets; H[H_NIDS] = h->n_ids; H[H_ROOTNCC] = h->root_ncc; H[H_MAXGID] = h->max_gid_seen; H[H_ANYINS] = h->any_insert;
-    H[H_NBGEN] = h->im.nb_genomes; H[H_NNAMES] = h->genomes.size(); H[H_CSW] = h->cs_w;  // (word 14: bytes per dictionary id)
-    for (int i = 0; i < 16; i++) H[H_INFO + i] = h->info[i];
-    for (int i = 0; i < 9; i++) H[H_IDX + i] = h->idx_sizes[i];
-}
-}  // namespace
-
-extern "C" int bft_gpu_image_size(bft_gpu* h, uint64_t* nbytes) {
-    if (!h || !nbytes) return fail(BFT_GPU_E_ARG, "NULL argument");
-    ENTER(h);
-    CK(bft_ensure_built(h, false));
-    BlobPlan p;
-    plan_blob(h, p);
-    *nbytes = p.hdr[H_TOTAL];
-    return BFT_GPU_OK;
-}
-
-extern "C" int bft_gpu_image_pack(bft_gpu* h, void* d_blob, uint64_t cap, void* hip_stream) {
-    if (!h || !d_blob) return fail(BFT_GPU_E_ARG, "NULL argument");
-    ENTER(h);
-    CK(bft_ensure_built(h));
-    BlobPlan p;
-    plan_blob(h, p);
-    if (cap < p.hdr[H_TOTAL]) return fail(BFT_GPU_E_NOSPACE, "blob buffer too small");
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
-    uint8_t* d = (uint8_t*)d_blob;
-    HIPCK(hipMemcpyAsync(d, p.hdr, sizeof(p.hdr), hipMemcpyHostToDevice, s));
-    for (int i = 0; i < BLOB_SECTIONS; i++) {
-        const uint64_t n = p.hdr[H_SEC + i];
-        if (!n) continue;
-        if (i != 12) HIPCK(hipMemcpyAsync(d + p.off[i], p.src[i], n, hipMemcpyDeviceToDevice, s));
-        else HIPCK(hipMemcpyAsync(d + p.off[i], p.names.data(), n, hipMemcpyHostToDevice, s));  // section 12: the genome names (host)
-    }
-    HIPCK(hipStreamSynchronize(s));  // the header and the names are host temporaries
-    bft_drop_table(h);  // ("compact_table": ensure_built brought the sorted table back for the blob; the source is a group member like the others)
-    return BFT_GPU_OK;
-}
-
-extern "C" int bft_gpu_image_unpack(const void* d_blob, uint64_t nbytes, int device, bft_gpu** out) {
-    if (!d_blob || !out) return fail(BFT_GPU_E_ARG, "NULL argument");
-    *out = nullptr;
-    DeviceScope ds_;
-    if (nbytes < BLOB_HDR_WORDS * 8) return fail(BFT_GPU_E_ARG, "blob shorter than its header");
-    int ndev = 0;
-    HIPCK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(BFT_GPU_E_ARG, "bad device index");
-    HIPCK(hipSetDevice(device));
-    uint64_t H[BLOB_HDR_WORDS];
-    HIPCK(hipMemcpy(H, d_blob, sizeof(H), hipMemcpyDeviceToHost));
-    if (H[H_MAGIC] != BLOB_MAGIC) return fail(BFT_GPU_E_IO, "not a bft_gpu image blob");
-    if (H[H_TOTAL] > nbytes) return fail(BFT_GPU_E_IO, "truncated image blob");
-    uint64_t off[BLOB_SECTIONS], o = BLOB_HDR_WORDS * 8;
-    for (int i = 0; i < BLOB_SECTIONS; i++) {
-        off[i] = o;
-        if (H[H_SEC + i] > H[H_TOTAL] - o) return fail(BFT_GPU_E_IO, "image blob section out of range");
-        o = align256(o + H[H_SEC + i]);
-    }
-    bft_gpu* h = nullptr;
-    CK(bft_gpu_create_seeded((int)H[H_K], device, (int)H[H_R1], (int)H[H_R2], &h));
-    const uint8_t* d = (const uint8_t*)d_blob;
-    DevBuf* dst[BLOB_SECTIONS] = {&h->d_nodes, &h->d_bfT, &h->d_ccs, &h->d_f2w, &h->d_clus, &h->d_child, &h->d_uck, &h->d_ucrow,
-                                  &h->d_tk, &h->d_tcol, &h->d_cs_off, &h->d_cs_ids, nullptr};
-    int rc = 0;
-    for (int i = 0; i < BLOB_SECTIONS && rc == 0; i++) {
-        if (i == 12) continue;  // names: below
-        rc = dst[i]->alloc(H[H_SEC + i]);
-        if (rc == 0 && H[H_SEC + i] &&
-            hipMemcpyAsync(dst[i]->p, d + off[i], H[H_SEC + i], hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
-            rc = fail(BFT_GPU_E_HIP, "image blob copy failed");
-    }
-    std::string names(H[H_SEC + 12], '\0');
-    if (rc == 0 && !names.empty() && hipMemcpyAsync(&names[0], d + off[12], names.size(), hipMemcpyDeviceToHost, h->stream) != hipSuccess)
-        rc = fail(BFT_GPU_E_HIP, "image blob copy failed");
-    if (rc == 0 && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(BFT_GPU_E_HIP, "image blob copy failed");
-    if (rc == 0) {
-        size_t a = 0;
-        for (uint64_t i = 0; i < H[H_NNAMES] && a < names.size(); i++) {
-            const size_t e = names.find('\0', a);
-            h->genomes.push_back(names.substr(a, e == std::string::npos ? std::string::npos : e - a));
-            a = e == std::string::npos ? names.size() : e + 1;
-        }
-        h->n_kmers = H[H_NKMERS]; h->n_pairs = H[H_NPAIRS]; h->n_sets = H[H_NSETS]; h->n_ids = H[H_NIDS];
-        h->root_ncc = (uint32_t)H[H_ROOTNCC]; h->max_gid_seen = (uint32_t)H[H_MAXGID]; h->any_insert = H[H_ANYINS] != 0;
-        h->cs_w = (uint32_t)H[H_CSW];
-        if (h->cs_w != 1 && h->cs_w != 2 && h->cs_w != 4) rc = fail(BFT_GPU_E_IO, "image blob: bad dictionary id width");
-        for (int i = 0; i < 16; i++) h->info[i] = H[H_INFO + i];
-        for (int i = 0; i < 9; i++) h->idx_sizes[i] = H[H_IDX + i];
-        h->cs_on_host = false;
-        h->im.nb_genomes = (uint32_t)H[H_NBGEN];
-        // ("compact_table", the default: the replica's k-mer hash is derived from the blob's sorted table, which need not stay)
-        if (rc == 0) rc = bft_rederive(h, BFT_DERIVE_ALL);
-    }
-    if (rc != 0) {
-        const std::string keep = g_err;
-        bft_gpu_free(h);
-        return fail(rc, keep);
-    }
-    h->built = true;
-    h->claims.ensure();
-    *out = h;
-    return BFT_GPU_OK;
-}
-
-// Test hook (tests/test_gpu_build.py): raw copy of one index array of the image.
-extern "C" int bft_gpu_debug_get_array(bft_gpu* h, const char* name, void* out, uint64_t cap_bytes, uint64_t* nbytes) {
-    if (!h || !name) return fail(BFT_GPU_E_ARG, "NULL argument");
-    ENTER(h);
-    CK(bft_ensure_built(h));
-    static const char* names[16] = {"nodes", "bfT", "ccs", "f2w", "clus", "child", "uck", "ucrow", "tk", "ccx", "f18", "fent", "kh", "tcol", "kh_ovf_k", "kh_ovf_v"};
-    const DevBuf* bufs[16] = {&h->d_nodes, &h->d_bfT, &h->d_ccs, &h->d_f2w, &h->d_clus, &h->d_child, &h->d_uck, &h->d_ucrow, &h->d_tk,
-                              &h->d_ccx, &h->d_f18, &h->d_fent, &h->d_kh, &h->d_tcol, &h->d_kh_ovf_k, &h->d_kh_ovf_v};
-    const uint64_t derived[7] = {h->idx_sizes[2] / sizeof(BftCC) * sizeof(BftCCX), h->n_f18 * 8, h->n_fent * 8,
-                                 h->kh_lines ? (h->kh_lines + BFT_KH_TAIL_LINES) * BFT_KH_LINE_WORDS * 8 : 0ull, h->n_kmers * 4,
-                                 (uint64_t)h->kh_ovf_n * h->W * 8, (uint64_t)h->kh_ovf_n * 4};
-    for (int i = 0; i < 16; i++)
-        if (std::string(name) == names[i]) {
-            const uint64_t sz = i < 9 ? h->idx_sizes[i] : derived[i - 9];
-            if (nbytes) *nbytes = sz;
-            if (!out) return BFT_GPU_OK;
-            if (cap_bytes < sz) return fail(BFT_GPU_E_NOSPACE, "buffer too small");
-            if (sz) HIPCK(hipMemcpy(out, bufs[i]->p, sz, hipMemcpyDeviceToHost));
-            return BFT_GPU_OK;
-        }
-    return fail(BFT_GPU_E_ARG, "unknown array");
 }
 
 // Test hook (tests/test_colour_cases_host.py, tests/test_gpu_colour_retrieval.py): the tile and the division constants the colour-row kernels
@@ -1170,7 +817,7 @@ extern "C" int bft_gpu_set_option(bft_gpu* h, const char* name, int64_t value) {
         // batches never re-allocates it (a caller usually knows the total: line 2 of a kmers_comp file, README.md:166-170)
         if (value < 0 || (uint64_t)value > h->opt_flush_pairs) return fail(BFT_GPU_E_ARG, "reserve_pairs must be in [0, flush_pairs]");
         ENTER(h);
-        CK(log_reserve(h, (uint64_t)value));
+        CK(bft_log_reserve(h, (uint64_t)value));
     } else if (nm == "ingest_chunk_chars") {  // characters per staged chunk of bft_gpu_insert_sequences' stream path (default 2^26; a test hook below that)
         if (value < (int64_t)BFT_ING_CHUNK_MIN || value > (1ll << 30)) return fail(BFT_GPU_E_ARG, "ingest_chunk_chars must be in [1024, 2^30]");
         h->opt_ingest_chunk = (uint64_t)value;
@@ -1288,11 +935,14 @@ extern "C" int bft_gpu_info(bft_gpu* h, uint64_t* out, int n_out) {
 
 extern "C" int bft_gpu_footprint(bft_gpu* h, uint64_t* out, int n_out) {
     if (!h || !out) return fail(BFT_GPU_E_ARG, "NULL argument");
-    const uint64_t v[12] = {h->d_tk.bytes, h->d_tcol.bytes, h->d_cs_off.bytes + h->d_cs_ids.bytes,
-                            h->d_nodes.bytes + h->d_bfT.bytes + h->d_ccs.bytes + h->d_f2w.bytes + h->d_clus.bytes + h->d_child.bytes + h->d_uck.bytes + h->d_ucrow.bytes,
-                            h->d_ccx.bytes + h->d_f18.bytes + h->d_fent.bytes, h->d_rdir.bytes + h->d_rstart.bytes + h->d_rq.bytes, h->d_nph.bytes, h->d_kh.bytes + h->d_rspec.bytes + h->d_kh_ovf_k.bytes + h->d_kh_ovf_v.bytes, h->d_cs_bm.bytes,
-                            h->d_hashmod.bytes, 0ull, h->log_k.bytes + h->log_g.bytes};
-    for (int i = 0; i < n_out && i < 12; i++) out[i] = v[i];
+    const BftStoredRows st = bft_stored_rows(h);
+    const BftDerivedRows dv = bft_derived_rows(h);
+    // table, colour set per k-mer, dictionary, containers; flat forms, root tables, node prefix hash, k-mer hash, bitmap dictionary; the rest
+    const uint64_t v[] = {bft_rows_resident(st.row, BFT_S_TK, BFT_S_TCOL), bft_rows_resident(st.row, BFT_S_TCOL, BFT_S_CS_OFF), bft_rows_resident(st.row, BFT_S_CS_OFF, BFT_N_STORED),
+                          bft_rows_resident(st.row, 0, BFT_S_TK), bft_rows_resident(dv.row, BFT_D_CCX, BFT_D_RDIR), bft_rows_resident(dv.row, BFT_D_RDIR, BFT_D_NPH),
+                          bft_rows_resident(dv.row, BFT_D_NPH, BFT_D_KH), bft_rows_resident(dv.row, BFT_D_KH, BFT_D_CS_BM), bft_rows_resident(dv.row, BFT_D_CS_BM, BFT_N_DERIVED),
+                          h->d_hashmod.bytes, 0ull, h->log_k.bytes + h->log_g.bytes};
+    for (int i = 0; i < n_out && i < (int)(sizeof(v) / sizeof(v[0])); i++) out[i] = v[i];
     return BFT_GPU_OK;
 }
 
@@ -1337,86 +987,8 @@ extern "C" int bft_gpu_build_stages(bft_gpu* h, char* names, uint32_t names_cap,
     return BFT_GPU_OK;
 }
 
-// stored T-form rows -> packed k-mers (the reference's layout), on the GPU: bft_gpu_extract copies bytes, not keys
-template <int W>
-__global__ void k_tform_to_packed(const uint64_t* __restrict__ tk, uint64_t n, int k, int B, uint8_t* __restrict__ out) {
-    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        uint64_t t[W], x[W];
-#pragma unroll
-        for (int w = 0; w < W; w++) t[w] = tk[i * W + w];
-        bft_x_from_tform<W>(t, k, x);
-        for (int b = 0; b < B; b++) {
-            uint64_t v = 0;
-#pragma unroll
-            for (int w = 0; w < W; w++)
-                if (w == (b >> 3)) v = x[w];
-            out[i * B + b] = (uint8_t)(v >> (8 * (b & 7)));
-        }
-    }
-}
-
-extern "C" int bft_gpu_extract(bft_gpu* h, uint8_t* kmers_out, uint32_t* colorset_out, uint64_t cap, uint64_t* n_out) {
-    if (!h) return fail(BFT_GPU_E_ARG, "NULL handle");
-    ENTER(h);
-    CK(bft_ensure_built(h));
-    if (n_out) *n_out = h->n_kmers;
-    if (!kmers_out && !colorset_out) return BFT_GPU_OK;
-    if (cap < h->n_kmers) return fail(BFT_GPU_E_NOSPACE, "extract buffer too small");
-    const uint64_t n = h->n_kmers;
-    if (kmers_out && n) {
-        DevBuf packed;
-        CK(packed.alloc(n * h->B));
-        const dim3 grid(bft_grid_for((n + 255) / 256)), block(256);
-        switch (h->W) {
-        case 1: hipLaunchKernelGGL(k_tform_to_packed<1>, grid, block, 0, h->stream, h->d_tk.as<uint64_t>(), n, h->k, h->B, packed.as<uint8_t>()); break;
-        case 2: hipLaunchKernelGGL(k_tform_to_packed<2>, grid, block, 0, h->stream, h->d_tk.as<uint64_t>(), n, h->k, h->B, packed.as<uint8_t>()); break;
-        case 3: hipLaunchKernelGGL(k_tform_to_packed<3>, grid, block, 0, h->stream, h->d_tk.as<uint64_t>(), n, h->k, h->B, packed.as<uint8_t>()); break;
-        default: hipLaunchKernelGGL(k_tform_to_packed<4>, grid, block, 0, h->stream, h->d_tk.as<uint64_t>(), n, h->k, h->B, packed.as<uint8_t>()); break;
-        }
-        HIPCK(hipGetLastError());
-        HIPCK(hipMemcpyAsync(kmers_out, packed.p, n * h->B, hipMemcpyDeviceToHost, h->stream));
-        HIPCK(hipStreamSynchronize(h->stream));
-    }
-    if (colorset_out && n) HIPCK(hipMemcpy(colorset_out, h->d_tcol.p, n * 4, hipMemcpyDeviceToHost));
-    return BFT_GPU_OK;
-}
-
-extern "C" int bft_gpu_colorset(bft_gpu* h, uint32_t cs, uint32_t* ids, uint32_t cap, uint32_t* n_out) {
-    if (!h) return fail(BFT_GPU_E_ARG, "NULL handle");
-    ENTER(h);
-    CK(bft_ensure_built(h, false));
-    CK(host_colorsets(h));
-    if ((uint64_t)cs + 1 >= h->cs_off.size()) return fail(BFT_GPU_E_ARG, "unknown colour set");
-    const uint32_t a = h->cs_off[cs], b = h->cs_off[cs + 1];
-    if (n_out) *n_out = b - a;
-    if (ids) {
-        if (cap < b - a) return fail(BFT_GPU_E_NOSPACE, "ids buffer too small");
-        memcpy(ids, &h->cs_ids[a], (size_t)(b - a) * 4);
-    }
-    return BFT_GPU_OK;
-}
-
 bool bft_stream_capturing(hipStream_t s) {
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
     return st != hipStreamCaptureStatusNone;
-}
-
-// The colour set `cs` in the reference's annotation bytes (smallest of modes 0/1/2, compute_best_mode,
-// src/annotation.c:634-650) -- what get_annotation hands out as BFT_annotation::annot (src/bft.c:363-387).
-extern "C" int bft_gpu_colorset_annot(bft_gpu* h, uint32_t cs, uint8_t* annot, uint32_t cap, uint32_t* n_out) {
-    if (!h) return fail(BFT_GPU_E_ARG, "NULL handle");
-    ENTER(h);
-    CK(bft_ensure_built(h, false));
-    CK(host_colorsets(h));
-    if ((uint64_t)cs + 1 >= h->cs_off.size()) return fail(BFT_GPU_E_ARG, "unknown colour set");
-    const uint32_t a = h->cs_off[cs], b = h->cs_off[cs + 1];
-    std::vector<uint8_t> enc;
-    bft_annot_encode(b > a ? &h->cs_ids[a] : nullptr, b - a, enc);
-    if (n_out) *n_out = (uint32_t)enc.size();
-    if (annot) {
-        if (cap < enc.size()) return fail(BFT_GPU_E_NOSPACE, "annotation buffer too small");
-        memcpy(annot, enc.data(), enc.size());
-    }
-    return BFT_GPU_OK;
 }

@@ -1,5 +1,6 @@
 // bft_handle.h -- the handle behind the C-ABI (struct bft_gpu) and the host helpers every entry point needs, for the translation units that hold
-// entry points: bft_gpu.hip (lifecycle, pool, log, build and commit, files, the blob, options and info: it defines the helpers), bft_derive.hip (what the
+// entry points: bft_gpu.hip (lifecycle, pool, log, build and commit, options and info: it defines the helpers), bft_image_io.hip (the image read out and
+// in: .bft files, the blob, the read-outs, the width of the dictionary's ids; over the tables of bft_stored.h), bft_derive.hip (what the
 // handle derives from a committed image, bft_derive.h: root tables, k-mer hash, node prefix hash, launch shape, compact table), bft_query.hip (the k-mer and
 // sequence queries, their tuner, the claim slots), bft_run.hip (the build's run stage, the sort and scan test hooks) and the analysis families
 // bft_prefix.hip, bft_paths.hip, bft_components.hip, bft_pangenome.hip, bft_subgraph.hip, bft_marking.hip, bft_setops.hip, bft_union.hip, bft_ingest.hip.
@@ -208,7 +209,7 @@ struct bft_gpu {
     struct ExtEv { hipStream_t stream; hipEvent_t ev; bool pending; };
     std::vector<ExtEv> ext;  // one event per caller stream seen (a double-buffered caller alternates between two: neither call blocks the host)
     uint32_t root_ncc = 0;
-    uint64_t idx_sizes[9] = {0};
+    uint64_t idx_sizes[9] = {0};  // true bytes of the container arrays and the sorted table (BFT_N_INDEX, bft_stored.h)
     // The container walk (k_query*): how it sits on a CU and how it probes suffix groups.  0 = by rule from the shape of the index
     // (default_launch_shape), or -- after bft_gpu_set_option("tune", 1) -- as measured on the image (bft_tune_residency).
     int opt_wgs_per_cu = 0;   // 1 / 2 workgroups of 1024 threads per CU, 3 = two of 768
@@ -272,6 +273,8 @@ struct bft_gpu {
     std::vector<Stage> stages;          // of the last build
 };
 
+#include "bft_stored.h"  // the handle's stored and derived arrays as tables
+
 // Every ABI call makes the handle's GPU current; the caller's current device is put back when the call returns.
 int bft_set_device(bft_gpu* h);
 struct DeviceScope {
@@ -295,6 +298,7 @@ int bft_ensure_built(bft_gpu* h, bool need_table = true);
 // writes enqueued (s: a caller's stream they run on, or null for the handle's), bft_log_commit does the bookkeeping of bft_gpu_insert_kmers_dev.
 int bft_log_prepare(bft_gpu* h, uint64_t n, uint32_t id_genome);
 int bft_log_commit(bft_gpu* h, uint64_t n, uint32_t id_genome, hipStream_t s);
+int bft_log_reserve(bft_gpu* h, uint64_t need);  // room for `need` rows in all (an empty log's format is decided here); the log may move: synchronises
 // The bitmap form of the colour-set dictionary (d_cs_bm: one dword-aligned row per set behind CS_BM_SLACK zero bytes), derived on the first call per
 // image on the handle's stream (synchronises once); has_cs_bm stays false where it would pass 4 GiB or "test_no_cs_bitmaps" is set.
 #define CS_BM_SLACK 32u  // zero bytes in front of and behind the bitmap dictionary
@@ -319,6 +323,16 @@ struct StageScope {
     explicit StageScope(bft_gpu* hh, hipStream_t s = nullptr);  // (s: the stream the first stage runs on, when not the handle's)
     ~StageScope();
 };
+
+// ---- bft_image_io.hip: the width of the dictionary's genome ids (bft_gpu::cs_w bytes each, resident; 32 bits everywhere else) ----
+uint32_t bft_id_width(uint32_t max_gid);  // the narrowest of 1 / 2 / 4 bytes that holds every id up to max_gid
+// ids32 (n u32) -> out in width w, synchronised; w == 4: the buffers are swapped
+int bft_narrow_ids(DevBuf& ids32, uint64_t n, uint32_t w, hipStream_t s, DevBuf& out);
+// h's dictionary as 32-bit ids + base, enqueued on s (k_un_shift, bft_union.hip; timed on `timed` when not null).  *ids: the resident array itself
+// where that is what it holds (cs_w == 4, no base), else `tmp`, allocated here; ids null: always into `tmp` (the caller wants a copy of its own).
+int bft_dict_ids32(const bft_gpu* h, uint32_t base, hipStream_t s, bft_gpu* timed, DevBuf& tmp, const uint32_t** ids);
+// ... and on the host, widened by a few threads: out holds n_ids of them (the caller's own vector: no second copy of a multi-gigabyte dictionary)
+int bft_fetch_ids32(bft_gpu* h, uint32_t* out);
 
 // ---- bft_query.hip ----
 // rows per probe block of the suffix-group search ("query_probe": 4 or 8) -> BftImage::probe_big

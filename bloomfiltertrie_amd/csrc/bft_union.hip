@@ -287,11 +287,10 @@ int copy_side(const bft_gpu* src, uint32_t base, bft_gpu* timed, hipStream_t ds,
     CK(mo.tk.alloc(n * src->W * 8));
     CK(mo.tcol.alloc(n * 4));
     CK(mo.cs_off.alloc((src->n_sets + 1) * 4));
-    CK(mo.cs_ids.alloc(std::max<uint64_t>(1, src->n_ids) * 4));
     HIPCK(hipMemcpyAsync(mo.tk.p, src->d_tk.p, n * src->W * 8, hipMemcpyDeviceToDevice, ds));
     HIPCK(hipMemcpyAsync(mo.tcol.p, src->d_tcol.p, n * 4, hipMemcpyDeviceToDevice, ds));
     HIPCK(hipMemcpyAsync(mo.cs_off.p, src->d_cs_off.p, (src->n_sets + 1) * 4, hipMemcpyDeviceToDevice, ds));
-    CK(un_launch(timed, ds, [&] { return bft_union_shift_ids(src->d_cs_ids.p, src->cs_w, src->n_ids, base, mo.cs_ids.as<uint32_t>(), ds); }));
+    CK(bft_dict_ids32(src, base, ds, timed, mo.cs_ids, nullptr));  // (a copy of the merged image's own, whatever the width)
     mo.n = n;
     mo.n_sets = src->n_sets;
     mo.n_ids = src->n_ids;
@@ -323,18 +322,9 @@ int merge_fill(bft_gpu* a, bft_gpu* b, uint32_t id_base, bft_gpu* d) {
     BftRunOut mo;
     if (n_a && n_b) {
         DevBuf ids_a, ids_b;
-        const uint32_t* a_ids = a->d_cs_ids.as<uint32_t>();
-        if (a->cs_w != 4) {
-            CK(ids_a.alloc(std::max<uint64_t>(1, a->n_ids) * 4));
-            CK(un_launch(a, ds, [&] { return bft_union_shift_ids(a->d_cs_ids.p, a->cs_w, a->n_ids, 0u, ids_a.as<uint32_t>(), ds); }));
-            a_ids = ids_a.as<uint32_t>();
-        }
-        const uint32_t* b_ids = b->d_cs_ids.as<uint32_t>();
-        if (b->cs_w != 4 || id_base) {
-            CK(ids_b.alloc(std::max<uint64_t>(1, b->n_ids) * 4));
-            CK(un_launch(a, ds, [&] { return bft_union_shift_ids(b->d_cs_ids.p, b->cs_w, b->n_ids, id_base, ids_b.as<uint32_t>(), ds); }));
-            b_ids = ids_b.as<uint32_t>();
-        }
+        const uint32_t *a_ids = nullptr, *b_ids = nullptr;
+        CK(bft_dict_ids32(a, 0u, ds, a, ids_a, &a_ids));
+        CK(bft_dict_ids32(b, id_base, ds, a, ids_b, &b_ids));
         const double moved = (a_ids != a->d_cs_ids.as<uint32_t>() ? (double)a->n_ids * (a->cs_w + 4) : 0.0) + (b_ids != b->d_cs_ids.as<uint32_t>() ? (double)b->n_ids * (b->cs_w + 4) : 0.0);
         bft_stage("merge: dictionaries widened, b's ids shifted", moved, ds);
         const BftRun run_a{a->d_tk.as<uint64_t>(), a->d_tcol.as<uint32_t>(), n_a, a->d_cs_off.as<uint32_t>(), a_ids, a->n_sets};

@@ -890,3 +890,116 @@ def test_ballot_ranks_in_the_device_wide_sort_build_the_same_image(k, ngen, glen
         assert (a[0][name] == b[0][name]).all(), name
     assert (a[1] == b[1]).all() and (a[2] == b[2]).all() and a[3] == b[3]
     assert (a[4] == b[4]).all() and all((x == y).all() for x, y in zip(a[5], b[5]))
+
+
+# ---- the stored image as the blob lays it out, the dictionary widened for a merge, the read-out names ---------------------------------------------
+INDEX_ARRAYS = ["nodes", "bfT", "ccs", "f2w", "clus", "child", "uck", "ucrow", "tk"]  # the blob's sections 0-8, in its order (format BFTGPU04, csrc/bft_image_io.hip)
+ID_DTYPE = {1: np.uint8, 2: np.uint16, 4: np.uint32}
+
+
+@pytest.mark.parametrize("cs_w,top_gid,n", [(1, None, 30000), (2, 300, 3000), (4, 70000, 3000)])
+def test_blob_layout_is_the_documented_one(cs_w, top_gid, n):
+    """The replication blob word by word and section by section: magic, size, the counts, the nine index sizes, the thirteen 256-byte aligned sections
+    in their order (nine index arrays, colour set per k-mer, dictionary offsets, dictionary ids in their resident width, genome names)."""
+    import torch
+    k, r1, r2 = 27, 12345, 6789
+    names = ["first.fa", "the second genome"]
+    g0 = _rk(n, k, 5)
+    g1 = np.concatenate([g0[:n // 3], _rk(n // 2, k, 6)])
+    t = BFT(k, r1=r1, r2=r2)
+    for nm in names:
+        t.add_genome(nm)
+    t.insert_kmers(g0, 0)
+    t.insert_kmers(g1, 1)
+    if top_gid is not None:
+        t.insert_kmers(g1[::3], top_gid)
+    t.build()
+    size = t.image_size()
+    blob = torch.zeros(size, dtype=torch.uint8, device="cuda:0")
+    t.image_pack(blob.data_ptr(), size)
+    host = blob.cpu().numpy()
+    del blob
+    H = host[:512].view(np.uint64)
+    info = t.info()
+    dictionary = [t.colorset(c) for c in range(info["colorsets"])]
+    n_ids = sum(len(ids) for ids in dictionary)
+    assert host[:8].tobytes() == b"BFTGPU04"
+    assert int(H[1]) == size
+    assert H[2:16].tolist() == [k, r1, r2, info["kmers"], info["pairs"], info["colorsets"], n_ids, info["root_ccs"], top_gid or 1, 1, info["genomes"],
+                                len(names), cs_w, 0]
+    index = {a: t.debug_array(a) for a in INDEX_ARRAYS}
+    sizes = [index[a].nbytes for a in INDEX_ARRAYS]
+    assert H[32:41].tolist() == sizes
+    names_blob = b"".join(nm.encode() + b"\0" for nm in names)
+    assert H[41:54].tolist() == sizes + [4 * info["kmers"], 4 * (info["colorsets"] + 1), n_ids * cs_w, len(names_blob)]
+    off, o = [], 512
+    for s in H[41:54].tolist():
+        off.append(o)
+        o = (o + s + 255) // 256 * 256
+    assert o == size
+    sec = lambda i: host[off[i]:off[i] + int(H[41 + i])]
+    assert (sec(8) == index["tk"]).all()
+    assert sec(11).view(ID_DTYPE[cs_w]).tolist() == [g for ids in dictionary for g in ids]
+    assert sec(10).view(np.uint32).tolist() == np.concatenate([[0], np.cumsum([len(ids) for ids in dictionary])]).tolist()
+    assert sec(12).tobytes() == names_blob
+    t.close()
+
+
+@pytest.mark.parametrize("cs_w,top_gid", [(1, 2), (2, 300), (4, 70000)])
+def test_insertions_merge_into_a_dictionary_of_every_width(cs_w, top_gid):
+    """A second build on a handle merges the new run into the index, whose dictionary -- resident in 1, 2 or 4 bytes per id -- is widened to 32 bits on
+    the way.  What the handle stores and the colour rows it answers with are the plain union of the two batches."""
+    k = 27
+    anc = S.random_genome(6000, 9)
+    gk = [S.distinct(S.kmers_of(S.mutate(anc, 0.03, 70 + i) if i else anc, k)) for i in range(4)]
+    first = [(gk[0], 0), (gk[1], 1), (gk[2][::2], top_gid)]
+    second = [(gk[2], top_gid), (gk[3], 1), (gk[0][::3], top_gid)]  # k-mers the index holds under the same and under other ids, and new ones
+    t = BFT(k)
+    truth = {}
+    for batch in (first, second):
+        for km, g in batch:
+            t.insert_kmers(km, g)
+            for row in km:
+                truth.setdefault(row.tobytes(), set()).add(g)
+        t.build()
+        info = t.info()
+        n_ids = sum(len(t.colorset(c)) for c in range(info["colorsets"]))
+        assert (t.footprint()["colorset_dictionary"] - 4 * (info["colorsets"] + 1)) // n_ids == cs_w
+    stored, _ = _colour_map(t)
+    assert stored == {kk: tuple(sorted(v)) for kk, v in truth.items()}
+    q = np.concatenate([km[::17] for km in gk] + [_rk(300, k, 8)])
+    bits, rows = t.query_color_rows(q)
+    present = S.from_bits(bits, len(q))
+    for i in range(len(q)):
+        want = truth.get(q[i].tobytes())
+        assert bool(present[i]) == (want is not None)
+        if want is not None:
+            assert np.flatnonzero(np.unpackbits(rows[i], bitorder="little")).tolist() == sorted(want)
+    t.close()
+
+
+def test_debug_get_array_answers_its_sixteen_names():
+    """Every array name of the read-out hook with the size its array has by the image's counts (csrc/bft_image.h: 16-byte nodes and CC headers, 32-byte
+    extended headers, 8-byte words, k-mer hash lines of 8 words with 256 lines of tail); an unknown name is an error."""
+    k = 63
+    W = 2
+    km = np.concatenate([_rk(30000, k, 3), S.low_entropy_kmers(20000, k, 16, seed=4, levels=2)])
+    t = BFT(k)
+    t.insert_kmers(km, 0)
+    t.insert_kmers(km[::2], 1)
+    t.build()
+    info, bt, fp = t.info(), t.build_time(), t.footprint()
+    got = {a: t.debug_array(a).nbytes for a in INDEX_ARRAYS + ["ccx", "f18", "fent", "kh", "tcol", "kh_ovf_k", "kh_ovf_v"]}
+    assert len(got) == 16
+    lines, ovf = int(bt["kmer_hash_lines"]), int(bt["kmer_hash_overflow"])
+    want = {"nodes": 16 * info["nodes"], "ccs": 16 * info["ccs"], "ccx": 32 * info["ccs"], "uck": 8 * W * info["uc_rows"], "ucrow": 4 * info["uc_rows"],
+            "tk": 8 * W * info["kmers"], "tcol": 4 * info["kmers"], "kh": (lines + 256) * 64 if lines else 0, "kh_ovf_k": 8 * W * ovf, "kh_ovf_v": 4 * ovf}
+    assert {a: got[a] for a in want} == want
+    for a in ("bfT", "f2w", "clus", "child", "f18", "fent"):  # whole 8-byte words, and no more than the blocks that hold them
+        assert got[a] % 8 == 0, a
+    assert got["bfT"] > 0 and got["f2w"] > 0 and got["clus"] > 0 and got["child"] > 0
+    assert sum(got[a] for a in INDEX_ARRAYS[:-1]) <= fp["containers"] and got["ccx"] + got["f18"] + got["fent"] <= fp["flat_ccs"]
+    assert (t.debug_array("tcol", np.uint32) == t.extract()[1]).all()
+    with pytest.raises(_lib.BFTError):
+        t.debug_array("no_such_array")
+    t.close()
