@@ -76,6 +76,10 @@ SIGNATURES = {
     "bft_gpu_kmers_by_count_dev": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_uint64, _P, _P]),
     "bft_gpu_pangenome_stats": (C.c_int, [_P, _P, _P, _P, C.c_uint32]),
     "bft_gpu_pangenome_stats_dev": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P]),
+    "bft_gpu_genome_matrix": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_uint32)]),
+    "bft_gpu_genome_matrix_dev": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.c_uint64, _P]),
+    "bft_gpu_genome_matrix_colorsets": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint32)]),
+    "bft_gpu_genome_matrix_colorsets_dev": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, _P]),
     "bft_gpu_combine_colors": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_int, C.c_int, _P, _P, _P]),
     "bft_gpu_combine_colors_dev": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_int, C.c_int, _P, _P, _P, _P]),
     "bft_gpu_combine_colorsets": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_int, _P, _P]),
@@ -121,6 +125,9 @@ SIGNATURES = {
 TEST_HOOKS = {
     # (d_seg_off, d_ids, nk, np, mode, narrow_w, distinct_hint, d_tcol, d_cs_off, cs_off_cap, d_cs_ids, cs_ids_cap, d_narrow, counts[5], hip_stream)
     "bft_gpu_test_intern": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, C.c_uint64, _P, _P, C.c_uint64, _P, C.c_uint64, _P, C.POINTER(C.c_uint64), _P]),
+    # csrc/bft_genome_matrix.hip; tests/test_gpu_genome_matrix.py: (h, d_weights, road, flush_sets, d_shared, cap, hip_stream) and (h, canary, out[2])
+    "bft_gpu_test_genome_matrix": (C.c_int, [_P, _P, C.c_int, C.c_uint32, _P, C.c_uint64, _P]),
+    "bft_gpu_test_genome_matrix_state": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint32)]),
 }
 
 

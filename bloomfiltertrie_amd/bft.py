@@ -492,6 +492,67 @@ class BFT:
         _lib.check(self._lib.bft_gpu_pangenome_stats_dev(self._h, C.c_void_p(d_spectrum_ptr or 0), C.c_void_p(d_genome_total_ptr or 0),
                                                          C.c_void_p(d_genome_private_ptr or 0), cap, C.c_void_p(stream or 0)))
 
+    # -- the genome-by-genome shared k-mer matrix (bft_gpu_genome_matrix*) and the distances computed from it ------------------------
+    def _genome_matrix(self, call):
+        g = C.c_uint32()
+        _lib.check(call(None, 0, C.byref(g)))
+        n = int(g.value)
+        shared = np.zeros((n, n), dtype=np.uint64)
+        _lib.check(call(shared.ctypes.data if n else None, n * n, C.byref(g)))
+        return shared
+
+    def genome_matrix(self, min_count=0, max_count=None):
+        """uint64 [G, G] (bft_gpu_genome_matrix): shared[i, j] = stored k-mers whose colour set holds both genome i and genome j, restricted to the
+        k-mers carried by min_count .. max_count genomes (None: no upper bound; 0, G - 1: the accessory genome).  Symmetric; the diagonal is
+        pangenome_stats()[1] when nothing is restricted.  Exact."""
+        lo, hi = int(min_count), 0xFFFFFFFF if max_count is None else int(max_count)
+        return self._genome_matrix(lambda out, cap, g: self._lib.bft_gpu_genome_matrix(self._h, lo, hi, out, cap, g))
+
+    def genome_matrix_colorsets(self, colorsets):
+        """uint64 [G, G] (bft_gpu_genome_matrix_colorsets): the same matrix over a batch of colour-set ids (of query_rows, query_prefixes or
+        extract), each id counted as often as it occurs; 0xFFFFFFFF (absent) is skipped, any other id past the dictionary raises."""
+        cs = np.ascontiguousarray(colorsets, dtype=np.uint32)
+        return self._genome_matrix(lambda out, cap, g: self._lib.bft_gpu_genome_matrix_colorsets(self._h, cs.ctypes.data if len(cs) else None, len(cs), out, cap, g))
+
+    def genome_matrix_dev(self, d_shared_ptr, cap, min_count=0, max_count=None, stream=None):
+        """Device-resident matrix (bft_gpu_genome_matrix_dev): G * G uint64 at d_shared_ptr (cap entries of room); no synchronisation."""
+        _lib.check(self._lib.bft_gpu_genome_matrix_dev(self._h, int(min_count), 0xFFFFFFFF if max_count is None else int(max_count), C.c_void_p(d_shared_ptr or 0),
+                                                       cap, C.c_void_p(stream or 0)))
+
+    def genome_matrix_colorsets_dev(self, d_colorsets_ptr, n, d_shared_ptr, cap, stream=None):
+        """Device-resident matrix over n colour-set ids (uint32) at d_colorsets_ptr (bft_gpu_genome_matrix_colorsets_dev): ids past the dictionary
+        are skipped; no synchronisation."""
+        _lib.check(self._lib.bft_gpu_genome_matrix_colorsets_dev(self._h, C.c_void_p(d_colorsets_ptr or 0), n, C.c_void_p(d_shared_ptr or 0), cap,
+                                                                 C.c_void_p(stream or 0)))
+
+    @staticmethod
+    def distances_from_matrix(shared, metric, k):
+        """float64 [G, G] from a shared k-mer matrix, S = shared[i, j], n_i = shared[i, i]: "jaccard" = S / (n_i + n_j - S), 0.0 for an empty
+        union; "containment"[i, j] = S / n_i, 0.0 for n_i = 0; "mash" = -ln(2 J / (1 + J)) / k, capped at 1.0 and 1.0 for J = 0."""
+        if metric not in ("jaccard", "containment", "mash"):
+            raise ValueError(f"unknown metric {metric!r}")
+        s = np.asarray(shared).astype(np.float64)
+        n = np.diag(s)
+        if metric == "containment":
+            den = np.repeat(n[:, None], len(n), axis=1)
+        else:
+            den = n[:, None] + n[None, :] - s
+        out = np.zeros_like(s)
+        np.divide(s, den, out=out, where=den > 0)
+        if metric == "mash":
+            j = out
+            out = np.ones_like(j)
+            pos = j > 0
+            out[pos] = np.minimum(1.0, -np.log(2.0 * j[pos] / (1.0 + j[pos])) / k)
+            out[out == 0] = 0.0  # (-0.0 for J = 1)
+        return out
+
+    def genome_distances(self, metric="jaccard", min_count=0, max_count=None):
+        """float64 [G, G] computed in numpy from genome_matrix(min_count, max_count): see distances_from_matrix."""
+        if metric not in ("jaccard", "containment", "mash"):
+            raise ValueError(f"unknown metric {metric!r}")
+        return self.distances_from_matrix(self.genome_matrix(min_count, max_count), metric, self.k)
+
     # -- colour-set algebra over groups (bft_gpu_combine_*: intersection / union / sym_difference of annotations, batched) -------
     SETOPS = {"and": 0, "or": 1, "symdiff": 2}
 

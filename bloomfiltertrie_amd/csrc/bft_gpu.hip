@@ -916,6 +916,9 @@ extern "C" int bft_gpu_set_option(bft_gpu* h, const char* name, int64_t value) {
     } else if (nm == "merge_place") {  // bft_gpu_merge(h, other, ...): 1 = co-ranked placement, 0 = the search of an insertion build (same image)
         if (value != 0 && value != 1) return fail(BFT_GPU_E_ARG, "merge_place must be 0 or 1");
         h->opt_merge_place = (int)value;
+    } else if (nm == "test_genome_matrix_road") {  // test hook (tests/test_gpu_genome_matrix.py): the road of bft_gpu_genome_matrix*: 0 = cost model, 1 = sparse, 2 = dense
+        if (value < 0 || value > 2) return fail(BFT_GPU_E_ARG, "test_genome_matrix_road must be 0, 1 or 2");
+        h->opt_gm_road = (int)value;
     } else if (nm == "flat_min") {
         if (value < 1 || value > 65536) return fail(BFT_GPU_E_ARG, "flat_min must be in [1,65536]");
         h->opt_flat_min = (uint32_t)value;

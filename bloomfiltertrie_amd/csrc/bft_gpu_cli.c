@@ -8,6 +8,7 @@
  *                         [-query_branching {kmers|kmers_comp} list_kmer_files]
  *                         [-query_sequences threshold {canonical|non_canonical} list_sequence_files]
  *                         [-extract_kmers {kmers|kmers_comp} output_file]
+ *                         [-genome_matrix {shared|jaccard|mash} output_file]
  *
  * It is the per-k-mer loops of src/file_io.c:89-213 (build), :651-895 (presence CSV) and :897-1020 (branching)
  * rewired to one batched GPU call per file; file reading, ASCII parsing (parseKmerCount, src/fasta.c:3-53) and CSV
@@ -18,9 +19,13 @@
  *   - stdout: "Nb k-mers present = <n>" (src/main.c:266), "Nb branching k-mers = <n>" (src/main.c:312).
  * An extension: with `sequences` / `sequences_canonical` the listed files are plain-text FASTA or four-line FASTQ and their k-mers are cut on the
  * GPU (bft_gpu_insert_sequence_file); -min_abundance N keeps the k-mers a file holds at least N times.
+ * Another: -genome_matrix writes the genome-by-genome shared k-mer matrix (bft_gpu_genome_matrix) as tab-separated text: a header line of the genome
+ * names behind an empty first cell, then one line per genome, its name and its row -- the counts (shared, %llu) or the distances computed from
+ * them (jaccard, mash: %.6f).
  */
 #define _GNU_SOURCE
 #include <libgen.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -303,6 +308,44 @@ static void extract_kmers(bft_gpu* h, const char* path, int k, int compressed) {
     free(km);
 }
 
+/* -genome_matrix: S = shared[i][j], n_i the diagonal; jaccard = S / (n_i + n_j - S), 0 for an empty union; mash = -ln(2 J / (1 + J)) / k, capped at
+ * 1 and 1 for J = 0 */
+static void genome_matrix(bft_gpu* h, const char* what, const char* path, int k, uint32_t nb_names, char** names) {
+    const int mode = strcmp(what, "shared") == 0 ? 0 : strcmp(what, "jaccard") == 0 ? 1 : strcmp(what, "mash") == 0 ? 2 : -1;
+    if (mode < 0) DIE("Unrecognized type of matrix for -genome_matrix: %s.\n", what);
+    uint32_t G = 0;
+    ck(bft_gpu_genome_matrix(h, 0, UINT32_MAX, NULL, 0, &G));
+    uint64_t* m = calloc((size_t)G * G + 1, 8);
+    ck(bft_gpu_genome_matrix(h, 0, UINT32_MAX, m, (uint64_t)G * G, &G));
+    FILE* f = fopen(path, "w");
+    if (!f) DIE("Cannot create %s\n", path);
+    for (uint32_t j = 0; j < G; j++) {
+        if (j < nb_names) fprintf(f, "\t%s", names[j]);
+        else fprintf(f, "\tgenome_%u", j);
+    }
+    fputc('\n', f);
+    for (uint32_t i = 0; i < G; i++) {
+        if (i < nb_names) fputs(names[i], f);
+        else fprintf(f, "genome_%u", i);
+        for (uint32_t j = 0; j < G; j++) {
+            const uint64_t s = m[(size_t)i * G + j];
+            if (mode == 0) { fprintf(f, "\t%llu", (unsigned long long)s); continue; }
+            const uint64_t un = m[(size_t)i * G + i] + m[(size_t)j * G + j] - s;
+            const double jac = un ? (double)s / (double)un : 0.0;
+            double d = jac;
+            if (mode == 2) {
+                d = jac > 0 ? -log(2.0 * jac / (1.0 + jac)) / k : 1.0;
+                if (d > 1.0) d = 1.0;
+                if (d <= 0) d = 0.0;
+            }
+            fprintf(f, "\t%.6f", d);
+        }
+        fputc('\n', f);
+    }
+    fclose(f);
+    free(m);
+}
+
 int main(int argc, char** argv) {
     if (argc >= 2 && (strcmp(argv[1], "--version") == 0 || strcmp(argv[1], "-v") == 0)) { /* src/main.c:51-55 */
         fprintf(stderr, "0.8 (%s)\n", bft_gpu_version());
@@ -315,7 +358,8 @@ int main(int argc, char** argv) {
             "[-query_kmers {kmers|kmers_comp} list_kmer_files]\n"
             "[-query_branching {kmers|kmers_comp} list_kmer_files]\n"
             "[-query_sequences threshold {canonical|non_canonical} list_sequence_files]\n"
-            "[-extract_kmers {kmers|kmers_comp} output_file]\n\n");
+            "[-extract_kmers {kmers|kmers_comp} output_file]\n"
+            "[-genome_matrix {shared|jaccard|mash} output_file]\n\n");
     bft_gpu* h = NULL;
     int k = 0, i = 0;
     char buffer[2048];
@@ -375,6 +419,7 @@ int main(int argc, char** argv) {
             i++;
             continue;
         }
+        if (strcmp(argv[i], "-genome_matrix") == 0) { genome_matrix(h, argv[i + 1], argv[i + 2], k, nb_genomes, names); continue; }
         const int binary = strcmp(argv[i + 1], "kmers_comp") == 0;
         if (!binary && strcmp(argv[i + 1], "kmers") != 0) DIE("Unrecognized type of input files for %s.\n", argv[i]);
         if (strcmp(argv[i], "-extract_kmers") == 0) { extract_kmers(h, argv[i + 2], k, binary); continue; }

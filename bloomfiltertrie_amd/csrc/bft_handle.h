@@ -3,7 +3,7 @@
 // in: .bft files, the blob, the read-outs, the width of the dictionary's ids; over the tables of bft_stored.h), bft_derive.hip (what the
 // handle derives from a committed image, bft_derive.h: root tables, k-mer hash, node prefix hash, launch shape, compact table), bft_query.hip (the k-mer and
 // sequence queries, their tuner, the claim slots), bft_run.hip (the build's run stage, the sort and scan test hooks) and the analysis families
-// bft_prefix.hip, bft_paths.hip, bft_components.hip, bft_pangenome.hip, bft_subgraph.hip, bft_marking.hip, bft_setops.hip, bft_union.hip, bft_ingest.hip.
+// bft_prefix.hip, bft_paths.hip, bft_components.hip, bft_pangenome.hip, bft_genome_matrix.hip, bft_subgraph.hip, bft_marking.hip, bft_setops.hip, bft_union.hip, bft_ingest.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -244,6 +244,10 @@ struct bft_gpu {
     HandleScratch pg{"k-mer classes"};
     DevBuf pg_buf, pg_tmp;           // pan-genome k-mer classes (BftPgScratch, bft_pangenome.h) and their scan's temporary
     uint64_t pg_m = 0, pg_sets = 0;  // rows and colour sets pg_buf has room for
+    HandleScratch gm{"genome matrix"};
+    DevBuf gm_buf, gm_bits;          // genome-by-genome matrix (BftGmScratch, bft_genome_matrix.h): usage / weights / digits / plan; the dense road's bit matrix
+    uint64_t gm_sets = 0;            // colour sets gm_buf has room for
+    int opt_gm_road = 0;             // test hook ("test_genome_matrix_road"): 0 = by the cost model, 1 = sparse, 2 = dense (same matrix)
     HandleScratch so{"colour-set algebra"};
     DevBuf so_buf;                   // set operations over groups (BftSoScratch, bft_setops.h): colour set per k-mer, presence bits, accumulators, split list
     HandleScratch ig{"sequence ingest"};
@@ -285,6 +289,11 @@ struct DeviceScope {
 #define ENTER(h)     \
     DeviceScope ds_; \
     CK(bft_set_device(h))
+
+// genomes added, one without k-mers included (graph->nb_genomes of the reference); ids inserted without a name count too
+static inline uint32_t bft_nb_genomes(const bft_gpu* h) {
+    return std::max<uint32_t>(std::max<uint32_t>((uint32_t)h->genomes.size(), h->im.nb_genomes), h->any_insert ? h->max_gid_seen + 1 : 0);
+}
 
 double bft_now_ms();
 bool bft_stream_capturing(hipStream_t s);

@@ -253,10 +253,7 @@ static int pg_prepare(bft_gpu* h) {
     if (h->n_kmers >= (1ull << 31)) return bft_fail(BFT_GPU_E_LIMIT, "k-mer classes: at most 2^31 - 1 k-mers");
     return 0;
 }
-// genomes added, one without k-mers included (graph->nb_genomes of the reference); ids inserted without a name count too
-static uint32_t pg_genomes(const bft_gpu* h) {
-    return std::max<uint32_t>(std::max<uint32_t>((uint32_t)h->genomes.size(), h->im.nb_genomes), h->any_insert ? h->max_gid_seen + 1 : 0);
-}
+static uint32_t pg_genomes(const bft_gpu* h) { return bft_nb_genomes(h); }  // (bft_handle.h: the genome-by-genome matrix counts them the same way)
 // The selection and its scan on stream s: slot[] filled, the number of selected rows at d_count (8 bytes, device).
 static int pg_select(bft_gpu* h, uint32_t lo, uint32_t hi, hipStream_t s, unsigned long long* d_count, const BftPgScratch& p) {
     const uint64_t n = h->n_kmers;

@@ -265,6 +265,7 @@ int bft_gpu_footprint(bft_gpu* h, uint64_t* out, int n_out);
  *   path: 2^26 by default, 1024..2^30; the result does not depend on it).
  * "test_no_cs_bitmaps" (test hook; 1: the bitmap form of the colour-set dictionary is not derived and one that exists is released -- what happens by itself where
  *   it would pass 4 GiB --, so the colour rows and bft_gpu_combine_* read the sorted id lists; 0: it is derived again by the next call that wants it; same answers).
+ * "test_genome_matrix_road" (test hook; the road of bft_gpu_genome_matrix*: 0 = the cost model, 1 = pair updates per colour set, 2 = the matrix cores; same matrix).
  * "timing" (0/1: record HIP events around query kernels; off until this option or the first bft_gpu_kernel_time call turns it on).
  * "build_stages" (0/1: bft_gpu_build records GPU time and algorithmic bytes per stage, see bft_gpu_build_stages). */
 int bft_gpu_set_option(bft_gpu* h, const char* name, int64_t value);
@@ -477,6 +478,33 @@ int bft_gpu_kmers_by_count_dev(bft_gpu* h, uint32_t min_count, uint32_t max_coun
 int bft_gpu_pangenome_stats(bft_gpu* h, uint64_t* spectrum, uint64_t* genome_total, uint64_t* genome_private, uint32_t cap);
 /* The same into device buffers (uint64) on hip_stream (NULL = the handle's stream), without host synchronisation.  Not inside a graph capture. */
 int bft_gpu_pangenome_stats_dev(bft_gpu* h, void* d_spectrum, void* d_genome_total, void* d_genome_private, uint32_t cap, void* hip_stream);
+
+/* The genome-by-genome shared k-mer matrix (an extension like <bft/ingest.h>: the reference has no counterpart): what Jaccard similarity, containment,
+ * Mash distance and a guide tree are computed from.  G = the number of genomes as bft_gpu_pangenome_stats counts them (a genome without k-mers
+ * counts, ids inserted without a name count).  shared is a full, symmetric, row-major G x G matrix of uint64: shared[i * G + j] = the stored k-mers
+ * whose colour set holds both i and j; the diagonal is genome_total of bft_gpu_pangenome_stats.  The results are exact: integer arithmetic only,
+ * independent of scheduling; no float is accumulated anywhere.  The work is one pass over the colour set of every row plus passes over the
+ * colour-set dictionary (M = B^T diag(usage) B), by one of two roads that agree bit for bit: pair updates per colour set, or 7-bit digits of the usage
+ * on the i8 matrix cores -- chosen on the device by a cost model, without synchronising ("test_genome_matrix_road" 1 / 2, a test hook of
+ * bft_gpu_set_option, forces the sparse / the dense one; 0 = the model).
+ * bft_gpu_genome_matrix restricts the matrix to the k-mers whose colour set holds min_count .. max_count genomes: 0, UINT32_MAX is everything; 0, G - 1
+ * the accessory genome (the core no longer drowns the signal); min_count > max_count gives all zeros.  cap = entries of room in shared; G * G are
+ * needed.  shared == NULL only sets *nb_genomes; a cap too small writes nothing and returns BFT_GPU_E_NOSPACE with *nb_genomes set.  The empty index
+ * and G = 0 succeed.  Pending insertions are built first ("compact_table": the sorted table comes back).  At most 2^31 - 1 k-mers and
+ * BFT_GPU_GENOME_MATRIX_MAX_GENOMES genomes (2 GiB of matrix): BFT_GPU_E_LIMIT beyond.  Launches are counted in bft_gpu_kernel_time; with
+ * "build_stages" on, the call's passes become the stages bft_gpu_build_stages reports. */
+#define BFT_GPU_GENOME_MATRIX_MAX_GENOMES 16384u
+int bft_gpu_genome_matrix(bft_gpu* h, uint32_t min_count, uint32_t max_count, uint64_t* shared, uint64_t cap, uint32_t* nb_genomes);
+/* The same into a device buffer (G * G uint64) on hip_stream (NULL = the handle's stream), without host synchronisation.  cap < G * G is
+ * BFT_GPU_E_NOSPACE (G is known on the host).  Scratch (about 13 bytes per colour set, and for the dense road G / 8 bytes per colour set) belongs to
+ * the handle and is shared with no other query family.  Not inside a graph capture (BFT_GPU_E_ARG). */
+int bft_gpu_genome_matrix_dev(bft_gpu* h, uint32_t min_count, uint32_t max_count, void* d_shared, uint64_t cap, void* hip_stream);
+/* The same matrix over a caller's batch of n colour-set ids, each id weighted by how often it occurs in the batch: the colorsets of
+ * bft_gpu_query_rows, the colorsets_out of bft_gpu_query_prefixes ("which genomes resemble each other over the k-mers under this prefix") or those of
+ * bft_gpu_extract (the whole-index matrix).  0xFFFFFFFF (absent) is skipped.  Any other id at or past the number of colour sets is BFT_GPU_E_ARG in
+ * the host form and is skipped in the _dev form.  n >= 2^31 is BFT_GPU_E_LIMIT.  The sorted table is not needed. */
+int bft_gpu_genome_matrix_colorsets(bft_gpu* h, const uint32_t* colorsets, uint64_t n, uint64_t* shared, uint64_t cap, uint32_t* nb_genomes);
+int bft_gpu_genome_matrix_colorsets_dev(bft_gpu* h, const void* d_colorsets, uint64_t n, void* d_shared, uint64_t cap, void* hip_stream);
 
 /* Colour-set algebra over groups of k-mers: intersection_annotations / union_annotations / sym_difference_annotations (reference include/bft.h:112-114,
  * src/bft.c:421-613) for a batch of groups, reduced on the GPU: one row per GROUP crosses to the caller, not one per k-mer (the route through
