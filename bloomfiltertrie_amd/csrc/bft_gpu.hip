@@ -898,6 +898,10 @@ extern "C" int bft_gpu_set_option(bft_gpu* h, const char* name, int64_t value) {
         if (value < 1 || value > 3) return fail(BFT_GPU_E_ARG, "test_stale_claims must be 1, 2 or 3");
         ENTER(h);
         CK(h->claims.stale((int)value));
+    } else if (nm == "test_walk_grid") {  // test hook (tests/test_gpu_walk_edges.py): the container walk's launches (k_query*, k_query6h, k_branching*) use
+        // at most this many workgroups, so that a batch of test size gives every wavefront several chunks (0: no cap); the claims are sized as ever
+        if (value < 0 || value > 65535) return fail(BFT_GPU_E_ARG, "test_walk_grid must be in [0,65535]");
+        h->opt_test_walk_grid = (uint32_t)value;
     } else if (nm == "test_no_cs_bitmaps") {  // test hook (tests/test_gpu_setops.py): the bitmap form of the dictionary is not derived (what happens by itself
         // where it would pass 4 GiB); one that exists is released, so the id lists serve the colour rows and the set operations from here on
         ENTER(h);

@@ -218,6 +218,7 @@ struct bft_gpu {
     int tuned_probe = 0;
     double tune_ms[3] = {0, 0, 0};  // best time of the tuning batch per residency 1 / 2 / 3
     int opt_grid_mult = 1;    // grid = resident workgroups x this
+    uint32_t opt_test_walk_grid = 0;  // test hook ("test_walk_grid"): the container walk's launches use at most this many workgroups (0: no cap)
     // The query kernels claim their blocks of k-mers from a counter per stream (ClaimSlots).  Batches too small to matter take the static split.
     int opt_query_dynamic = 1;
     uint64_t opt_query_dynamic_min = (uint64_t)1 << 16;  // batches below this many k-mers (lines of work for the branching kernel) keep the static split

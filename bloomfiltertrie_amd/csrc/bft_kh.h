@@ -44,4 +44,4 @@ int bft_kh_seq(const BftImage& im, const uint64_t* d_codes, const uint32_t* d_ba
 
 // bft_walkh.hip: the container walk with plain root groups looked up in the k-mer hash ("walk_hash"): presence bits (and colour sets when
 // im.emit_cs) of n k-mers of `rec` bytes; d_ctr: the stream's claim counters or NULL
-int bft_walkh_query(const BftImage& im, const uint8_t* d_kmers, uint64_t n, int rec, uint64_t* d_bits64, uint32_t* d_rows, BftClaimCtr d_ctr, uint32_t grid_mult, hipStream_t s);
+int bft_walkh_query(const BftImage& im, const uint8_t* d_kmers, uint64_t n, int rec, uint64_t* d_bits64, uint32_t* d_rows, BftClaimCtr d_ctr, uint32_t grid_mult, uint32_t grid_cap, hipStream_t s);

@@ -163,13 +163,14 @@ static int launch_walk(bft_gpu* h, const BftImage& im, const WalkShape& sh, cons
     // chunks of 1024 k-mers per wavefront (query_body): the first by wavefront number, the others claimed from the stream's counter
     const uint64_t n_chunks = (n + 1023) / 1024, wg_chunks = (n_chunks + sh.block / 64 - 1) / (sh.block / 64);
     const ClaimSlots::Claim claim = h->claims.take(s, claims_wanted(h, n), n_chunks);
-    const dim3 grid((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(wg_chunks, sh.resident * h->opt_grid_mult)));
+    const uint64_t grid_cap = h->opt_test_walk_grid ? h->opt_test_walk_grid : ~0ull;  // ("test_walk_grid": the claim above is still sized by n_chunks)
+    const dim3 grid((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(wg_chunks, sh.resident * h->opt_grid_mult), grid_cap)));
     CK(walk_dispatch<true>(h, im.probe_big && !im.walk_kh, [&](auto w, auto staged, auto probe) {
         constexpr int W = decltype(w)::value, PROBE = decltype(probe)::value;
         constexpr bool STAGED = decltype(staged)::value;
         static std::atomic<uint64_t> lds_allowed{0};
         CK(allow_walk_lds(lds_allowed, h->device, {(const void*)k_query<W, 1024, STAGED, PROBE>, (const void*)k_query8<W, 1024, STAGED, PROBE>, (const void*)k_query6<W, STAGED, PROBE>}));
-        if (im.walk_kh && PROBE == 0) return bft_walkh_query(im, d_kmers, n, rec, d_bits64, d_rows, claim.ctr, (uint32_t)h->opt_grid_mult, s);
+        if (im.walk_kh && PROBE == 0) return bft_walkh_query(im, d_kmers, n, rec, d_bits64, d_rows, claim.ctr, (uint32_t)h->opt_grid_mult, h->opt_test_walk_grid, s);
         if (sh.res == 1) hipLaunchKernelGGL((k_query<W, 1024, STAGED, PROBE>), grid, dim3(sh.block), sh.lds, s, im, d_kmers, n, rec, d_bits64, d_rows, claim.ctr);
         else if (sh.res == 3) hipLaunchKernelGGL((k_query6<W, STAGED, PROBE>), grid, dim3(sh.block), sh.lds, s, im, d_kmers, n, rec, d_bits64, d_rows, claim.ctr);
         else hipLaunchKernelGGL((k_query8<W, 1024, STAGED, PROBE>), grid, dim3(sh.block), sh.lds, s, im, d_kmers, n, rec, d_bits64, d_rows, claim.ctr);
@@ -368,7 +369,8 @@ int bft_tune_residency(bft_gpu* h) {
 // eight walks per k-mer over image im at shape sh (the residency measured for k_query applies); h: the device, the root's CC count, B
 static int launch_branching_walk(const bft_gpu* h, const BftImage& im, const WalkShape& sh, const uint8_t* d_kmers, uint64_t n, uint64_t* d_bits64, uint8_t* d_counts, hipStream_t s) {
     const uint64_t nblk = (n + sh.block - 1) / sh.block;
-    const dim3 grid((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(nblk, sh.resident)));
+    const uint64_t grid_cap = h->opt_test_walk_grid ? h->opt_test_walk_grid : ~0ull;  // ("test_walk_grid")
+    const dim3 grid((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(nblk, sh.resident), grid_cap)));
     return walk_dispatch<false>(h, false, [&](auto w, auto staged, auto probe) {
         constexpr int W = decltype(w)::value, PROBE = decltype(probe)::value;
         constexpr bool STAGED = decltype(staged)::value;

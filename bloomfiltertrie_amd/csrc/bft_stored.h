@@ -33,8 +33,9 @@ static inline BftStoredRows bft_stored_rows(bft_gpu* h) {
 }
 static inline BftDerivedRows bft_derived_rows(bft_gpu* h) {
     return {{{"ccx", &h->d_ccx, h->idx_sizes[BFT_S_CCS] / sizeof(BftCC) * sizeof(BftCCX)}, {"f18", &h->d_f18, h->n_f18 * 8}, {"fent", &h->d_fent, h->n_fent * 8},
-             {nullptr, &h->d_rdir, 0}, {nullptr, &h->d_rstart, 0}, {nullptr, &h->d_rq, 0}, {nullptr, &h->d_nph, 0},
-             {"kh", &h->d_kh, h->kh_lines ? (h->kh_lines + BFT_KH_TAIL_LINES) * BFT_KH_LINE_WORDS * 8 : 0ull}, {nullptr, &h->d_rspec, 0},
+             {nullptr, &h->d_rdir, 0}, {"rstart", &h->d_rstart, h->rstart_ok ? ((1ull << 18) + 2) * 4 : 0ull}, {"rq", &h->d_rq, h->rq_ok ? (1ull << 18) * 4 : 0ull},
+             {nullptr, &h->d_nph, 0}, {"kh", &h->d_kh, h->kh_lines ? (h->kh_lines + BFT_KH_TAIL_LINES) * BFT_KH_LINE_WORDS * 8 : 0ull},
+             {"rspec", &h->d_rspec, h->im.rspec ? (1ull << 18) / 8 : 0ull},
              {"kh_ovf_k", &h->d_kh_ovf_k, (uint64_t)h->kh_ovf_n * h->W * 8}, {"kh_ovf_v", &h->d_kh_ovf_v, (uint64_t)h->kh_ovf_n * 4}, {nullptr, &h->d_cs_bm, 0}}};
 }
 // what rows [a, b) of a table hold of the device's memory

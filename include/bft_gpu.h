@@ -266,6 +266,8 @@ int bft_gpu_footprint(bft_gpu* h, uint64_t* out, int n_out);
  * "test_no_cs_bitmaps" (test hook; 1: the bitmap form of the colour-set dictionary is not derived and one that exists is released -- what happens by itself where
  *   it would pass 4 GiB --, so the colour rows and bft_gpu_combine_* read the sorted id lists; 0: it is derived again by the next call that wants it; same answers).
  * "test_genome_matrix_road" (test hook; the road of bft_gpu_genome_matrix*: 0 = the cost model, 1 = pair updates per colour set, 2 = the matrix cores; same matrix).
+ * "test_walk_grid" (test hook; 1..65535: the launches of the container walk -- presence, rows, "walk_hash", branching without the k-mer hash -- use at most this
+ *   many workgroups, so that a small batch gives every wavefront several chunks; 0, the default: no cap; same answers).
  * "timing" (0/1: record HIP events around query kernels; off until this option or the first bft_gpu_kernel_time call turns it on).
  * "build_stages" (0/1: bft_gpu_build records GPU time and algorithmic bytes per stage, see bft_gpu_build_stages). */
 int bft_gpu_set_option(bft_gpu* h, const char* name, int64_t value);

@@ -826,7 +826,10 @@ def test_claim_counters_survive_an_unfinished_launch(k):
     """The query kernels claim their blocks from a per-stream counter (bft_claims.h).  The counter only grows and every launch raises it to the start
     of its own range, so a launch that never finished -- its counter left anywhere inside the range it was given -- cannot make the next one skip
     blocks: "test_stale_claims" leaves every counter one below the next base / exactly there / back at zero, and presence (k-mer hash, container walk
-    with and without hashed root groups), branching and sequence queries still answer whole batches, bit for bit as before."""
+    with and without hashed root groups), branching and sequence queries still answer whole batches, bit for bit as before.
+    The walk's launches here run static: its resident grid (512 workgroups of 12 wavefronts at the default residency) covers 6.29 M k-mers in its
+    first round, so it takes no counter at 3 M.  The capped, claimed walk after stale counters is tests/test_gpu_walk_edges.py's
+    (test_dealing_does_not_change_bits)."""
     import torch
     from bloomfiltertrie_amd import BFT
     anc = S.random_genome(150000, 3 * k)
@@ -837,7 +840,7 @@ def test_claim_counters_survive_an_unfinished_launch(k):
     allk = S.distinct(np.concatenate(gk))
     rng = np.random.default_rng(k)
     base = np.concatenate([allk, S.snp_mutants(allk, k, 2)])
-    q = np.ascontiguousarray(base[rng.integers(0, len(base), 3_000_000)])  # (claims start at 2^16 k-mers; the resident grid covers 2^21 in its first round)
+    q = np.ascontiguousarray(base[rng.integers(0, len(base), 3_000_000)])  # (claims start at 2^16 k-mers; k_query_kh's resident grid covers 2^21 in its first round, the walk's more than this batch)
     truth = S.member(q, allk)
     dq = torch.from_numpy(q).cuda()
     nq = len(q)
