@@ -428,6 +428,40 @@ class BFT:
         _lib.check(self._lib.bft_gpu_simple_paths_dev(self._h, int(min_shared), C.c_void_p(d_offsets_ptr or 0), C.c_void_p(d_seqs_ptr or 0), paths_cap,
                                                       chars_cap, C.c_void_p(d_counts_ptr), C.c_void_p(stream or 0)))
 
+    def unitigs(self, min_shared=0):
+        """The canonical (bidirected) unitigs of a canonical index -- one built with insert_sequences(..., canonical=True) -- on the GPU
+        (bft_gpu_unitigs defines them): maximal non-branching paths over k-mers and their reverse complements, each reported on one strand, in
+        ascending id of their first oriented vertex.  min_shared = t as in simple_paths.  Returns (offsets: uint64 [n_paths + 1], in characters;
+        seqs: uint8 [n_chars], ASCII ACGT): unitig i is seqs[offsets[i]:offsets[i + 1]].  An index that is not canonical raises (BFT_GPU_E_STATE)."""
+        n_paths, n_chars = C.c_uint64(), C.c_uint64()
+        _lib.check(self._lib.bft_gpu_unitigs(self._h, int(min_shared), None, None, 0, 0, C.byref(n_paths), C.byref(n_chars)))
+        offsets = np.zeros(n_paths.value + 1, dtype=np.uint64)
+        seqs = np.zeros(max(1, n_chars.value), dtype=np.uint8)
+        _lib.check(self._lib.bft_gpu_unitigs(self._h, int(min_shared), offsets.ctypes.data, seqs.ctypes.data, n_paths.value, n_chars.value,
+                                             C.byref(n_paths), C.byref(n_chars)))
+        return offsets, seqs[:n_chars.value]
+
+    def unitigs_dev(self, d_offsets_ptr, d_seqs_ptr, paths_cap, chars_cap, d_counts_ptr, min_shared=0, stream=None):
+        """Device-resident unitigs (bft_gpu_unitigs_dev): {n_paths, n_chars, longest, non-canonical rows} (4 uint64) at d_counts_ptr always, the
+        offsets entries j <= paths_cap and the characters below chars_cap into the buffers that are not 0; no synchronisation."""
+        _lib.check(self._lib.bft_gpu_unitigs_dev(self._h, int(min_shared), C.c_void_p(d_offsets_ptr or 0), C.c_void_p(d_seqs_ptr or 0), paths_cap,
+                                                 chars_cap, C.c_void_p(d_counts_ptr), C.c_void_p(stream or 0)))
+
+    def bidirected_degrees(self):
+        """Bidirected degrees of every stored k-mer (bft_gpu_bidirected_degrees), on any index: (degrees: uint8 per row in the extract order,
+        out(s, 0) << 4 | out(s, 1) over k-mers and reverse complements; the number of rows that are not canonical)."""
+        bad = C.c_uint64()
+        _lib.check(self._lib.bft_gpu_bidirected_degrees(self._h, None, 0, C.byref(bad)))  # (pending insertions are built: the row count is final)
+        deg = np.zeros(int(self.info()["kmers"]), dtype=np.uint8)
+        _lib.check(self._lib.bft_gpu_bidirected_degrees(self._h, deg.ctypes.data if len(deg) else None, len(deg), C.byref(bad)))
+        return deg, int(bad.value)
+
+    def bidirected_degrees_dev(self, d_degrees_ptr, cap, d_noncanonical_ptr, stream=None):
+        """Device-resident bidirected degrees (bft_gpu_bidirected_degrees_dev): the count of non-canonical rows (1 uint64) at d_noncanonical_ptr
+        always, the degree bytes of the rows below cap at d_degrees_ptr when it is not 0; no synchronisation."""
+        _lib.check(self._lib.bft_gpu_bidirected_degrees_dev(self._h, C.c_void_p(d_degrees_ptr or 0), cap, C.c_void_p(d_noncanonical_ptr),
+                                                            C.c_void_p(stream or 0)))
+
     def components(self, genome_ids=()):
         """get_nb_connected_component (reference snippets.h, src/snippets.c:605-960) on the GPU: the connected components of the index, or of the
         sub-graph of k-mers that carry every genome id of genome_ids (strictly increasing; bft_gpu_components defines them).  Returns

@@ -15,6 +15,7 @@
 #include "../../include/bft/ingest.h"
 #include "../../include/bft/merge.h"
 #include "../../include/bft/snippets.h"
+#include "../../include/bft/unitigs.h"
 
 #define DIE(...) do { fprintf(stderr, __VA_ARGS__); exit(EXIT_FAILURE); } while (0)
 #define NOT_NULL(p, where) do { if ((p) == NULL) DIE("%s: NULL pointer\n", where); } while (0)
@@ -814,16 +815,18 @@ void merging_BFT(char* prefix_bft1, char* prefix_bft2, char* output_prefix, int 
 /* ---------------------------------------------------------------- simple paths (<bft/snippets.h>) */
 
 /* src/snippets.c:306-344 and :563-603 without the walk: the file is opened first (the reference's ERROR on failure), then one
- * bft_gpu_simple_paths call counts the paths and a second one fetches them; they are written one per line and the longest is reported. */
-static void simple_paths_to_disk(BFT* bft, uint32_t t, const char* filename, const char* open_error, const char* what, const char* where) {
+ * bft_gpu_simple_paths call counts the paths and a second one fetches them; they are written one per line and the longest is reported.
+ * paths: bft_gpu_simple_paths, or bft_gpu_unitigs for <bft/unitigs.h> (the same arguments, the same host rules). */
+typedef int (*paths_call)(bft_gpu*, uint32_t, uint64_t*, char*, uint64_t, uint64_t, uint64_t*, uint64_t*);
+static void paths_to_disk(BFT* bft, paths_call paths, uint32_t t, const char* filename, const char* open_error, const char* report, const char* where) {
     FILE* file = fopen(filename, "w");
     if (file == NULL) DIE("%s", open_error);
     uint64_t n_paths = 0, n_chars = 0;
-    ck(bft_gpu_simple_paths(bft->gpu, t, NULL, NULL, 0, 0, &n_paths, &n_chars), where);
+    ck(paths(bft->gpu, t, NULL, NULL, 0, 0, &n_paths, &n_chars), where);
     uint64_t* offsets = malloc((size_t)(n_paths + 1) * sizeof(uint64_t));
     char* seqs = malloc((size_t)(n_chars ? n_chars : 1));
     if (offsets == NULL || seqs == NULL) DIE("%s: out of memory\n", where);
-    ck(bft_gpu_simple_paths(bft->gpu, t, offsets, seqs, n_paths, n_chars, &n_paths, &n_chars), where);
+    ck(paths(bft->gpu, t, offsets, seqs, n_paths, n_chars, &n_paths, &n_chars), where);
     uint64_t longest = 0;
     for (uint64_t i = 0; i < n_paths; i++) {
         const uint64_t len = offsets[i + 1] - offsets[i];
@@ -833,7 +836,12 @@ static void simple_paths_to_disk(BFT* bft, uint32_t t, const char* filename, con
     if (fclose(file) != 0) DIE("%s: failed to write the output file.\n", where);
     free(offsets);
     free(seqs);
-    printf("Longest simple %spath has %d nuc.\n", what, (int)longest);
+    printf(report, (int)longest);
+}
+static void simple_paths_to_disk(BFT* bft, uint32_t t, const char* filename, const char* open_error, const char* what, const char* where) {
+    char report[64];
+    snprintf(report, sizeof report, "Longest simple %spath has %%d nuc.\n", what);
+    paths_to_disk(bft, bft_gpu_simple_paths, t, filename, open_error, report, where);
 }
 
 void extract_simple_paths_to_disk(BFT* graph, char* filename_output) {
@@ -848,6 +856,14 @@ void extract_simple_core_paths_to_disk(BFT* graph, double core_ratio, char* file
     const int t = (int)(core_ratio * graph->nb_genomes); /* (truncated, as src/snippets.c:366; a negative threshold holds for every k-mer) */
     simple_paths_to_disk(graph, t > 0 ? (uint32_t)t : 0u, filename_output, "extract_simple_core_paths_to_disk(): failed to create/open output file.\n", "core ",
                          "extract_simple_core_paths_to_disk()");
+}
+
+/* <bft/unitigs.h>: the same file, from bft_gpu_unitigs */
+void extract_unitigs_to_disk(BFT* graph, int min_shared, char* filename_output) {
+    NOT_NULL(graph, "extract_unitigs_to_disk()");
+    NOT_NULL(filename_output, "extract_unitigs_to_disk()");
+    paths_to_disk(graph, bft_gpu_unitigs, min_shared > 0 ? (uint32_t)min_shared : 0u, filename_output, "extract_unitigs_to_disk(): failed to create output file.\n",
+                  "Longest unitig has %d nuc.\n", "extract_unitigs_to_disk()");
 }
 
 /* ---------------------------------------------------------------- marking (include/bft.h:143-146, src/bft.c:686-765) */

@@ -9,6 +9,7 @@
  *                         [-query_sequences threshold {canonical|non_canonical} list_sequence_files]
  *                         [-extract_kmers {kmers|kmers_comp} output_file]
  *                         [-genome_matrix {shared|jaccard|mash} output_file]
+ *                         [-unitigs min_shared output_file]
  *
  * It is the per-k-mer loops of src/file_io.c:89-213 (build), :651-895 (presence CSV) and :897-1020 (branching)
  * rewired to one batched GPU call per file; file reading, ASCII parsing (parseKmerCount, src/fasta.c:3-53) and CSV
@@ -19,6 +20,8 @@
  *   - stdout: "Nb k-mers present = <n>" (src/main.c:266), "Nb branching k-mers = <n>" (src/main.c:312).
  * An extension: with `sequences` / `sequences_canonical` the listed files are plain-text FASTA or four-line FASTQ and their k-mers are cut on the
  * GPU (bft_gpu_insert_sequence_file); -min_abundance N keeps the k-mers a file holds at least N times.
+ * Another: -unitigs writes the canonical (bidirected) unitigs of a canonical index (bft_gpu_unitigs; min_shared 0: every k-mer) as FASTA records
+ * `>unitig_<i> length=<L>`, in the call's order.
  * Another: -genome_matrix writes the genome-by-genome shared k-mer matrix (bft_gpu_genome_matrix) as tab-separated text: a header line of the genome
  * names behind an empty first cell, then one line per genome, its name and its row -- the counts (shared, %llu) or the distances computed from
  * them (jaccard, mash: %.6f).
@@ -346,6 +349,30 @@ static void genome_matrix(bft_gpu* h, const char* what, const char* path, int k,
     free(m);
 }
 
+/* -unitigs: one count call, one fetch, FASTA records in the order of bft_gpu_unitigs */
+static void unitigs(bft_gpu* h, const char* min_shared, const char* path) {
+    char* end = NULL;
+    const long t = strtol(min_shared, &end, 10);
+    if (end == min_shared || *end || t < 0) DIE("Could not parse min_shared for command -unitigs.\n");
+    uint64_t n_paths = 0, n_chars = 0;
+    ck(bft_gpu_unitigs(h, (uint32_t)t, NULL, NULL, 0, 0, &n_paths, &n_chars));
+    uint64_t* offsets = calloc((size_t)n_paths + 1, 8);
+    char* seqs = malloc((size_t)(n_chars ? n_chars : 1));
+    if (!offsets || !seqs) DIE("-unitigs: out of memory\n");
+    ck(bft_gpu_unitigs(h, (uint32_t)t, offsets, seqs, n_paths, n_chars, &n_paths, &n_chars));
+    FILE* f = fopen(path, "w");
+    if (!f) DIE("Cannot create %s\n", path);
+    for (uint64_t i = 0; i < n_paths; i++) {
+        const uint64_t len = offsets[i + 1] - offsets[i];
+        fprintf(f, ">unitig_%llu length=%llu\n", (unsigned long long)i, (unsigned long long)len);
+        fwrite(seqs + offsets[i], 1, (size_t)len, f);
+        fputc('\n', f);
+    }
+    if (fclose(f) != 0) DIE("Cannot write %s\n", path);
+    free(offsets);
+    free(seqs);
+}
+
 int main(int argc, char** argv) {
     if (argc >= 2 && (strcmp(argv[1], "--version") == 0 || strcmp(argv[1], "-v") == 0)) { /* src/main.c:51-55 */
         fprintf(stderr, "0.8 (%s)\n", bft_gpu_version());
@@ -359,7 +386,8 @@ int main(int argc, char** argv) {
             "[-query_branching {kmers|kmers_comp} list_kmer_files]\n"
             "[-query_sequences threshold {canonical|non_canonical} list_sequence_files]\n"
             "[-extract_kmers {kmers|kmers_comp} output_file]\n"
-            "[-genome_matrix {shared|jaccard|mash} output_file]\n\n");
+            "[-genome_matrix {shared|jaccard|mash} output_file]\n"
+            "[-unitigs min_shared output_file]\n\n");
     bft_gpu* h = NULL;
     int k = 0, i = 0;
     char buffer[2048];
@@ -420,6 +448,7 @@ int main(int argc, char** argv) {
             continue;
         }
         if (strcmp(argv[i], "-genome_matrix") == 0) { genome_matrix(h, argv[i + 1], argv[i + 2], k, nb_genomes, names); continue; }
+        if (strcmp(argv[i], "-unitigs") == 0) { unitigs(h, argv[i + 1], argv[i + 2]); continue; }
         const int binary = strcmp(argv[i + 1], "kmers_comp") == 0;
         if (!binary && strcmp(argv[i + 1], "kmers") != 0) DIE("Unrecognized type of input files for %s.\n", argv[i]);
         if (strcmp(argv[i], "-extract_kmers") == 0) { extract_kmers(h, argv[i + 2], k, binary); continue; }

@@ -61,27 +61,8 @@ __global__ __launch_bounds__(SP_THREADS) void k_sp_degrees(const uint64_t* __res
     }
 }
 
-__device__ __forceinline__ uint32_t sp_set_size(const uint32_t* cs_off, uint32_t cs) { return cs_off[cs + 1] - cs_off[cs]; }
-
 __device__ __forceinline__ bool sp_node(uint32_t i, uint32_t t, const uint32_t* succ, const uint32_t* indeg, const uint32_t* tcol, const uint32_t* cs_off) {
     return indeg[i] <= 1u && succ[i] != BFT_SP_MANY && (t == 0u || sp_set_size(cs_off, tcol[i]) >= t);
-}
-
-// |C(a) & C(b)| >= t for two sorted id lists
-__device__ bool sp_shared(uint32_t ca, uint32_t cb, uint32_t t, const uint32_t* cs_off, const void* cs_ids, uint32_t cs_w) {
-    if (t == 0u || ca == cb) return true;  // (a node's own set has t ids or more)
-    uint32_t i = cs_off[ca], ie = cs_off[ca + 1], j = cs_off[cb], je = cs_off[cb + 1], got = 0;
-    while (i < ie && j < je) {
-        if (got + min(ie - i, je - j) < t) return false;
-        const uint32_t a = bft_cs_id_at(cs_ids, cs_w, i), b = bft_cs_id_at(cs_ids, cs_w, j);
-        if (a == b) {
-            if (++got >= t) return true;
-            i++;
-            j++;
-        } else if (a < b) i++;
-        else j++;
-    }
-    return got >= t;
 }
 
 __global__ __launch_bounds__(SP_THREADS) void k_sp_links(uint32_t n, uint32_t t, const uint32_t* __restrict__ tcol, const uint32_t* __restrict__ cs_off,

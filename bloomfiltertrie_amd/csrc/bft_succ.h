@@ -1,5 +1,6 @@
 // bft_succ.h -- the successor search over the sorted T-form table tk shared by the whole-graph kernels (simple paths, bft_paths.hip; connected
-// components, bft_components.hip): the bucket of a T-form's top bits, and every stored successor x[1..k-1]+N of a row with ONE lower bound.
+// components, bft_components.hip): the bucket of a T-form's top bits, and every stored successor x[1..k-1]+N of a row with ONE lower bound;
+// and the colour-set tests of their nodes and edges (also the bidirected paths', bft_unitigs.hip).
 // Device code only, header only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -47,4 +48,24 @@ __device__ __forceinline__ void bft_for_each_successor(const uint64_t* __restric
         if ((c[W - 1] & ~wild) != t[W - 1]) continue;
         f(r);
     }
+}
+
+// the number of genomes of colour set cs
+__device__ __forceinline__ uint32_t sp_set_size(const uint32_t* cs_off, uint32_t cs) { return cs_off[cs + 1] - cs_off[cs]; }
+
+// |C(a) & C(b)| >= t for two sorted id lists
+__device__ inline bool sp_shared(uint32_t ca, uint32_t cb, uint32_t t, const uint32_t* cs_off, const void* cs_ids, uint32_t cs_w) {
+    if (t == 0u || ca == cb) return true;  // (a node's own set has t ids or more)
+    uint32_t i = cs_off[ca], ie = cs_off[ca + 1], j = cs_off[cb], je = cs_off[cb + 1], got = 0;
+    while (i < ie && j < je) {
+        if (got + min(ie - i, je - j) < t) return false;
+        const uint32_t a = bft_cs_id_at(cs_ids, cs_w, i), b = bft_cs_id_at(cs_ids, cs_w, j);
+        if (a == b) {
+            if (++got >= t) return true;
+            i++;
+            j++;
+        } else if (a < b) i++;
+        else j++;
+    }
+    return got >= t;
 }

@@ -407,8 +407,8 @@ int bft_gpu_merge(bft_gpu* a, bft_gpu* b, uint32_t id_base, bft_gpu** out);
 /* Simple (non-branching) paths, or unitigs: extract_simple_paths_to_disk(bft, filename) and extract_simple_core_paths_to_disk(bft, core_ratio,
  * filename) (reference snippets.h, src/snippets.c:115-603) without the disk, for a threshold t = min_shared on shared genomes (0: plain simple
  * paths; the core form passes (int)(core_ratio * nb_genomes)).
- *   degrees  the successors of a stored k-mer x are the stored x[1..k-1]+N, its predecessors the stored N+x[0..k-2] (not canonical); they
- *            always count the whole index;
+ *   degrees  the successors of a stored k-mer x are the stored x[1..k-1]+N, its predecessors the stored N+x[0..k-2] (not canonical: for the
+ *            unitigs of a canonical index see bft_gpu_unitigs); they always count the whole index;
  *   nodes    stored k-mers with in-degree <= 1, out-degree <= 1 and a colour set of t genomes or more (branching k-mers are in no path);
  *   edges    u -> v when v is u's only successor, u is v's only predecessor, both are nodes, v != u and |C(u) & C(v)| >= t;
  *   paths    the maximal chains of edges, spelled as their first k-mer plus the last nucleotide of each following one (a lone node: its k-mer).
@@ -428,7 +428,41 @@ int bft_gpu_simple_paths(bft_gpu* h, uint32_t min_shared, uint64_t* offsets, cha
 int bft_gpu_simple_paths_dev(bft_gpu* h, uint32_t min_shared, void* d_offsets, void* d_seqs, uint64_t paths_cap, uint64_t chars_cap, void* d_counts,
                              void* hip_stream);
 
-/* Connected components: get_nb_connected_component(bft, &nb, BFS | DFS) and (..., BFS_subgraph | DFS_subgraph, nb_id_genomes, ids...) (reference
+/* Canonical (bidirected) unitigs: the compacted de Bruijn graph of a CANONICAL index -- every stored s has s <= rc(s) by nucleotide, A < C < G < T
+ * (a palindrome s == rc(s) is canonical): what bft_gpu_insert_sequences(..., canonical = 1) builds.  Rows are those of bft_gpu_extract.
+ *   vertices    (s, o), o in {0, 1}, id 2 * row(s) + o; word w(s, 0) = s, w(s, 1) = rc(s); flip(s, o) = (s, 1 - o);
+ *   successors  for each N of ACGT the word y = w(v)[1..k-1]+N is represented when y or rc(y) is stored; out(v) counts the represented WORDS (0..4: a
+ *               palindromic y once), the successor vertex of y is (y, 0) when y is stored, else (rc(y), 1); in(v) = out(flip(v));
+ *   nodes       out(v) <= 1, out(flip(v)) <= 1 and a colour set of t = min_shared genomes or more (as bft_gpu_simple_paths): both orientations of a
+ *               row together;
+ *   edges       u -> v when v is u's only successor, flip(u) is flip(v)'s only successor, both are nodes, row(u) != row(v) (no self-loop, no hairpin
+ *               x -> rc(x)), neither k-mer is a palindrome and |C(u) & C(v)| >= t.  A palindrome counts in its neighbours' degrees and is
+ *               always a path of its own;
+ *   paths       the maximal chains of edges and the cycles.  Each occurs twice, as P and as its mirror (reversed, every vertex flipped); one is
+ *               reported: a chain with head h and tail q iff id(h) < id(flip(q)) (a lone node: its stored k-mer), a cycle in the orientation
+ *               that holds the (s, 0) of its smallest row, from that vertex, for m + k - 1 nucleotides.  A path is spelled as the word of its first
+ *               vertex plus the last nucleotide of the word of each following one; paths come in ascending id of their first vertex.
+ * Buffers, caps, counting with NULL outputs, BFT_GPU_E_NOSPACE, pending insertions, "compact_table", kernel time, "build_stages" and the limit of
+ * 2^31 - 1 k-mers: as bft_gpu_simple_paths.  An index that is not canonical gives BFT_GPU_E_STATE, and nothing is written. */
+int bft_gpu_unitigs(bft_gpu* h, uint32_t min_shared, uint64_t* offsets, char* seqs, uint64_t paths_cap, uint64_t chars_cap, uint64_t* n_paths,
+                    uint64_t* n_chars);
+/* The same into device buffers on hip_stream (NULL = the handle's stream), without host synchronisation: d_counts (4 x uint64) always receives
+ * {n_paths, n_chars, longest path in characters, rows with s > rc(s)}; d_offsets (may be NULL) receives the entries j <= paths_cap of the offsets,
+ * d_seqs (may be NULL) the characters below chars_cap.  When d_counts[3] != 0 the index is not canonical and the other outputs are unspecified
+ * (nothing is written beyond the caps).  Scratch (107 bytes per k-mer) is shared with bft_gpu_simple_paths: the two are serialised on a handle.
+ * Not inside a graph capture (BFT_GPU_E_ARG). */
+int bft_gpu_unitigs_dev(bft_gpu* h, uint32_t min_shared, void* d_offsets, void* d_seqs, uint64_t paths_cap, uint64_t chars_cap, void* d_counts,
+                        void* hip_stream);
+/* The bidirected degrees of every stored k-mer, the canonical counterpart of bft_gpu_query_branching's counts: degrees[row] =
+ * out(s, 0) << 4 | out(s, 1) as defined above (out(s, 1) = in(s, 0)), defined and returned on ANY index; *n_noncanonical = the rows with s > rc(s)
+ * (0: the index is canonical).  degrees (may be NULL: the count alone) holds cap bytes, n_kmers are needed: BFT_GPU_E_NOSPACE, with nothing
+ * written, when cap is too small.  Pending insertions are built first ("compact_table": the sorted table comes back). */
+int bft_gpu_bidirected_degrees(bft_gpu* h, uint8_t* degrees, uint64_t cap, uint64_t* n_noncanonical);
+/* The same into device buffers on hip_stream (NULL = the handle's stream), without host synchronisation: d_noncanonical (1 x uint64) always,
+ * d_degrees (may be NULL) the bytes of the rows below cap.  Not inside a graph capture (BFT_GPU_E_ARG). */
+int bft_gpu_bidirected_degrees_dev(bft_gpu* h, void* d_degrees, uint64_t cap, void* d_noncanonical, void* hip_stream);
+
+/* Connected components:get_nb_connected_component(bft, &nb, BFS | DFS) and (..., BFS_subgraph | DFS_subgraph, nb_id_genomes, ids...) (reference
  * snippets.h, src/snippets.c:605-960) without the walk, over the whole graph (nb_ids = 0) or the sub-graph of genome_ids.
  *   vertices  the stored k-mers; in a sub-graph, only the members: k-mers whose colour set holds EVERY id of genome_ids;
  *   edges     x - y when y is a stored x[1..k-1]+N or a stored N+x[0..k-2] (the 8 neighbours of get_neighbors, undirected; not canonical); in
