@@ -15,8 +15,6 @@
 //                 lanes all hold one label adds once
 //   k_cc_sizes    sizes[c] out; the largest component (an atomic from a wavefront only when it beats the counter's current value)
 // No kernel needs LDS or scratch memory.
-#include <type_traits>
-
 #include "bft_components.h"
 #include "bft_dev.h"
 #include "bft_handle.h"
@@ -25,7 +23,6 @@
 
 namespace {
 
-constexpr int CC_THREADS = 256;
 constexpr int CC_COUNT_ROUNDS = 64;  // rows per lane in k_cc_count (64-row rounds of a wavefront's stretch)
 
 struct CcIds {
@@ -33,9 +30,9 @@ struct CcIds {
     uint32_t id[BFT_CC_IDS];
 };
 
-__global__ __launch_bounds__(CC_THREADS) void k_cc_sets(uint32_t n_sets, const uint32_t* __restrict__ cs_off, const void* __restrict__ cs_ids, uint32_t cs_w,
+__global__ __launch_bounds__(BFT_LAUNCH_THREADS) void k_cc_sets(uint32_t n_sets, const uint32_t* __restrict__ cs_off, const void* __restrict__ cs_ids, uint32_t cs_w,
                                                         CcIds q, int first, uint8_t* __restrict__ member) {
-    for (uint64_t c = blockIdx.x * (uint64_t)CC_THREADS + threadIdx.x; c < n_sets; c += (uint64_t)gridDim.x * CC_THREADS) {
+    for (uint64_t c = blockIdx.x * (uint64_t)BFT_LAUNCH_THREADS + threadIdx.x; c < n_sets; c += (uint64_t)gridDim.x * BFT_LAUNCH_THREADS) {
         uint32_t i = cs_off[c];
         const uint32_t e = cs_off[c + 1];
         bool ok = first || member[c] != 0;
@@ -50,9 +47,9 @@ __global__ __launch_bounds__(CC_THREADS) void k_cc_sets(uint32_t n_sets, const u
 }
 
 // (marks: the two-bit vertex flags of bft_marking.h, 16 rows per word -- a member must also hold the flag `through`; NULL: no such condition)
-__global__ __launch_bounds__(CC_THREADS) void k_cc_init(uint32_t n, const uint32_t* __restrict__ tcol, const uint8_t* __restrict__ member,
+__global__ __launch_bounds__(BFT_LAUNCH_THREADS) void k_cc_init(uint32_t n, const uint32_t* __restrict__ tcol, const uint8_t* __restrict__ member,
                                                         const uint32_t* __restrict__ marks, uint32_t through, uint32_t* __restrict__ parent) {
-    for (uint64_t u = blockIdx.x * (uint64_t)CC_THREADS + threadIdx.x; u < n; u += (uint64_t)gridDim.x * CC_THREADS) {
+    for (uint64_t u = blockIdx.x * (uint64_t)BFT_LAUNCH_THREADS + threadIdx.x; u < n; u += (uint64_t)gridDim.x * BFT_LAUNCH_THREADS) {
         bool in = tcol == nullptr || member[tcol[u]];
         if (in && marks != nullptr) in = ((marks[u >> 4] >> (2u * ((uint32_t)u & 15u))) & 3u) == through;
         parent[u] = in ? (uint32_t)u : BFT_CC_NONE;
@@ -92,9 +89,9 @@ __device__ __forceinline__ void cc_unite(uint32_t* parent, uint32_t a, uint32_t 
 }
 
 template <int W>
-__global__ __launch_bounds__(CC_THREADS) void k_cc_hook(const uint64_t* __restrict__ tk, uint32_t n, int k, int sb, const uint32_t* __restrict__ start,
+__global__ __launch_bounds__(BFT_LAUNCH_THREADS) void k_cc_hook(const uint64_t* __restrict__ tk, uint32_t n, int k, int sb, const uint32_t* __restrict__ start,
                                                         uint32_t* parent) {
-    for (uint64_t u = blockIdx.x * (uint64_t)CC_THREADS + threadIdx.x; u < n; u += (uint64_t)gridDim.x * CC_THREADS) {
+    for (uint64_t u = blockIdx.x * (uint64_t)BFT_LAUNCH_THREADS + threadIdx.x; u < n; u += (uint64_t)gridDim.x * BFT_LAUNCH_THREADS) {
         if (cc_load(&parent[u]) == BFT_CC_NONE) continue;  // (membership never changes: a member's parent is never BFT_CC_NONE)
         bft_for_each_successor<W>(tk, n, k, sb, start, u, [&](uint32_t r) {
             if (r != (uint32_t)u && cc_load(&parent[r]) != BFT_CC_NONE) cc_unite(parent, (uint32_t)u, r);
@@ -104,8 +101,8 @@ __global__ __launch_bounds__(CC_THREADS) void k_cc_hook(const uint64_t* __restri
 
 // (plain loads: the hook's writes are visible after the kernel boundary; a lane here reads either a row's parent from the hook or the root another
 // lane wrote, and both lead to the same root)
-__global__ __launch_bounds__(CC_THREADS) void k_cc_flatten(uint32_t n, uint32_t* parent) {
-    for (uint64_t u = blockIdx.x * (uint64_t)CC_THREADS + threadIdx.x; u < n; u += (uint64_t)gridDim.x * CC_THREADS) {
+__global__ __launch_bounds__(BFT_LAUNCH_THREADS) void k_cc_flatten(uint32_t n, uint32_t* parent) {
+    for (uint64_t u = blockIdx.x * (uint64_t)BFT_LAUNCH_THREADS + threadIdx.x; u < n; u += (uint64_t)gridDim.x * BFT_LAUNCH_THREADS) {
         const uint32_t p = parent[u];
         if (p == BFT_CC_NONE || p == (uint32_t)u) continue;
         uint32_t r = p, q = parent[r];
@@ -117,8 +114,8 @@ __global__ __launch_bounds__(CC_THREADS) void k_cc_flatten(uint32_t n, uint32_t*
     }
 }
 
-__global__ __launch_bounds__(CC_THREADS) void k_cc_label(uint32_t n, uint32_t* __restrict__ parent, uint32_t* __restrict__ num, uint32_t* __restrict__ labels) {
-    for (uint64_t u = blockIdx.x * (uint64_t)CC_THREADS + threadIdx.x; u < n; u += (uint64_t)gridDim.x * CC_THREADS) {
+__global__ __launch_bounds__(BFT_LAUNCH_THREADS) void k_cc_label(uint32_t n, uint32_t* __restrict__ parent, uint32_t* __restrict__ num, uint32_t* __restrict__ labels) {
+    for (uint64_t u = blockIdx.x * (uint64_t)BFT_LAUNCH_THREADS + threadIdx.x; u < n; u += (uint64_t)gridDim.x * BFT_LAUNCH_THREADS) {
         const uint32_t p = parent[u];
         const uint32_t lab = p == BFT_CC_NONE ? BFT_CC_NONE : num[p];
         if (labels) labels[u] = lab;
@@ -127,11 +124,11 @@ __global__ __launch_bounds__(CC_THREADS) void k_cc_label(uint32_t n, uint32_t* _
     }
 }
 
-__global__ __launch_bounds__(CC_THREADS) void k_cc_count(uint32_t n, const uint32_t* __restrict__ lab, uint32_t* __restrict__ sz) {
+__global__ __launch_bounds__(BFT_LAUNCH_THREADS) void k_cc_count(uint32_t n, const uint32_t* __restrict__ lab, uint32_t* __restrict__ sz) {
     constexpr uint64_t STRETCH = 64ull * CC_COUNT_ROUNDS;  // rows per wavefront and pass
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t waves = (uint64_t)gridDim.x * (CC_THREADS / 64);
-    for (uint64_t base = (blockIdx.x * (uint64_t)(CC_THREADS / 64) + (threadIdx.x >> 6)) * STRETCH; base < n; base += waves * STRETCH) {
+    const uint64_t waves = (uint64_t)gridDim.x * (BFT_LAUNCH_THREADS / 64);
+    for (uint64_t base = (blockIdx.x * (uint64_t)(BFT_LAUNCH_THREADS / 64) + (threadIdx.x >> 6)) * STRETCH; base < n; base += waves * STRETCH) {
         uint32_t cur = BFT_CC_NONE, cnt = 0;
         for (int r = 0; r < CC_COUNT_ROUNDS; r++) {
             const uint64_t i = base + (uint64_t)r * 64u + lane;
@@ -159,11 +156,11 @@ __global__ __launch_bounds__(CC_THREADS) void k_cc_count(uint32_t n, const uint3
     }
 }
 
-__global__ __launch_bounds__(CC_THREADS) void k_cc_sizes(const uint32_t* __restrict__ sz, uint64_t* __restrict__ sizes, uint64_t cap,
+__global__ __launch_bounds__(BFT_LAUNCH_THREADS) void k_cc_sizes(const uint32_t* __restrict__ sz, uint64_t* __restrict__ sizes, uint64_t cap,
                                                          unsigned long long* __restrict__ counts) {
     const uint64_t nc = counts[0];
     // (every lane of a wavefront runs the same iterations: the wavefront's maximum is combined with shuffles)
-    for (uint64_t c0 = blockIdx.x * (uint64_t)CC_THREADS + (threadIdx.x & ~63u); c0 < nc; c0 += (uint64_t)gridDim.x * CC_THREADS) {
+    for (uint64_t c0 = blockIdx.x * (uint64_t)BFT_LAUNCH_THREADS + (threadIdx.x & ~63u); c0 < nc; c0 += (uint64_t)gridDim.x * BFT_LAUNCH_THREADS) {
         const uint64_t c = c0 + (threadIdx.x & 63u);
         uint32_t v = 0;
         if (c < nc) {
@@ -177,69 +174,40 @@ __global__ __launch_bounds__(CC_THREADS) void k_cc_sizes(const uint32_t* __restr
     }
 }
 
-dim3 cc_grid(uint64_t n) { return dim3(bft_grid_for((n + CC_THREADS - 1) / CC_THREADS)); }
-
 }  // namespace
 
 int bft_cc_sets(uint64_t n_sets, const uint32_t* d_cs_off, const void* d_cs_ids, uint32_t cs_w, const uint32_t* ids, uint32_t nb, bool first, const BftCcScratch& p,
                 hipStream_t s) {
-    if (n_sets == 0) return 0;
     CcIds q{};
     q.n = nb < BFT_CC_IDS ? nb : BFT_CC_IDS;
     for (uint32_t j = 0; j < q.n; j++) q.id[j] = ids[j];
-    hipLaunchKernelGGL(k_cc_sets, cc_grid(n_sets), dim3(CC_THREADS), 0, s, (uint32_t)n_sets, d_cs_off, d_cs_ids, cs_w, q, first ? 1 : 0, p.member);
-    HIPCK(hipGetLastError());
-    return 0;
+    return bft_launch256(k_cc_sets, n_sets, s, (uint32_t)n_sets, d_cs_off, d_cs_ids, cs_w, q, first ? 1 : 0, p.member);
 }
 
 int bft_cc_init(uint64_t n, const uint32_t* d_tcol, const BftCcScratch& p, hipStream_t s, const uint32_t* d_marks, uint32_t through) {
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(k_cc_init, cc_grid(n), dim3(CC_THREADS), 0, s, (uint32_t)n, d_tcol, (const uint8_t*)p.member, d_marks, through, p.parent);
-    HIPCK(hipGetLastError());
-    return 0;
+    return bft_launch256(k_cc_init, n, s, (uint32_t)n, d_tcol, (const uint8_t*)p.member, d_marks, through, p.parent);
 }
 
 int bft_cc_hook(int W, const uint64_t* d_tk, uint64_t n, int k, const BftCcScratch& p, hipStream_t s) {
-    if (n == 0) return 0;
-    auto go = [&](auto KW) {
-        hipLaunchKernelGGL((k_cc_hook<KW>), cc_grid(n), dim3(CC_THREADS), 0, s, d_tk, (uint32_t)n, k, p.sp.sb, (const uint32_t*)p.sp.start, p.parent);
-    };
-    switch (W) {
-    case 1: go(std::integral_constant<int, 1>()); break;
-    case 2: go(std::integral_constant<int, 2>()); break;
-    case 3: go(std::integral_constant<int, 3>()); break;
-    default: go(std::integral_constant<int, 4>()); break;
-    }
-    HIPCK(hipGetLastError());
-    return 0;
+    return bft_for_w(W, [&](auto KW) { return bft_launch256(k_cc_hook<KW>, n, s, d_tk, (uint32_t)n, k, p.sp.sb, (const uint32_t*)p.sp.start, p.parent); });
 }
 
 int bft_cc_flatten(uint64_t n, const BftCcScratch& p, hipStream_t s) {
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(k_cc_flatten, cc_grid(n), dim3(CC_THREADS), 0, s, (uint32_t)n, p.parent);
-    HIPCK(hipGetLastError());
-    return 0;
+    return bft_launch256(k_cc_flatten, n, s, (uint32_t)n, p.parent);
 }
 
 int bft_cc_label(uint64_t n, const BftCcScratch& p, uint32_t* d_labels, hipStream_t s) {
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(k_cc_label, cc_grid(n), dim3(CC_THREADS), 0, s, (uint32_t)n, p.parent, p.num, d_labels);
-    HIPCK(hipGetLastError());
-    return 0;
+    return bft_launch256(k_cc_label, n, s, (uint32_t)n, p.parent, p.num, d_labels);
 }
 
 int bft_cc_count(uint64_t n, const BftCcScratch& p, hipStream_t s) {
     if (n == 0) return 0;
-    hipLaunchKernelGGL(k_cc_count, cc_grid((n + CC_COUNT_ROUNDS - 1) / CC_COUNT_ROUNDS), dim3(CC_THREADS), 0, s, (uint32_t)n, (const uint32_t*)p.num, p.parent);
-    HIPCK(hipGetLastError());
-    return 0;
+    // (the items are lanes: each takes CC_COUNT_ROUNDS rows)
+    return bft_launch256(k_cc_count, (n + CC_COUNT_ROUNDS - 1) / CC_COUNT_ROUNDS, s, (uint32_t)n, (const uint32_t*)p.num, p.parent);
 }
 
 int bft_cc_sizes(uint64_t n, const BftCcScratch& p, uint64_t* d_sizes, uint64_t sizes_cap, unsigned long long* d_counts, hipStream_t s) {
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(k_cc_sizes, cc_grid(n), dim3(CC_THREADS), 0, s, (const uint32_t*)p.parent, d_sizes, sizes_cap, d_counts);
-    HIPCK(hipGetLastError());
-    return 0;
+    return bft_launch256(k_cc_sizes, n, s, (const uint32_t*)p.parent, d_sizes, sizes_cap, d_counts);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -256,8 +224,8 @@ static size_t cc_carve(uint64_t m, uint64_t sets, uint8_t* base, BftCcScratch* p
 }
 // The handle's scratch (h->cc: HandleScratch, bft_handle.h) for an index of n rows and n_sets colour sets on stream s: its own block, shared with no
 // other query, sized exactly.
-static int cc_scratch(bft_gpu* h, uint64_t n, uint64_t n_sets, hipStream_t s, BftCcScratch* p) {
-    CK(h->cc.acquire(s, false));  // (the entry points refuse a capturing stream)
+static int cc_scratch(bft_gpu* h, HandleScratch::Lease& lease, uint64_t n, uint64_t n_sets, hipStream_t s, BftCcScratch* p) {
+    CK(lease.acquire(s, false));  // (the entry points refuse a capturing stream)
     p->sp = BftSpScratch{};
     p->sp.sb = bft_sp_bucket_bits(h->k);
     h->cc_m = std::max(n, h->cc_m);
@@ -318,13 +286,13 @@ extern "C" int bft_gpu_components_dev(bft_gpu* h, const uint32_t* genome_ids, ui
         CK(bft_zero_async(d_counts, 24, s));
         return bft_note_foreign_stream(h, s);
     }
-    BftCcScratch p;
-    CK(cc_scratch(h, h->n_kmers, h->n_sets, s, &p));
     {
+        HandleScratch::Lease lease(h->cc);
+        BftCcScratch p;
+        CK(cc_scratch(h, lease, h->n_kmers, h->n_sets, s, &p));
         StageScope stage_scope(h, s);
         CK(cc_run(h, genome_ids, nb_ids, s, (unsigned long long*)d_counts, p, (uint32_t*)d_labels, (uint64_t*)d_sizes, sizes_cap));
     }
-    h->cc.release();
     return bft_note_foreign_stream(h, s);
 }
 
@@ -342,18 +310,16 @@ extern "C" int bft_gpu_components(bft_gpu* h, const uint32_t* genome_ids, uint32
     const hipStream_t s = h->stream;
     DevBuf dcnt;
     CK(dcnt.alloc(24));
+    HandleScratch::Lease lease(h->cc);
     BftCcScratch p;
-    CK(cc_scratch(h, n, h->n_sets, s, &p));
+    CK(cc_scratch(h, lease, n, h->n_sets, s, &p));
     StageScope stage_scope(h);
     CK(cc_run(h, genome_ids, nb_ids, s, dcnt.as<unsigned long long>(), p, nullptr, nullptr, 0));
     unsigned long long cnt[3] = {0, 0, 0};
     HIPCK(hipMemcpyAsync(cnt, dcnt.p, 24, hipMemcpyDeviceToHost, s));
     HIPCK(hipStreamSynchronize(s));
     for (int i = 0; i < 3; i++) counts[i] = cnt[i];
-    if ((labels && labels_cap < n) || (sizes && sizes_cap < cnt[0])) {
-        h->cc.release();
-        return bft_fail(BFT_GPU_E_NOSPACE, "component buffers too small");
-    }
+    if ((labels && labels_cap < n) || (sizes && sizes_cap < cnt[0])) return bft_fail(BFT_GPU_E_NOSPACE, "component buffers too small");
     DevBuf dsz;
     if (sizes && cnt[0]) {  // (the counters are 32-bit in the scratch: widened by a second pass of the last kernel)
         CK(dsz.alloc(cnt[0] * 8));
@@ -362,6 +328,5 @@ extern "C" int bft_gpu_components(bft_gpu* h, const uint32_t* genome_ids, uint32
     }
     if (labels) HIPCK(hipMemcpyAsync(labels, p.num, n * 4, hipMemcpyDeviceToHost, s));
     if (labels || sizes) HIPCK(hipStreamSynchronize(s));
-    h->cc.release();
     return BFT_GPU_OK;
 }

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/bft_gpu.h"
@@ -115,6 +116,31 @@ struct PinBlock {
 static inline int bft_grid_for(uint64_t nblk) {
     const uint64_t cap = 256ull * 8ull;  // 256 CUs x 8 resident workgroups of 256 threads
     return (int)std::max<uint64_t>(1, std::min<uint64_t>(nblk, cap));
+}
+
+// The launch kit of the whole-graph and analysis units (host only): their kernels run grid-stride loops in workgroups of BFT_LAUNCH_THREADS.
+constexpr int BFT_LAUNCH_THREADS = 256;
+// kernel<<<bft_grid_for(ceil(items / 256)), 256, 0, s>>>(args...); nothing at items == 0
+template <class K, class... A>
+static int bft_launch256(K kernel, uint64_t items, hipStream_t s, A... args) {
+    if (items == 0) return 0;
+    hipLaunchKernelGGL(kernel, dim3(bft_grid_for((items + BFT_LAUNCH_THREADS - 1) / BFT_LAUNCH_THREADS)), dim3(BFT_LAUNCH_THREADS), 0, s, args...);
+    HIPCK(hipGetLastError());
+    return 0;
+}
+// f(std::integral_constant<int, W>) for the key width W = 1..4 (words per k-mer): the kernels are templates over it.  f launches and returns a code
+template <class F>
+static int bft_for_w(int W, F&& f) {
+    int rc;
+    switch (W) {
+    case 1: rc = f(std::integral_constant<int, 1>()); break;
+    case 2: rc = f(std::integral_constant<int, 2>()); break;
+    case 3: rc = f(std::integral_constant<int, 3>()); break;
+    default: rc = f(std::integral_constant<int, 4>()); break;
+    }
+    CK(rc);
+    HIPCK(hipGetLastError());
+    return 0;
 }
 
 // GPU container assembly and colour interning (bft_assemble.hip)

@@ -335,8 +335,8 @@ static size_t gm_carve(uint64_t sets, uint8_t* base, BftGmScratch* p) {
 static uint64_t gm_bits_bytes(uint64_t n_sets, uint32_t G) { return gm_pad(G, BFT_GM_TILE) * (gm_pad(n_sets, BFT_GM_STEP) / 8); }
 // The handle's scratch (h->gm) for n_sets colour sets and G genomes on stream s.  *dense_ok: the bit matrix is there -- always when the road is
 // forced to be the dense one, never when it is forced to be the sparse one, else while it stays below BFT_GM_DENSE_MAX_BYTES.
-static int gm_scratch(bft_gpu* h, uint64_t n_sets, uint32_t G, int forced, hipStream_t s, BftGmScratch* p, bool* dense_ok) {
-    CK(h->gm.acquire(s, false));  // (the entry points refuse a capturing stream)
+static int gm_scratch(bft_gpu* h, HandleScratch::Lease& lease, uint64_t n_sets, uint32_t G, int forced, hipStream_t s, BftGmScratch* p, bool* dense_ok) {
+    CK(lease.acquire(s, false));  // (the entry points refuse a capturing stream)
     // (the carving depends on the set count: a block carved for more sets than this image has would put the arrays elsewhere, so it is carved for
     // this count and only its size is kept from shrinking)
     h->gm_sets = std::max(n_sets, h->gm_sets);
@@ -376,9 +376,11 @@ static int gm_matrix(bft_gpu* h, uint32_t G, bool whole, const uint32_t* d_ids, 
     if (G == 0) return 0;
     CK(bft_zero_async(d_shared, (size_t)G * G * 8, s));
     if (h->n_sets == 0 || lo > hi || (whole ? h->n_kmers == 0 : n == 0)) return 0;
+    // (the scratch's use ends with this function: the callers' copies behind it read d_shared alone)
+    HandleScratch::Lease lease(h->gm);
     BftGmScratch p{};
     bool dense_ok = false;
-    CK(gm_scratch(h, h->n_sets, G, h->opt_gm_road, s, &p, &dense_ok));
+    CK(gm_scratch(h, lease, h->n_sets, G, h->opt_gm_road, s, &p, &dense_ok));
     {
         StageScope stage_scope(h, s);
         CK(bft_zero_async(p.usage, (size_t)h->n_sets * 4, s));
@@ -392,7 +394,6 @@ static int gm_matrix(bft_gpu* h, uint32_t G, bool whole, const uint32_t* d_ids, 
         }
         CK(gm_roads(h, G, p.usage, lo, hi, h->opt_gm_road, dense_ok, BFT_GM_FLUSH_SETS, p, d_shared, s));
     }
-    h->gm.release();
     return 0;
 }
 
@@ -471,12 +472,12 @@ extern "C" int bft_gpu_test_genome_matrix(bft_gpu* h, const void* d_weights, int
     if (G == 0) return BFT_GPU_OK;
     CK(bft_zero_async(d_shared, (size_t)G * G * 8, s));
     if (h->n_sets == 0) return bft_note_foreign_stream(h, s);
+    HandleScratch::Lease lease(h->gm);
     BftGmScratch p{};
     bool dense_ok = false;
-    CK(gm_scratch(h, h->n_sets, G, road, s, &p, &dense_ok));
+    CK(gm_scratch(h, lease, h->n_sets, G, road, s, &p, &dense_ok));
     StageScope stage_scope(h, s);
     CK(gm_roads(h, G, (const uint32_t*)d_weights, 0, 0xFFFFFFFFu, road, dense_ok, flush_sets ? flush_sets : BFT_GM_FLUSH_SETS, p, (unsigned long long*)d_shared, s));
-    h->gm.release();
     return bft_note_foreign_stream(h, s);
 }
 
@@ -493,7 +494,8 @@ extern "C" int bft_gpu_test_genome_matrix_state(bft_gpu* h, uint32_t canary, uin
     BftGmScratch p{};
     bool dense_ok = false;
     const bool fresh = h->gm_buf.bytes == 0;
-    CK(gm_scratch(h, h->n_sets, G, BFT_GM_SPARSE, s, &p, &dense_ok));
+    HandleScratch::Lease lease(h->gm);
+    CK(gm_scratch(h, lease, h->n_sets, G, BFT_GM_SPARSE, s, &p, &dense_ok));
     if (fresh) HIPCK(hipMemsetAsync(p.plan, 0, 32, s));
     if (canary) HIPCK(hipMemcpyAsync(p.usage + h->n_sets, &canary, 4, hipMemcpyHostToDevice, s));
     unsigned long long plan[4] = {0, 0, 0, 0};
@@ -501,6 +503,5 @@ extern "C" int bft_gpu_test_genome_matrix_state(bft_gpu* h, uint32_t canary, uin
     HIPCK(hipMemcpyAsync(&out[1], p.usage + h->n_sets, 4, hipMemcpyDeviceToHost, s));
     HIPCK(hipStreamSynchronize(s));
     out[0] = (uint32_t)plan[2];
-    h->gm.release();
     return BFT_GPU_OK;
 }

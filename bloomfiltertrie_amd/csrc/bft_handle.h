@@ -3,7 +3,7 @@
 // in: .bft files, the blob, the read-outs, the width of the dictionary's ids; over the tables of bft_stored.h), bft_derive.hip (what the
 // handle derives from a committed image, bft_derive.h: root tables, k-mer hash, node prefix hash, launch shape, compact table), bft_query.hip (the k-mer and
 // sequence queries, their tuner, the claim slots), bft_run.hip (the build's run stage, the sort and scan test hooks) and the analysis families
-// bft_prefix.hip, bft_paths.hip, bft_components.hip, bft_pangenome.hip, bft_genome_matrix.hip, bft_subgraph.hip, bft_marking.hip, bft_setops.hip, bft_union.hip, bft_ingest.hip.
+// bft_prefix.hip, bft_paths.hip (the path engine and the simple paths), bft_unitigs.hip (its mirrored family), bft_components.hip, bft_pangenome.hip, bft_genome_matrix.hip, bft_subgraph.hip, bft_marking.hip, bft_setops.hip, bft_union.hip, bft_ingest.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,14 +14,39 @@
 #include "bft_kh.h"
 
 // Scratch of ONE query family of a handle: blocks (DevBufs beside it in struct bft_gpu) that belong to the handle, not to a stream -- one stream uses
-// them at a time, they grow and never shrink.  A call takes them with acquire(), sizes each block with grow(), and says with release() behind its last
-// launch where its use ends.  While the stream is being captured nothing waits and nothing allocates: the call is refused (the caller makes one direct
+// them at a time, they grow and never shrink.  A call takes them through a Lease (acquire(), fallible), sizes each block with grow(), and its use
+// ends where the lease leaves scope: behind its last launch, and on every error return as well.  While the stream is being captured nothing waits and nothing allocates: the call is refused (the caller makes one direct
 // call of that size first, include/bft_gpu.h), and the scratch stays with that stream -- a graph's replays are not ordered against other streams' calls.
 struct HandleScratch {
     explicit HandleScratch(const char* w) : what(w) {}
     HandleScratch(const HandleScratch&) = delete;
     HandleScratch& operator=(const HandleScratch&) = delete;
     ~HandleScratch() { if (ev) (void)hipEventDestroy(ev); }
+    // b holds `need` bytes at least (a new block: need + slack).  A block this stream may still be using is not replaced before the stream has drained.
+    int grow(DevBuf& b, size_t need, size_t slack) {
+        if (b.bytes >= need) return 0;
+        if (capturing) return bft_fail(BFT_GPU_E_ARG, std::string(what) + " recorded into a graph: make one direct call of this size first (nothing may allocate in a capture)");
+        if (!idle) HIPCK(hipStreamSynchronize(stream));
+        idle = true;
+        return b.alloc(need + slack);
+    }
+    // One call's use of the scratch, as a scope -- the only way to it.  acquire() may be called again by a helper of the same call; the use ends once,
+    // where the lease leaves scope.  (A call that ends its use before an unrelated tail closes the lease's block there.)
+    struct Lease {
+        explicit Lease(HandleScratch& o) : owner(o) {}
+        Lease(const Lease&) = delete;
+        Lease& operator=(const Lease&) = delete;
+        ~Lease() { if (held) owner.release(); }
+        int acquire(hipStream_t s, bool capturing_) {
+            CK(owner.acquire(s, capturing_));
+            held = true;
+            return 0;
+        }
+    private:
+        HandleScratch& owner;
+        bool held = false;
+    };
+private:
     // In use on another stream: that use ends at an event of the handle's own (the other stream is the caller's and may be gone by now).
     int acquire(hipStream_t s, bool capturing_) {
         if (used && stream != s) {
@@ -35,20 +60,12 @@ struct HandleScratch {
         capturing = capturing_;
         return 0;
     }
-    // b holds `need` bytes at least (a new block: need + slack).  A block this stream may still be using is not replaced before the stream has drained.
-    int grow(DevBuf& b, size_t need, size_t slack) {
-        if (b.bytes >= need) return 0;
-        if (capturing) return bft_fail(BFT_GPU_E_ARG, std::string(what) + " recorded into a graph: make one direct call of this size first (nothing may allocate in a capture)");
-        if (!idle) HIPCK(hipStreamSynchronize(stream));
-        idle = true;
-        return b.alloc(need + slack);
-    }
+    // where the use that acquire() began ends on its stream (a failed event record is swallowed)
     void release() {
         if (capturing) return;  // (an event recorded there would belong to the graph: the next eager call on another stream would wait on it)
         if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { ev = nullptr; (void)hipGetLastError(); }
         if (ev && hipEventRecord(ev, stream) != hipSuccess) (void)hipGetLastError();
     }
-private:
     const char* what;              // the family, for the messages
     hipStream_t stream = nullptr;  // the last user
     hipEvent_t ev = nullptr;       // where its last eager use ends

@@ -239,13 +239,13 @@ int ing_sort(bft_gpu* h, uint64_t n, hipStream_t s) {
     return 0;
 }
 
-// One batch of sequences resident on the device, on stream s; st: the call's four counters, added to.  The handle's ingest scratch is taken and
-// released here.  Waits for s once per piece (stream path; twice where the piece may not fit the log) or twice (counting path).
-int ingest_core(bft_gpu* h, const char* d_seqs, const uint64_t* d_seq_off, uint64_t n_seqs, uint64_t total_chars, int canonical, uint32_t min_abundance,
+// One batch of sequences resident on the device, on stream s; st: the call's four counters, added to.  The handle's ingest scratch is taken here,
+// through the caller's lease (which may hold it already: the host form stages its chunk into the handle's blocks first) and with it released.  Waits for s once per piece (stream path; twice where the piece may not fit the log) or twice (counting path).
+int ingest_core(bft_gpu* h, HandleScratch::Lease& lease, const char* d_seqs, const uint64_t* d_seq_off, uint64_t n_seqs, uint64_t total_chars, int canonical, uint32_t min_abundance,
                 uint32_t gid, uint64_t st[4], hipStream_t s) {
     if (n_seqs == 0) return 0;
     if (n_seqs >= (1ull << 32)) return bft_fail(BFT_GPU_E_LIMIT, "insert_sequences: at most 2^32 - 1 sequences per call");
-    CK(h->ig.acquire(s, false));
+    CK(lease.acquire(s, false));
     auto need = [&](DevBuf& b, size_t bytes) { return h->ig.grow(b, bytes, bytes / 8); };
     StageScope stages(h, s);
     PinBlock pin;  // [0] k-mer positions of the batch, [1] valid positions of the piece / kept runs, [2] (a device word beside it: distinct k-mers)
@@ -382,7 +382,6 @@ int ingest_core(bft_gpu* h, const char* d_seqs, const uint64_t* d_seq_off, uint6
     }
     // the caller may reuse its buffers -- and the log's rows are complete -- when the call returns
     if (hipStreamSynchronize(s) != hipSuccess && rc == 0) rc = bft_fail(BFT_GPU_E_HIP, "insert_sequences: stream synchronisation");
-    h->ig.release();
     return rc;
 }
 
@@ -431,7 +430,8 @@ extern "C" int bft_gpu_insert_sequences_dev(bft_gpu* h, const void* d_seqs, cons
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
     if (bft_stream_capturing(s)) return bft_fail(BFT_GPU_E_ARG, "insert_sequences: not inside a graph capture (the call waits for its row count)");
     bft_pool_set_stream(h->device, s);  // (the sort's temporaries are used on s: whoever takes them next is ordered behind it or waits for it)
-    const int rc = ingest_core(h, (const char*)d_seqs, (const uint64_t*)d_seq_off, n_seqs, total_chars, canonical, min_abundance, id_genome, st, s);
+    HandleScratch::Lease lease(h->ig);
+    const int rc = ingest_core(h, lease, (const char*)d_seqs, (const uint64_t*)d_seq_off, n_seqs, total_chars, canonical, min_abundance, id_genome, st, s);
     if (stats) memcpy(stats, st, sizeof(st));
     return rc;
 }
@@ -463,12 +463,13 @@ extern "C" int bft_gpu_insert_sequences(bft_gpu* h, const char* seqs, const uint
         const uint64_t ns = off.size() - 1, nchars = off.back();
         if (ns == 0) return bft_fail(BFT_GPU_E_ARG, "insert_sequences: empty chunk");  // (cannot happen: chunk >= 2k)
         // the staging blocks are the handle's: the chunk before was waited for by ingest_core
-        CK(h->ig.acquire(s, false));
+        HandleScratch::Lease lease(h->ig);
+        CK(lease.acquire(s, false));
         CK(h->ig.grow(h->ig_seq, nchars + 16, nchars / 8));
         CK(h->ig.grow(h->ig_soff, (ns + 1) * 8, ns));
         if (nchars) HIPCK(hipMemcpyAsync(h->ig_seq.p, seqs + c0, nchars, hipMemcpyHostToDevice, s));
         HIPCK(hipMemcpyAsync(h->ig_soff.p, off.data(), (ns + 1) * 8, hipMemcpyHostToDevice, s));
-        rc = ingest_core(h, h->ig_seq.as<char>(), h->ig_soff.as<uint64_t>(), ns, nchars, canonical, min_abundance, id_genome, st, s);
+        rc = ingest_core(h, lease, h->ig_seq.as<char>(), h->ig_soff.as<uint64_t>(), ns, nchars, canonical, min_abundance, id_genome, st, s);
     }
     if (stats) memcpy(stats, st, sizeof(st));
     return rc;

@@ -21,7 +21,6 @@
 //   k_mk_unseed   best[root of a seed] = none again: the forest is ready for the next reach
 // The number of launches depends on the arguments alone, never on the data.  No kernel needs scratch memory; k_mk_counts and the counters' reduction
 // use 64 bytes of LDS.
-#include <type_traits>
 
 #include "bft_components.h"
 #include "bft_dev.h"
@@ -32,8 +31,6 @@
 #include "bft_succ.h"
 
 namespace {
-
-constexpr int MK_THREADS = 256;
 
 __device__ __forceinline__ uint32_t mk_load(uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
@@ -46,7 +43,7 @@ __device__ __forceinline__ void mk_block_add(uint32_t v, unsigned long long* dst
     if (threadIdx.x == 0) {
         uint32_t t = 0;
 #pragma unroll
-        for (int w = 0; w < MK_THREADS / 64; w++) t += lds[w];
+        for (int w = 0; w < BFT_LAUNCH_THREADS / 64; w++) t += lds[w];
         if (t && dst) atomicAdd(dst, (unsigned long long)t);
     }
     __syncthreads();
@@ -65,11 +62,11 @@ __device__ __forceinline__ bool mk_move(uint32_t* words, uint32_t r, uint32_t ex
     return false;
 }
 
-__global__ __launch_bounds__(MK_THREADS) void k_mk_set(const uint32_t* __restrict__ rows, uint64_t n, uint32_t n_rows, const uint8_t* __restrict__ fl, uint32_t flag,
+__global__ __launch_bounds__(BFT_LAUNCH_THREADS) void k_mk_set(const uint32_t* __restrict__ rows, uint64_t n, uint32_t n_rows, const uint8_t* __restrict__ fl, uint32_t flag,
                                                        uint32_t* words, unsigned long long* absent) {
-    __shared__ uint32_t lds[MK_THREADS / 64];
+    __shared__ uint32_t lds[BFT_LAUNCH_THREADS / 64];
     uint32_t miss = 0;
-    for (uint64_t i = blockIdx.x * (uint64_t)MK_THREADS + threadIdx.x; i < n; i += (uint64_t)gridDim.x * MK_THREADS) {
+    for (uint64_t i = blockIdx.x * (uint64_t)BFT_LAUNCH_THREADS + threadIdx.x; i < n; i += (uint64_t)gridDim.x * BFT_LAUNCH_THREADS) {
         const uint32_t r = rows[i];
         if (r >= n_rows) {
             miss++;
@@ -96,11 +93,11 @@ __global__ __launch_bounds__(MK_THREADS) void k_mk_set(const uint32_t* __restric
     mk_block_add(miss, absent, lds);
 }
 
-__global__ __launch_bounds__(MK_THREADS) void k_mk_get(const uint32_t* __restrict__ rows, uint64_t n, uint32_t n_rows, const uint32_t* __restrict__ words,
+__global__ __launch_bounds__(BFT_LAUNCH_THREADS) void k_mk_get(const uint32_t* __restrict__ rows, uint64_t n, uint32_t n_rows, const uint32_t* __restrict__ words,
                                                        uint8_t* __restrict__ out, unsigned long long* absent) {
-    __shared__ uint32_t lds[MK_THREADS / 64];
+    __shared__ uint32_t lds[BFT_LAUNCH_THREADS / 64];
     uint32_t miss = 0;
-    for (uint64_t i = blockIdx.x * (uint64_t)MK_THREADS + threadIdx.x; i < n; i += (uint64_t)gridDim.x * MK_THREADS) {
+    for (uint64_t i = blockIdx.x * (uint64_t)BFT_LAUNCH_THREADS + threadIdx.x; i < n; i += (uint64_t)gridDim.x * BFT_LAUNCH_THREADS) {
         const uint32_t r = rows[i];
         if (r >= n_rows) {
             miss++;
@@ -111,11 +108,11 @@ __global__ __launch_bounds__(MK_THREADS) void k_mk_get(const uint32_t* __restric
     mk_block_add(miss, absent, lds);
 }
 
-__global__ __launch_bounds__(MK_THREADS) void k_mk_tas(const uint32_t* __restrict__ rows, uint64_t n, uint32_t n_rows, uint32_t expect, uint32_t flag, uint32_t* words,
+__global__ __launch_bounds__(BFT_LAUNCH_THREADS) void k_mk_tas(const uint32_t* __restrict__ rows, uint64_t n, uint32_t n_rows, uint32_t expect, uint32_t flag, uint32_t* words,
                                                        uint8_t* __restrict__ won, unsigned long long* absent) {
-    __shared__ uint32_t lds[MK_THREADS / 64];
+    __shared__ uint32_t lds[BFT_LAUNCH_THREADS / 64];
     uint32_t miss = 0;
-    for (uint64_t i = blockIdx.x * (uint64_t)MK_THREADS + threadIdx.x; i < n; i += (uint64_t)gridDim.x * MK_THREADS) {
+    for (uint64_t i = blockIdx.x * (uint64_t)BFT_LAUNCH_THREADS + threadIdx.x; i < n; i += (uint64_t)gridDim.x * BFT_LAUNCH_THREADS) {
         const uint32_t r = rows[i];
         bool w = false;
         if (r >= n_rows) miss++;
@@ -125,18 +122,18 @@ __global__ __launch_bounds__(MK_THREADS) void k_mk_tas(const uint32_t* __restric
     mk_block_add(miss, absent, lds);
 }
 
-__global__ __launch_bounds__(MK_THREADS) void k_mk_fill(uint32_t* __restrict__ words, uint64_t n_words, uint32_t n_rows, uint32_t flag) {
+__global__ __launch_bounds__(BFT_LAUNCH_THREADS) void k_mk_fill(uint32_t* __restrict__ words, uint64_t n_words, uint32_t n_rows, uint32_t flag) {
     const uint32_t full = flag * 0x55555555u;
-    for (uint64_t i = blockIdx.x * (uint64_t)MK_THREADS + threadIdx.x; i < n_words; i += (uint64_t)gridDim.x * MK_THREADS) {
+    for (uint64_t i = blockIdx.x * (uint64_t)BFT_LAUNCH_THREADS + threadIdx.x; i < n_words; i += (uint64_t)gridDim.x * BFT_LAUNCH_THREADS) {
         const uint32_t live = n_rows - (uint32_t)i * 16u;  // rows of this word that exist (>= 1)
         words[i] = live >= 16u ? full : full & ((1u << (2u * live)) - 1u);
     }
 }
 
-__global__ __launch_bounds__(MK_THREADS) void k_mk_counts(const uint32_t* __restrict__ words, uint64_t n_words, uint32_t n_rows, unsigned long long* counts) {
-    __shared__ uint32_t lds[MK_THREADS / 64];
+__global__ __launch_bounds__(BFT_LAUNCH_THREADS) void k_mk_counts(const uint32_t* __restrict__ words, uint64_t n_words, uint32_t n_rows, unsigned long long* counts) {
+    __shared__ uint32_t lds[BFT_LAUNCH_THREADS / 64];
     uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-    for (uint64_t i = blockIdx.x * (uint64_t)MK_THREADS + threadIdx.x; i < n_words; i += (uint64_t)gridDim.x * MK_THREADS) {
+    for (uint64_t i = blockIdx.x * (uint64_t)BFT_LAUNCH_THREADS + threadIdx.x; i < n_words; i += (uint64_t)gridDim.x * BFT_LAUNCH_THREADS) {
         const uint32_t w = words[i], lo = w & 0x55555555u, hi = (w >> 1) & 0x55555555u;
         const uint32_t live = n_rows - (uint32_t)i * 16u;
         const uint32_t a = (uint32_t)__popc(lo & ~hi), b = (uint32_t)__popc(hi & ~lo), c = (uint32_t)__popc(lo & hi);
@@ -151,16 +148,16 @@ __global__ __launch_bounds__(MK_THREADS) void k_mk_counts(const uint32_t* __rest
     mk_block_add(c3, counts + 3, lds);
 }
 
-__global__ __launch_bounds__(MK_THREADS) void k_mk_unhit(uint32_t n, uint32_t* __restrict__ best) {
-    for (uint64_t u = blockIdx.x * (uint64_t)MK_THREADS + threadIdx.x; u < n; u += (uint64_t)gridDim.x * MK_THREADS) best[u] = BFT_MK_NONE;
+__global__ __launch_bounds__(BFT_LAUNCH_THREADS) void k_mk_unhit(uint32_t n, uint32_t* __restrict__ best) {
+    for (uint64_t u = blockIdx.x * (uint64_t)BFT_LAUNCH_THREADS + threadIdx.x; u < n; u += (uint64_t)gridDim.x * BFT_LAUNCH_THREADS) best[u] = BFT_MK_NONE;
 }
 
 // (parent[] is flattened: parent[r] is r's root.  A row of the forest whose flag is no longer `through` was painted by an earlier reach: not eligible)
-__global__ __launch_bounds__(MK_THREADS) void k_mk_seed(const uint32_t* __restrict__ rows, uint64_t n_seeds, uint32_t n_rows, const uint32_t* __restrict__ parent,
+__global__ __launch_bounds__(BFT_LAUNCH_THREADS) void k_mk_seed(const uint32_t* __restrict__ rows, uint64_t n_seeds, uint32_t n_rows, const uint32_t* __restrict__ parent,
                                                         const uint32_t* __restrict__ words, uint32_t through, uint32_t* best, unsigned long long* absent) {
-    __shared__ uint32_t lds[MK_THREADS / 64];
+    __shared__ uint32_t lds[BFT_LAUNCH_THREADS / 64];
     uint32_t miss = 0;
-    for (uint64_t i = blockIdx.x * (uint64_t)MK_THREADS + threadIdx.x; i < n_seeds; i += (uint64_t)gridDim.x * MK_THREADS) {
+    for (uint64_t i = blockIdx.x * (uint64_t)BFT_LAUNCH_THREADS + threadIdx.x; i < n_seeds; i += (uint64_t)gridDim.x * BFT_LAUNCH_THREADS) {
         const uint32_t r = rows[i];
         if (r >= n_rows) {
             miss++;
@@ -172,12 +169,12 @@ __global__ __launch_bounds__(MK_THREADS) void k_mk_seed(const uint32_t* __restri
     mk_block_add(miss, absent, lds);
 }
 
-__global__ __launch_bounds__(MK_THREADS) void k_mk_paint(uint32_t n_rows, uint64_t n_words, const uint32_t* __restrict__ parent, const uint32_t* __restrict__ best,
+__global__ __launch_bounds__(BFT_LAUNCH_THREADS) void k_mk_paint(uint32_t n_rows, uint64_t n_words, const uint32_t* __restrict__ parent, const uint32_t* __restrict__ best,
                                                          uint32_t* __restrict__ words, uint32_t through, uint32_t to, const uint32_t* __restrict__ rows,
                                                          uint64_t n_seeds, uint8_t* __restrict__ seed_new, unsigned long long* painted) {
-    __shared__ uint32_t lds[MK_THREADS / 64];
+    __shared__ uint32_t lds[BFT_LAUNCH_THREADS / 64];
     uint32_t cnt = 0;
-    for (uint64_t i = blockIdx.x * (uint64_t)MK_THREADS + threadIdx.x; i < n_words; i += (uint64_t)gridDim.x * MK_THREADS) {
+    for (uint64_t i = blockIdx.x * (uint64_t)BFT_LAUNCH_THREADS + threadIdx.x; i < n_words; i += (uint64_t)gridDim.x * BFT_LAUNCH_THREADS) {
         const uint32_t w = words[i];
         uint32_t nw = w;
 #pragma unroll
@@ -192,7 +189,7 @@ __global__ __launch_bounds__(MK_THREADS) void k_mk_paint(uint32_t n_rows, uint64
         if (nw != w) words[i] = nw;
     }
     if (seed_new)
-        for (uint64_t i = blockIdx.x * (uint64_t)MK_THREADS + threadIdx.x; i < n_seeds; i += (uint64_t)gridDim.x * MK_THREADS) {
+        for (uint64_t i = blockIdx.x * (uint64_t)BFT_LAUNCH_THREADS + threadIdx.x; i < n_seeds; i += (uint64_t)gridDim.x * BFT_LAUNCH_THREADS) {
             const uint32_t r = rows[i];
             const uint32_t p = r < n_rows ? parent[r] : BFT_CC_NONE;
             seed_new[i] = (p != BFT_CC_NONE && best[p] == (uint32_t)i) ? 1u : 0u;
@@ -203,13 +200,13 @@ __global__ __launch_bounds__(MK_THREADS) void k_mk_paint(uint32_t n_rows, uint64
 // (after k_mk_paint: parent[] and best[] are only read here, and tell the painted members whatever their flag says now; the flags of the rows
 // outside the forest move through -> to by CAS alone)
 template <int W>
-__global__ __launch_bounds__(MK_THREADS) void k_mk_boundary(const uint64_t* __restrict__ tk, uint32_t n, int k, int sb, const uint32_t* __restrict__ start,
+__global__ __launch_bounds__(BFT_LAUNCH_THREADS) void k_mk_boundary(const uint64_t* __restrict__ tk, uint32_t n, int k, int sb, const uint32_t* __restrict__ start,
                                                             const uint32_t* __restrict__ parent, const uint32_t* __restrict__ best, uint32_t* words,
                                                             uint32_t through, uint32_t to, const uint32_t* __restrict__ rows, uint64_t n_seeds,
                                                             unsigned long long* painted) {
-    __shared__ uint32_t lds[MK_THREADS / 64];
+    __shared__ uint32_t lds[BFT_LAUNCH_THREADS / 64];
     uint32_t cnt = 0;
-    for (uint64_t u = blockIdx.x * (uint64_t)MK_THREADS + threadIdx.x; u < n; u += (uint64_t)gridDim.x * MK_THREADS) {
+    for (uint64_t u = blockIdx.x * (uint64_t)BFT_LAUNCH_THREADS + threadIdx.x; u < n; u += (uint64_t)gridDim.x * BFT_LAUNCH_THREADS) {
         const uint32_t pu = parent[u];
         const bool hit_u = pu != BFT_CC_NONE && best[pu] != BFT_MK_NONE;
         // an outside row that does not hold `through` now never will again in this kernel; a member that was not hit has no painted neighbour
@@ -223,23 +220,21 @@ __global__ __launch_bounds__(MK_THREADS) void k_mk_boundary(const uint64_t* __re
                 cnt++;
         });
     }
-    for (uint64_t i = blockIdx.x * (uint64_t)MK_THREADS + threadIdx.x; i < n_seeds; i += (uint64_t)gridDim.x * MK_THREADS) {
+    for (uint64_t i = blockIdx.x * (uint64_t)BFT_LAUNCH_THREADS + threadIdx.x; i < n_seeds; i += (uint64_t)gridDim.x * BFT_LAUNCH_THREADS) {
         const uint32_t r = rows[i];
         if (r < n && parent[r] == BFT_CC_NONE && mk_move(words, r, through, to)) cnt++;
     }
     mk_block_add(cnt, painted, lds);
 }
 
-__global__ __launch_bounds__(MK_THREADS) void k_mk_unseed(const uint32_t* __restrict__ rows, uint64_t n_seeds, uint32_t n_rows, const uint32_t* __restrict__ parent,
+__global__ __launch_bounds__(BFT_LAUNCH_THREADS) void k_mk_unseed(const uint32_t* __restrict__ rows, uint64_t n_seeds, uint32_t n_rows, const uint32_t* __restrict__ parent,
                                                           uint32_t* __restrict__ best) {
-    for (uint64_t i = blockIdx.x * (uint64_t)MK_THREADS + threadIdx.x; i < n_seeds; i += (uint64_t)gridDim.x * MK_THREADS) {
+    for (uint64_t i = blockIdx.x * (uint64_t)BFT_LAUNCH_THREADS + threadIdx.x; i < n_seeds; i += (uint64_t)gridDim.x * BFT_LAUNCH_THREADS) {
         const uint32_t r = rows[i];
         const uint32_t p = r < n_rows ? parent[r] : BFT_CC_NONE;
         if (p != BFT_CC_NONE) best[p] = BFT_MK_NONE;  // (seeds of one component all write the same value)
     }
 }
-
-dim3 mk_grid(uint64_t n) { return dim3(bft_grid_for((n + MK_THREADS - 1) / MK_THREADS)); }
 
 struct MkForest {
     BftCcScratch cc;
@@ -258,16 +253,12 @@ size_t mk_carve(uint64_t n, uint64_t sets, uint8_t* base, MkForest* f) {
 
 uint32_t* mk_words(bft_gpu* h) { return h->mk_flags.as<uint32_t>(); }
 
-// What every marks call starts with: the handle is marking, the table is resident, the marks' blocks are this stream's.
-int mk_enter(bft_gpu* h, hipStream_t s, const char* what) {
+// What every marks call starts with: the handle is marking, the table is resident, the marks' blocks are this stream's until `lease` leaves scope.
+int mk_enter(bft_gpu* h, HandleScratch::Lease& lease, hipStream_t s, const char* what) {
     if (!h->marking) return bft_fail(BFT_GPU_E_STATE, std::string(what) + ": the graph is not initialized for marking (bft_gpu_marks_begin)");
     if (bft_stream_capturing(s)) return bft_fail(BFT_GPU_E_ARG, std::string(what) + " recorded into a graph: not supported (the table may have to come back, scratch may grow)");
     CK(bft_ensure_built(h));  // ("compact_table": the sorted table comes back if an option sent it away; nothing is pending while marking)
-    return h->mk.acquire(s, false);
-}
-int mk_leave(bft_gpu* h, hipStream_t s, bool foreign) {
-    h->mk.release();
-    return foreign ? bft_note_foreign_stream(h, s) : 0;
+    return lease.acquire(s, false);
 }
 
 // rows of n resident packed k-mers into h->mk_rows, by the lookup bft_gpu_query_rows uses
@@ -292,11 +283,9 @@ int mk_batch(bft_gpu* h, MkOp op, const uint8_t* d_kmers, uint64_t n, uint8_t* d
     const uint32_t* rows = h->mk_rows.as<uint32_t>();
     const uint32_t nr = (uint32_t)h->n_kmers;
     return bft_timed_launch(h, s, [&] {
-        if (op == MK_SET) hipLaunchKernelGGL(k_mk_set, mk_grid(n), dim3(MK_THREADS), 0, s, rows, n, nr, (const uint8_t*)d_io, a, mk_words(h), d_absent);
-        else if (op == MK_GET) hipLaunchKernelGGL(k_mk_get, mk_grid(n), dim3(MK_THREADS), 0, s, rows, n, nr, (const uint32_t*)mk_words(h), d_io, d_absent);
-        else hipLaunchKernelGGL(k_mk_tas, mk_grid(n), dim3(MK_THREADS), 0, s, rows, n, nr, a, b, mk_words(h), d_io, d_absent);
-        HIPCK(hipGetLastError());
-        return 0;
+        if (op == MK_SET) return bft_launch256(k_mk_set, n, s, rows, n, nr, (const uint8_t*)d_io, a, mk_words(h), d_absent);
+        else if (op == MK_GET) return bft_launch256(k_mk_get, n, s, rows, n, nr, (const uint32_t*)mk_words(h), d_io, d_absent);
+        else return bft_launch256(k_mk_tas, n, s, rows, n, nr, a, b, mk_words(h), d_io, d_absent);
     });
 }
 
@@ -328,22 +317,14 @@ int mk_fill(bft_gpu* h, uint32_t flag, hipStream_t s) {
     h->mk_forest_ok = false;
     const uint64_t nw = bft_mk_words(h->n_kmers);
     if (nw == 0) return 0;
-    return bft_timed_launch(h, s, [&] {
-        hipLaunchKernelGGL(k_mk_fill, mk_grid(nw), dim3(MK_THREADS), 0, s, mk_words(h), nw, (uint32_t)h->n_kmers, flag);
-        HIPCK(hipGetLastError());
-        return 0;
-    });
+    return bft_timed_launch(h, s, [&] { return bft_launch256(k_mk_fill, nw, s, mk_words(h), nw, (uint32_t)h->n_kmers, flag); });
 }
 
 int mk_counts(bft_gpu* h, unsigned long long* d_counts, hipStream_t s) {
     CK(bft_zero_async(d_counts, 32, s));
     const uint64_t nw = bft_mk_words(h->n_kmers);
     if (nw == 0) return 0;
-    return bft_timed_launch(h, s, [&] {
-        hipLaunchKernelGGL(k_mk_counts, mk_grid(nw), dim3(MK_THREADS), 0, s, (const uint32_t*)mk_words(h), nw, (uint32_t)h->n_kmers, d_counts);
-        HIPCK(hipGetLastError());
-        return 0;
-    });
+    return bft_timed_launch(h, s, [&] { return bft_launch256(k_mk_counts, nw, s, (const uint32_t*)mk_words(h), nw, (uint32_t)h->n_kmers, d_counts); });
 }
 
 // the selection's scan on stream s: slot[] filled (slot[n] included), the number of selected rows at d_count
@@ -401,11 +382,7 @@ int mk_reach(bft_gpu* h, const uint8_t* d_seeds, uint64_t n_seeds, const uint32_
         CK(bft_timed_launch(h, s, [&] { return bft_sp_buckets(W, tk, n, k, f.cc.sp, s); }));
         CK(bft_timed_launch(h, s, [&] { return bft_cc_hook(W, tk, n, k, f.cc, s); }));
         CK(bft_timed_launch(h, s, [&] { return bft_cc_flatten(n, f.cc, s); }));
-        CK(bft_timed_launch(h, s, [&] {
-            hipLaunchKernelGGL(k_mk_unhit, mk_grid(n), dim3(MK_THREADS), 0, s, (uint32_t)n, f.best);
-            HIPCK(hipGetLastError());
-            return 0;
-        }));
+        CK(bft_timed_launch(h, s, [&] { return bft_launch256(k_mk_unhit, n, s, (uint32_t)n, f.best); }));
         h->mk_forest_through = through;
         h->mk_forest_ids.assign(ids, ids + nb);
         h->mk_forest_ok = true;
@@ -413,37 +390,21 @@ int mk_reach(bft_gpu* h, const uint8_t* d_seeds, uint64_t n_seeds, const uint32_
     if (n_seeds == 0) return 0;
     const uint64_t nw = bft_mk_words(n);
     CK(bft_timed_launch(h, s, [&] {
-        hipLaunchKernelGGL(k_mk_seed, mk_grid(n_seeds), dim3(MK_THREADS), 0, s, rows, n_seeds, (uint32_t)n, (const uint32_t*)f.cc.parent, (const uint32_t*)mk_words(h), through,
-                           f.best, d_counts + 2);
-        HIPCK(hipGetLastError());
-        return 0;
+        return bft_launch256(k_mk_seed, n_seeds, s, rows, n_seeds, (uint32_t)n, (const uint32_t*)f.cc.parent, (const uint32_t*)mk_words(h), through,
+                             f.best, d_counts + 2);
     }));
     CK(bft_timed_launch(h, s, [&] {
-        hipLaunchKernelGGL(k_mk_paint, mk_grid(nw), dim3(MK_THREADS), 0, s, (uint32_t)n, nw, (const uint32_t*)f.cc.parent, (const uint32_t*)f.best, mk_words(h), through, to,
-                           rows, n_seeds, d_seed_new, d_counts);
-        HIPCK(hipGetLastError());
-        return 0;
+        return bft_launch256(k_mk_paint, nw, s, (uint32_t)n, nw, (const uint32_t*)f.cc.parent, (const uint32_t*)f.best, mk_words(h), through, to,
+                             rows, n_seeds, d_seed_new, d_counts);
     }));
     if (boundary)
         CK(bft_timed_launch(h, s, [&] {
-            auto go = [&](auto KW) {
-                hipLaunchKernelGGL((k_mk_boundary<KW>), mk_grid(n), dim3(MK_THREADS), 0, s, tk, (uint32_t)n, k, f.cc.sp.sb, (const uint32_t*)f.cc.sp.start,
-                                   (const uint32_t*)f.cc.parent, (const uint32_t*)f.best, mk_words(h), through, to, rows, n_seeds, d_counts + 1);
-            };
-            switch (W) {
-            case 1: go(std::integral_constant<int, 1>()); break;
-            case 2: go(std::integral_constant<int, 2>()); break;
-            case 3: go(std::integral_constant<int, 3>()); break;
-            default: go(std::integral_constant<int, 4>()); break;
-            }
-            HIPCK(hipGetLastError());
-            return 0;
+            return bft_for_w(W, [&](auto KW) {
+                return bft_launch256(k_mk_boundary<KW>, n, s, tk, (uint32_t)n, k, f.cc.sp.sb, (const uint32_t*)f.cc.sp.start, (const uint32_t*)f.cc.parent,
+                                     (const uint32_t*)f.best, mk_words(h), through, to, rows, n_seeds, d_counts + 1);
+            });
         }));
-    return bft_timed_launch(h, s, [&] {
-        hipLaunchKernelGGL(k_mk_unseed, mk_grid(n_seeds), dim3(MK_THREADS), 0, s, rows, n_seeds, (uint32_t)n, (const uint32_t*)f.cc.parent, f.best);
-        HIPCK(hipGetLastError());
-        return 0;
-    });
+    return bft_timed_launch(h, s, [&] { return bft_launch256(k_mk_unseed, n_seeds, s, rows, n_seeds, (uint32_t)n, (const uint32_t*)f.cc.parent, f.best); });
 }
 
 hipStream_t mk_stream(bft_gpu* h, void* hip_stream) { return hip_stream ? (hipStream_t)hip_stream : h->stream; }
@@ -459,11 +420,13 @@ extern "C" int bft_gpu_marks_begin(bft_gpu* h) {
     if (h->marking) return BFT_GPU_OK;  // (src/bft.c:694: a graph that is already marking keeps its flags)
     CK(bft_ensure_built(h));
     if (h->n_kmers >= (1ull << 32) - 1) return bft_fail(BFT_GPU_E_LIMIT, "marks: at most 2^32 - 2 k-mers");
-    CK(h->mk.acquire(h->stream, false));
-    const size_t bytes = (size_t)bft_mk_words(h->n_kmers) * 4;
-    CK(h->mk_flags.alloc(bytes));
-    if (bytes) CK(bft_zero_async(h->mk_flags.p, bytes, h->stream));
-    h->mk.release();
+    {
+        HandleScratch::Lease lease(h->mk);
+        CK(lease.acquire(h->stream, false));
+        const size_t bytes = (size_t)bft_mk_words(h->n_kmers) * 4;
+        CK(h->mk_flags.alloc(bytes));
+        if (bytes) CK(bft_zero_async(h->mk_flags.p, bytes, h->stream));
+    }
     h->mk_forest_ok = false;
     h->marking = true;
     return BFT_GPU_OK;
@@ -473,7 +436,8 @@ extern "C" int bft_gpu_marks_end(bft_gpu* h) {
     if (!h) return bft_fail(BFT_GPU_E_ARG, "NULL handle");
     ENTER(h);
     if (!h->marking) return BFT_GPU_OK;
-    CK(h->mk.acquire(h->stream, false));  // (a use on a caller's stream ends first)
+    HandleScratch::Lease lease(h->mk);
+    CK(lease.acquire(h->stream, false));  // (a use on a caller's stream ends first)
     HIPCK(hipStreamSynchronize(h->stream));
     h->mk_flags.release();
     h->mk_rows.release();
@@ -496,34 +460,42 @@ extern "C" int bft_gpu_marks_set_dev(bft_gpu* h, const void* d_kmers, uint64_t n
     if (!d_flags) MK_FLAG(flag, "marks_set");
     ENTER(h);
     const hipStream_t s = mk_stream(h, hip_stream);
-    CK(mk_enter(h, s, "marks_set"));
-    CK(mk_batch(h, MK_SET, (const uint8_t*)d_kmers, nb_kmers, (uint8_t*)d_flags, flag, 0, (unsigned long long*)d_n_absent, s));
-    return mk_leave(h, s, true);
+    {
+        HandleScratch::Lease lease(h->mk);
+        CK(mk_enter(h, lease, s, "marks_set"));
+        CK(mk_batch(h, MK_SET, (const uint8_t*)d_kmers, nb_kmers, (uint8_t*)d_flags, flag, 0, (unsigned long long*)d_n_absent, s));
+    }
+    return bft_note_foreign_stream(h, s);
 }
 extern "C" int bft_gpu_marks_set(bft_gpu* h, const uint8_t* kmers, uint64_t nb_kmers, const uint8_t* flags, uint8_t flag, uint64_t* n_absent) {
     if (!h || (!kmers && nb_kmers)) return bft_fail(BFT_GPU_E_ARG, "NULL argument");
     if (!flags) MK_FLAG(flag, "marks_set");
     for (uint64_t i = 0; flags && i < nb_kmers; i++) MK_FLAG(flags[i], "marks_set");
     ENTER(h);
-    CK(mk_enter(h, h->stream, "marks_set"));
+    HandleScratch::Lease lease(h->mk);
+    CK(mk_enter(h, lease, h->stream, "marks_set"));
     CK(mk_batch_host(h, MK_SET, kmers, nb_kmers, flags, nullptr, flag, 0, n_absent));
-    return mk_leave(h, h->stream, false);
+    return BFT_GPU_OK;
 }
 
 extern "C" int bft_gpu_marks_get_dev(bft_gpu* h, const void* d_kmers, uint64_t nb_kmers, void* d_flags_out, void* d_n_absent, void* hip_stream) {
     if (!h || ((!d_kmers || !d_flags_out) && nb_kmers)) return bft_fail(BFT_GPU_E_ARG, "NULL argument");
     ENTER(h);
     const hipStream_t s = mk_stream(h, hip_stream);
-    CK(mk_enter(h, s, "marks_get"));
-    CK(mk_batch(h, MK_GET, (const uint8_t*)d_kmers, nb_kmers, (uint8_t*)d_flags_out, 0, 0, (unsigned long long*)d_n_absent, s));
-    return mk_leave(h, s, true);
+    {
+        HandleScratch::Lease lease(h->mk);
+        CK(mk_enter(h, lease, s, "marks_get"));
+        CK(mk_batch(h, MK_GET, (const uint8_t*)d_kmers, nb_kmers, (uint8_t*)d_flags_out, 0, 0, (unsigned long long*)d_n_absent, s));
+    }
+    return bft_note_foreign_stream(h, s);
 }
 extern "C" int bft_gpu_marks_get(bft_gpu* h, const uint8_t* kmers, uint64_t nb_kmers, uint8_t* flags_out, uint64_t* n_absent) {
     if (!h || ((!kmers || !flags_out) && nb_kmers)) return bft_fail(BFT_GPU_E_ARG, "NULL argument");
     ENTER(h);
-    CK(mk_enter(h, h->stream, "marks_get"));
+    HandleScratch::Lease lease(h->mk);
+    CK(mk_enter(h, lease, h->stream, "marks_get"));
     CK(mk_batch_host(h, MK_GET, kmers, nb_kmers, nullptr, flags_out, 0, 0, n_absent));
-    return mk_leave(h, h->stream, false);
+    return BFT_GPU_OK;
 }
 
 extern "C" int bft_gpu_marks_test_and_set_dev(bft_gpu* h, const void* d_kmers, uint64_t nb_kmers, uint8_t expect, uint8_t flag, void* d_won_out, void* d_n_absent,
@@ -534,9 +506,12 @@ extern "C" int bft_gpu_marks_test_and_set_dev(bft_gpu* h, const void* d_kmers, u
     if (expect == flag) return bft_fail(BFT_GPU_E_ARG, "marks_test_and_set: `flag` must differ from `expect`");
     ENTER(h);
     const hipStream_t s = mk_stream(h, hip_stream);
-    CK(mk_enter(h, s, "marks_test_and_set"));
-    CK(mk_batch(h, MK_TAS, (const uint8_t*)d_kmers, nb_kmers, (uint8_t*)d_won_out, expect, flag, (unsigned long long*)d_n_absent, s));
-    return mk_leave(h, s, true);
+    {
+        HandleScratch::Lease lease(h->mk);
+        CK(mk_enter(h, lease, s, "marks_test_and_set"));
+        CK(mk_batch(h, MK_TAS, (const uint8_t*)d_kmers, nb_kmers, (uint8_t*)d_won_out, expect, flag, (unsigned long long*)d_n_absent, s));
+    }
+    return bft_note_foreign_stream(h, s);
 }
 extern "C" int bft_gpu_marks_test_and_set(bft_gpu* h, const uint8_t* kmers, uint64_t nb_kmers, uint8_t expect, uint8_t flag, uint8_t* won_out, uint64_t* n_absent) {
     if (!h || ((!kmers || !won_out) && nb_kmers)) return bft_fail(BFT_GPU_E_ARG, "NULL argument");
@@ -544,9 +519,10 @@ extern "C" int bft_gpu_marks_test_and_set(bft_gpu* h, const uint8_t* kmers, uint
     MK_FLAG(flag, "marks_test_and_set");
     if (expect == flag) return bft_fail(BFT_GPU_E_ARG, "marks_test_and_set: `flag` must differ from `expect`");
     ENTER(h);
-    CK(mk_enter(h, h->stream, "marks_test_and_set"));
+    HandleScratch::Lease lease(h->mk);
+    CK(mk_enter(h, lease, h->stream, "marks_test_and_set"));
     CK(mk_batch_host(h, MK_TAS, kmers, nb_kmers, nullptr, won_out, expect, flag, n_absent));
-    return mk_leave(h, h->stream, false);
+    return BFT_GPU_OK;
 }
 
 extern "C" int bft_gpu_marks_fill_dev(bft_gpu* h, uint8_t flag, void* hip_stream) {
@@ -554,38 +530,46 @@ extern "C" int bft_gpu_marks_fill_dev(bft_gpu* h, uint8_t flag, void* hip_stream
     MK_FLAG(flag, "marks_fill");
     ENTER(h);
     const hipStream_t s = mk_stream(h, hip_stream);
-    CK(mk_enter(h, s, "marks_fill"));
-    CK(mk_fill(h, flag, s));
-    return mk_leave(h, s, true);
+    {
+        HandleScratch::Lease lease(h->mk);
+        CK(mk_enter(h, lease, s, "marks_fill"));
+        CK(mk_fill(h, flag, s));
+    }
+    return bft_note_foreign_stream(h, s);
 }
 extern "C" int bft_gpu_marks_fill(bft_gpu* h, uint8_t flag) {
     if (!h) return bft_fail(BFT_GPU_E_ARG, "NULL handle");
     MK_FLAG(flag, "marks_fill");
     ENTER(h);
-    CK(mk_enter(h, h->stream, "marks_fill"));
+    HandleScratch::Lease lease(h->mk);
+    CK(mk_enter(h, lease, h->stream, "marks_fill"));
     CK(mk_fill(h, flag, h->stream));
     HIPCK(hipStreamSynchronize(h->stream));
-    return mk_leave(h, h->stream, false);
+    return BFT_GPU_OK;
 }
 
 extern "C" int bft_gpu_marks_counts_dev(bft_gpu* h, void* d_counts, void* hip_stream) {
     if (!h || !d_counts) return bft_fail(BFT_GPU_E_ARG, "NULL argument");
     ENTER(h);
     const hipStream_t s = mk_stream(h, hip_stream);
-    CK(mk_enter(h, s, "marks_counts"));
-    CK(mk_counts(h, (unsigned long long*)d_counts, s));
-    return mk_leave(h, s, true);
+    {
+        HandleScratch::Lease lease(h->mk);
+        CK(mk_enter(h, lease, s, "marks_counts"));
+        CK(mk_counts(h, (unsigned long long*)d_counts, s));
+    }
+    return bft_note_foreign_stream(h, s);
 }
 extern "C" int bft_gpu_marks_counts(bft_gpu* h, uint64_t* counts) {
     if (!h || !counts) return bft_fail(BFT_GPU_E_ARG, "NULL argument");
     ENTER(h);
-    CK(mk_enter(h, h->stream, "marks_counts"));
+    HandleScratch::Lease lease(h->mk);
+    CK(mk_enter(h, lease, h->stream, "marks_counts"));
     DevBuf d;
     CK(d.alloc(32));
     CK(mk_counts(h, d.as<unsigned long long>(), h->stream));
     HIPCK(hipMemcpyAsync(counts, d.p, 32, hipMemcpyDeviceToHost, h->stream));
     HIPCK(hipStreamSynchronize(h->stream));
-    return mk_leave(h, h->stream, false);
+    return BFT_GPU_OK;
 }
 
 extern "C" int bft_gpu_marks_select_dev(bft_gpu* h, uint32_t mask, void* d_kmers_out, void* d_ascii_out, void* d_rows_out, uint64_t cap, void* d_count, void* hip_stream) {
@@ -593,14 +577,17 @@ extern "C" int bft_gpu_marks_select_dev(bft_gpu* h, uint32_t mask, void* d_kmers
     if (mask > 15) return bft_fail(BFT_GPU_E_ARG, "marks_select: the mask has one bit per flag value, 0 .. 15");
     ENTER(h);
     const hipStream_t s = mk_stream(h, hip_stream);
-    CK(mk_enter(h, s, "marks_select"));
-    if (h->n_kmers >= (1ull << 31)) return bft_fail(BFT_GPU_E_LIMIT, "marks_select: at most 2^31 - 1 k-mers");
-    if (h->n_kmers == 0) CK(bft_zero_async(d_count, 8, s));
-    else {
-        CK(mk_select_scan(h, mask, (unsigned long long*)d_count, s));
-        CK(mk_select_emit(h, (uint8_t*)d_kmers_out, (char*)d_ascii_out, (uint32_t*)d_rows_out, cap, s));
+    {
+        HandleScratch::Lease lease(h->mk);
+        CK(mk_enter(h, lease, s, "marks_select"));
+        if (h->n_kmers >= (1ull << 31)) return bft_fail(BFT_GPU_E_LIMIT, "marks_select: at most 2^31 - 1 k-mers");
+        if (h->n_kmers == 0) CK(bft_zero_async(d_count, 8, s));
+        else {
+            CK(mk_select_scan(h, mask, (unsigned long long*)d_count, s));
+            CK(mk_select_emit(h, (uint8_t*)d_kmers_out, (char*)d_ascii_out, (uint32_t*)d_rows_out, cap, s));
+        }
     }
-    return mk_leave(h, s, true);
+    return bft_note_foreign_stream(h, s);
 }
 // The host form: the selection is counted on the device, and the outputs filled only when cap holds it all (as bft_gpu_kmers_by_count).
 extern "C" int bft_gpu_marks_select(bft_gpu* h, uint32_t mask, uint8_t* kmers_out, char* ascii_out, uint32_t* rows_out, uint64_t cap, uint64_t* n_out) {
@@ -608,10 +595,11 @@ extern "C" int bft_gpu_marks_select(bft_gpu* h, uint32_t mask, uint8_t* kmers_ou
     if (mask > 15) return bft_fail(BFT_GPU_E_ARG, "marks_select: the mask has one bit per flag value, 0 .. 15");
     ENTER(h);
     const hipStream_t s = h->stream;
-    CK(mk_enter(h, s, "marks_select"));
+    HandleScratch::Lease lease(h->mk);
+    CK(mk_enter(h, lease, s, "marks_select"));
     *n_out = 0;
     if (h->n_kmers >= (1ull << 31)) return bft_fail(BFT_GPU_E_LIMIT, "marks_select: at most 2^31 - 1 k-mers");
-    if (h->n_kmers == 0) return mk_leave(h, s, false);
+    if (h->n_kmers == 0) return BFT_GPU_OK;
     DevBuf dcnt;
     CK(dcnt.alloc(8));
     CK(mk_select_scan(h, mask, dcnt.as<unsigned long long>(), s));
@@ -620,10 +608,7 @@ extern "C" int bft_gpu_marks_select(bft_gpu* h, uint32_t mask, uint8_t* kmers_ou
     HIPCK(hipStreamSynchronize(s));
     *n_out = cnt;
     const bool any = kmers_out || ascii_out || rows_out;
-    if (any && cap < cnt) {
-        h->mk.release();
-        return bft_fail(BFT_GPU_E_NOSPACE, "marks_select: buffers too small");
-    }
+    if (any && cap < cnt) return bft_fail(BFT_GPU_E_NOSPACE, "marks_select: buffers too small");
     if (any && cnt) {
         const size_t kb = (size_t)cnt * h->B, ab = (size_t)cnt * (h->k + 1);
         DevBuf dk, da, dr;
@@ -636,7 +621,7 @@ extern "C" int bft_gpu_marks_select(bft_gpu* h, uint32_t mask, uint8_t* kmers_ou
         if (rows_out) HIPCK(hipMemcpyAsync(rows_out, dr.p, cnt * 4, hipMemcpyDeviceToHost, s));
         HIPCK(hipStreamSynchronize(s));
     }
-    return mk_leave(h, s, false);
+    return BFT_GPU_OK;
 }
 
 extern "C" int bft_gpu_marks_reach_dev(bft_gpu* h, const void* d_seeds, uint64_t n_seeds, const uint32_t* genome_ids, uint32_t nb_ids, uint8_t through, uint8_t to,
@@ -645,10 +630,13 @@ extern "C" int bft_gpu_marks_reach_dev(bft_gpu* h, const void* d_seeds, uint64_t
     CK(mk_check_ids(genome_ids, nb_ids));
     ENTER(h);
     const hipStream_t s = mk_stream(h, hip_stream);
-    CK(mk_enter(h, s, "marks_reach"));
-    CK(mk_check_reach(h, through, to));
-    CK(mk_reach(h, (const uint8_t*)d_seeds, n_seeds, genome_ids, nb_ids, through, to, boundary != 0, (uint8_t*)d_seed_new, (unsigned long long*)d_counts, s));
-    return mk_leave(h, s, true);
+    {
+        HandleScratch::Lease lease(h->mk);
+        CK(mk_enter(h, lease, s, "marks_reach"));
+        CK(mk_check_reach(h, through, to));
+        CK(mk_reach(h, (const uint8_t*)d_seeds, n_seeds, genome_ids, nb_ids, through, to, boundary != 0, (uint8_t*)d_seed_new, (unsigned long long*)d_counts, s));
+    }
+    return bft_note_foreign_stream(h, s);
 }
 extern "C" int bft_gpu_marks_reach(bft_gpu* h, const uint8_t* seeds, uint64_t n_seeds, const uint32_t* genome_ids, uint32_t nb_ids, uint8_t through, uint8_t to,
                                    int boundary, uint8_t* seed_new, uint64_t* counts) {
@@ -656,7 +644,8 @@ extern "C" int bft_gpu_marks_reach(bft_gpu* h, const uint8_t* seeds, uint64_t n_
     CK(mk_check_ids(genome_ids, nb_ids));
     ENTER(h);
     const hipStream_t s = h->stream;
-    CK(mk_enter(h, s, "marks_reach"));
+    HandleScratch::Lease lease(h->mk);
+    CK(mk_enter(h, lease, s, "marks_reach"));
     CK(mk_check_reach(h, through, to));
     DevBuf dk, dn, dc;
     CK(dk.alloc(n_seeds * h->B));
@@ -670,39 +659,32 @@ extern "C" int bft_gpu_marks_reach(bft_gpu* h, const uint8_t* seeds, uint64_t n_
     HIPCK(hipStreamSynchronize(s));
     if (counts)
         for (int i = 0; i < 3; i++) counts[i] = cnt[i];
-    return mk_leave(h, s, false);
+    return BFT_GPU_OK;
 }
 
 extern "C" int bft_gpu_marks_read(bft_gpu* h, uint8_t* bytes_out, uint64_t cap, uint64_t* n_bytes) {
     if (!h) return bft_fail(BFT_GPU_E_ARG, "NULL handle");
     ENTER(h);
-    CK(mk_enter(h, h->stream, "marks_read"));
+    HandleScratch::Lease lease(h->mk);
+    CK(mk_enter(h, lease, h->stream, "marks_read"));
     const uint64_t nb = bft_mk_bytes(h->n_kmers);
     if (n_bytes) *n_bytes = nb;
     if (bytes_out) {
-        if (cap < nb) {
-            h->mk.release();
-            return bft_fail(BFT_GPU_E_NOSPACE, "marks_read: buffer too small");
-        }
+        if (cap < nb) return bft_fail(BFT_GPU_E_NOSPACE, "marks_read: buffer too small");
         if (nb) HIPCK(hipMemcpyAsync(bytes_out, h->mk_flags.p, nb, hipMemcpyDeviceToHost, h->stream));
         HIPCK(hipStreamSynchronize(h->stream));
     }
-    return mk_leave(h, h->stream, false);
+    return BFT_GPU_OK;
 }
 
 extern "C" int bft_gpu_marks_write(bft_gpu* h, const uint8_t* bytes_in, uint64_t n_bytes) {
     if (!h || (!bytes_in && n_bytes)) return bft_fail(BFT_GPU_E_ARG, "NULL argument");
     ENTER(h);
-    CK(mk_enter(h, h->stream, "marks_write"));
+    HandleScratch::Lease lease(h->mk);
+    CK(mk_enter(h, lease, h->stream, "marks_write"));
     const uint64_t n = h->n_kmers, nb = bft_mk_bytes(n);
-    if (n_bytes != nb) {
-        h->mk.release();
-        return bft_fail(BFT_GPU_E_ARG, "marks_write: the array holds CEIL(k-mers / 4) bytes");
-    }
-    if ((n & 3u) && (bytes_in[nb - 1] >> (2u * (n & 3u)))) {
-        h->mk.release();
-        return bft_fail(BFT_GPU_E_ARG, "marks_write: the bits behind the last k-mer must be 0");
-    }
+    if (n_bytes != nb) return bft_fail(BFT_GPU_E_ARG, "marks_write: the array holds CEIL(k-mers / 4) bytes");
+    if ((n & 3u) && (bytes_in[nb - 1] >> (2u * (n & 3u)))) return bft_fail(BFT_GPU_E_ARG, "marks_write: the bits behind the last k-mer must be 0");
     h->mk_forest_ok = false;
     if (nb) {
         // (the last word's bytes past the array stay 0, as bft_gpu_marks_begin and the fill leave them)
@@ -710,5 +692,5 @@ extern "C" int bft_gpu_marks_write(bft_gpu* h, const uint8_t* bytes_in, uint64_t
         HIPCK(hipMemcpyAsync(h->mk_flags.p, bytes_in, nb, hipMemcpyHostToDevice, h->stream));
         HIPCK(hipStreamSynchronize(h->stream));
     }
-    return mk_leave(h, h->stream, false);
+    return BFT_GPU_OK;
 }

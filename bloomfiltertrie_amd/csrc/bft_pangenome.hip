@@ -14,7 +14,6 @@
 //                 Up to BFT_PG_LDS_GENOMES genomes the 3 G + 1 counters of a workgroup live in LDS (32 bits are enough: no counter exceeds the number
 //                 of rows, < 2^31) and reach memory once per workgroup as 64-bit atomics, zeros skipped; beyond, 64-bit atomics straight to memory
 // Integer atomics only: the results are exact and do not depend on scheduling.  No kernel needs scratch memory.
-#include <type_traits>
 
 #include "bft_dev.h"
 #include "bft_handle.h"
@@ -24,7 +23,6 @@
 
 namespace {
 
-constexpr int PG_THREADS = 256;
 constexpr int PG_ROUNDS = 64;         // rows per lane and stretch in k_pg_usage (64-row rounds of a wavefront's stretch)
 constexpr int PG_BATCH = 8;           // rounds loaded before any is counted
 constexpr int PG_IDS_PER_LANE = 16;   // consecutive dictionary ids per lane in k_pg_dict
@@ -41,9 +39,9 @@ __device__ __forceinline__ void pg_write(uint8_t* p, int len, F&& c) {
 }
 
 template <int W>
-__global__ __launch_bounds__(PG_THREADS) void k_pg_emit(const uint64_t* __restrict__ tk, uint32_t n, int k, int B, const uint32_t* __restrict__ slot,
+__global__ __launch_bounds__(BFT_LAUNCH_THREADS) void k_pg_emit(const uint64_t* __restrict__ tk, uint32_t n, int k, int B, const uint32_t* __restrict__ slot,
                                                         uint8_t* __restrict__ kmers, char* __restrict__ ascii, uint32_t* __restrict__ rows, uint64_t cap) {
-    for (uint64_t i = blockIdx.x * (uint64_t)PG_THREADS + threadIdx.x; i < n; i += (uint64_t)gridDim.x * PG_THREADS) {
+    for (uint64_t i = blockIdx.x * (uint64_t)BFT_LAUNCH_THREADS + threadIdx.x; i < n; i += (uint64_t)gridDim.x * BFT_LAUNCH_THREADS) {
         const uint32_t s = slot[i];
         if (slot[i + 1] == s || s >= cap) continue;
         if (rows) rows[s] = (uint32_t)i;
@@ -72,12 +70,12 @@ __device__ __forceinline__ uint32_t pg_wave_sum(uint32_t v) {
     return v;
 }
 
-__global__ __launch_bounds__(PG_THREADS) void k_pg_usage(uint32_t n, const uint32_t* __restrict__ tcol, uint32_t* __restrict__ usage) {
+__global__ __launch_bounds__(BFT_LAUNCH_THREADS) void k_pg_usage(uint32_t n, const uint32_t* __restrict__ tcol, uint32_t* __restrict__ usage) {
     constexpr uint64_t STRETCH = 64ull * PG_ROUNDS;  // rows per wavefront and pass
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t waves = (uint64_t)gridDim.x * (PG_THREADS / 64);
+    const uint64_t waves = (uint64_t)gridDim.x * (BFT_LAUNCH_THREADS / 64);
     uint32_t hot = BFT_PG_NONE, hot_cnt = 0;  // (hot is the same in every lane of the wavefront; hot_cnt is the lane's share)
-    for (uint64_t base = (blockIdx.x * (uint64_t)(PG_THREADS / 64) + (threadIdx.x >> 6)) * STRETCH; base < n; base += waves * STRETCH) {
+    for (uint64_t base = (blockIdx.x * (uint64_t)(BFT_LAUNCH_THREADS / 64) + (threadIdx.x >> 6)) * STRETCH; base < n; base += waves * STRETCH) {
         // the stretch's hot set: the most frequent of the sets at lanes 0, 16, 32, 48 of its first round
         const uint32_t c0 = base + lane < n ? tcol[base + lane] : BFT_PG_NONE;
         uint32_t best = BFT_PG_NONE;
@@ -129,7 +127,7 @@ __global__ __launch_bounds__(PG_THREADS) void k_pg_usage(uint32_t n, const uint3
 
 // counters: [0, G] spectrum, [G + 1, 2 G] genome_total, [2 G + 1, 3 G] genome_private
 template <bool LDS>
-__global__ __launch_bounds__(PG_THREADS) void k_pg_dict(uint32_t n_sets, uint64_t n_ids, const uint32_t* __restrict__ cs_off, const void* __restrict__ cs_ids,
+__global__ __launch_bounds__(BFT_LAUNCH_THREADS) void k_pg_dict(uint32_t n_sets, uint64_t n_ids, const uint32_t* __restrict__ cs_off, const void* __restrict__ cs_ids,
                                                         uint32_t cs_w, const uint32_t* __restrict__ usage, uint32_t G, unsigned long long* __restrict__ spectrum,
                                                         unsigned long long* __restrict__ total, unsigned long long* __restrict__ priv) {
     __shared__ uint32_t bins[LDS ? PG_LDS_BINS : 1u];
@@ -144,10 +142,10 @@ __global__ __launch_bounds__(PG_THREADS) void k_pg_dict(uint32_t n_sets, uint64_
         else if (unsigned long long* o = out(b)) atomicAdd(o, (unsigned long long)v);
     };
     if (LDS) {
-        for (uint32_t b = threadIdx.x; b < nbins; b += PG_THREADS) bins[b] = 0;
+        for (uint32_t b = threadIdx.x; b < nbins; b += BFT_LAUNCH_THREADS) bins[b] = 0;
         __syncthreads();
     }
-    const uint64_t tid = blockIdx.x * (uint64_t)PG_THREADS + threadIdx.x, nthreads = (uint64_t)gridDim.x * PG_THREADS;
+    const uint64_t tid = blockIdx.x * (uint64_t)BFT_LAUNCH_THREADS + threadIdx.x, nthreads = (uint64_t)gridDim.x * BFT_LAUNCH_THREADS;
     for (uint64_t c = tid; c < n_sets; c += nthreads) {
         const uint32_t u = usage[c], sz = cs_off[c + 1] - cs_off[c];
         if (u && sz <= G) add(sz, u);
@@ -177,7 +175,7 @@ __global__ __launch_bounds__(PG_THREADS) void k_pg_dict(uint32_t n_sets, uint64_
     }
     if (LDS) {
         __syncthreads();
-        for (uint32_t b = threadIdx.x; b < nbins; b += PG_THREADS) {
+        for (uint32_t b = threadIdx.x; b < nbins; b += BFT_LAUNCH_THREADS) {
             const uint32_t v = bins[b];
             if (v == 0) continue;
             if (unsigned long long* o = out(b)) atomicAdd(o, (unsigned long long)v);
@@ -185,44 +183,29 @@ __global__ __launch_bounds__(PG_THREADS) void k_pg_dict(uint32_t n_sets, uint64_
     }
 }
 
-dim3 pg_grid(uint64_t n) { return dim3(bft_grid_for((n + PG_THREADS - 1) / PG_THREADS)); }
-
 }  // namespace
 
 int bft_pg_emit(int W, const uint64_t* d_tk, uint64_t n, int k, int B, const BftPgScratch& p, uint8_t* d_kmers, char* d_ascii, uint32_t* d_rows, uint64_t cap,
                 hipStream_t s) {
     if (n == 0 || cap == 0 || (!d_kmers && !d_ascii && !d_rows)) return 0;
-    auto go = [&](auto KW) {
-        hipLaunchKernelGGL((k_pg_emit<KW>), pg_grid(n), dim3(PG_THREADS), 0, s, d_tk, (uint32_t)n, k, B, (const uint32_t*)p.slot, d_kmers, d_ascii, d_rows, cap);
-    };
-    switch (W) {
-    case 1: go(std::integral_constant<int, 1>()); break;
-    case 2: go(std::integral_constant<int, 2>()); break;
-    case 3: go(std::integral_constant<int, 3>()); break;
-    default: go(std::integral_constant<int, 4>()); break;
-    }
-    HIPCK(hipGetLastError());
-    return 0;
+    return bft_for_w(W, [&](auto KW) { return bft_launch256(k_pg_emit<KW>, n, s, d_tk, (uint32_t)n, k, B, (const uint32_t*)p.slot, d_kmers, d_ascii, d_rows, cap); });
 }
 
 int bft_pg_usage(uint64_t n, const uint32_t* d_tcol, const BftPgScratch& p, hipStream_t s) {
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(k_pg_usage, pg_grid((n + PG_ROUNDS - 1) / PG_ROUNDS), dim3(PG_THREADS), 0, s, (uint32_t)n, d_tcol, p.usage);
-    HIPCK(hipGetLastError());
-    return 0;
+    // (the items are lanes: each takes PG_ROUNDS rows)
+    return bft_launch256(k_pg_usage, (n + PG_ROUNDS - 1) / PG_ROUNDS, s, (uint32_t)n, d_tcol, p.usage);
 }
 
 int bft_pg_dict(uint64_t n_sets, uint64_t n_ids, const uint32_t* d_cs_off, const void* d_cs_ids, uint32_t cs_w, uint32_t G, const BftPgScratch& p,
                 unsigned long long* d_spectrum, unsigned long long* d_total, unsigned long long* d_private, hipStream_t s) {
     if (n_sets == 0 || (!d_spectrum && !d_total && !d_private)) return 0;
     const uint64_t lanes = std::max(n_sets, (n_ids + PG_IDS_PER_LANE - 1) / PG_IDS_PER_LANE);
-    if (G <= BFT_PG_LDS_GENOMES) {
-        const dim3 grid((unsigned)std::min<uint64_t>(PG_DICT_BLOCKS, (lanes + PG_THREADS - 1) / PG_THREADS));
-        hipLaunchKernelGGL(k_pg_dict<true>, grid, dim3(PG_THREADS), 0, s, (uint32_t)n_sets, n_ids, d_cs_off, d_cs_ids, cs_w, (const uint32_t*)p.usage, G, d_spectrum,
-                           d_total, d_private);
-    } else
-        hipLaunchKernelGGL(k_pg_dict<false>, pg_grid(lanes), dim3(PG_THREADS), 0, s, (uint32_t)n_sets, n_ids, d_cs_off, d_cs_ids, cs_w, (const uint32_t*)p.usage, G,
-                           d_spectrum, d_total, d_private);
+    if (G > BFT_PG_LDS_GENOMES)
+        return bft_launch256(k_pg_dict<false>, lanes, s, (uint32_t)n_sets, n_ids, d_cs_off, d_cs_ids, cs_w, (const uint32_t*)p.usage, G, d_spectrum, d_total, d_private);
+    // (the LDS form: a grid of its own, every workgroup ends with up to 3 G + 1 atomics)
+    const dim3 grid((unsigned)std::min<uint64_t>(PG_DICT_BLOCKS, (lanes + BFT_LAUNCH_THREADS - 1) / BFT_LAUNCH_THREADS));
+    hipLaunchKernelGGL(k_pg_dict<true>, grid, dim3(BFT_LAUNCH_THREADS), 0, s, (uint32_t)n_sets, n_ids, d_cs_off, d_cs_ids, cs_w, (const uint32_t*)p.usage, G, d_spectrum,
+                       d_total, d_private);
     HIPCK(hipGetLastError());
     return 0;
 }
@@ -239,8 +222,8 @@ static size_t pg_carve(uint64_t m, uint64_t sets, uint8_t* base, BftPgScratch* p
 }
 // The handle's scratch (h->pg: HandleScratch, bft_handle.h) for an index of n rows and n_sets colour sets on stream s: its own block, shared with no
 // other query, sized exactly.
-static int pg_scratch(bft_gpu* h, uint64_t n, uint64_t n_sets, hipStream_t s, BftPgScratch* p) {
-    CK(h->pg.acquire(s, false));  // (the entry points refuse a capturing stream)
+static int pg_scratch(bft_gpu* h, HandleScratch::Lease& lease, uint64_t n, uint64_t n_sets, hipStream_t s, BftPgScratch* p) {
+    CK(lease.acquire(s, false));  // (the entry points refuse a capturing stream)
     h->pg_m = std::max(n, h->pg_m);
     h->pg_sets = std::max(n_sets, h->pg_sets);
     CK(h->pg.grow(h->pg_buf, pg_carve(h->pg_m, h->pg_sets, nullptr, p), 0));
@@ -283,14 +266,14 @@ extern "C" int bft_gpu_kmers_by_count_dev(bft_gpu* h, uint32_t min_count, uint32
         CK(bft_zero_async(d_count, 8, s));
         return bft_note_foreign_stream(h, s);
     }
-    BftPgScratch p;
-    CK(pg_scratch(h, h->n_kmers, h->n_sets, s, &p));
     {
+        HandleScratch::Lease lease(h->pg);
+        BftPgScratch p;
+        CK(pg_scratch(h, lease, h->n_kmers, h->n_sets, s, &p));
         StageScope stage_scope(h, s);
         CK(pg_select(h, min_count, max_count, s, (unsigned long long*)d_count, p));
         CK(pg_emit(h, p, (uint8_t*)d_kmers_out, (char*)d_ascii_out, (uint32_t*)d_rows_out, cap, std::min<uint64_t>(cap, h->n_kmers), s));
     }
-    h->pg.release();
     return bft_note_foreign_stream(h, s);
 }
 
@@ -306,8 +289,9 @@ extern "C" int bft_gpu_kmers_by_count(bft_gpu* h, uint32_t min_count, uint32_t m
     const hipStream_t s = h->stream;
     DevBuf dcnt;
     CK(dcnt.alloc(8));
+    HandleScratch::Lease lease(h->pg);
     BftPgScratch p;
-    CK(pg_scratch(h, n, h->n_sets, s, &p));
+    CK(pg_scratch(h, lease, n, h->n_sets, s, &p));
     StageScope stage_scope(h);
     CK(pg_select(h, min_count, max_count, s, dcnt.as<unsigned long long>(), p));
     unsigned long long cnt = 0;
@@ -315,10 +299,7 @@ extern "C" int bft_gpu_kmers_by_count(bft_gpu* h, uint32_t min_count, uint32_t m
     HIPCK(hipStreamSynchronize(s));
     *n_out = cnt;
     const bool any = kmers_out || ascii_out || rows_out;
-    if (any && cap < cnt) {
-        h->pg.release();
-        return bft_fail(BFT_GPU_E_NOSPACE, "k-mer class buffers too small");
-    }
+    if (any && cap < cnt) return bft_fail(BFT_GPU_E_NOSPACE, "k-mer class buffers too small");
     if (any && cnt) {
         const size_t kb = (size_t)cnt * h->B, ab = (size_t)cnt * (h->k + 1);
         DevBuf dk, da, dr;
@@ -331,7 +312,6 @@ extern "C" int bft_gpu_kmers_by_count(bft_gpu* h, uint32_t min_count, uint32_t m
         if (rows_out) HIPCK(hipMemcpyAsync(rows_out, dr.p, cnt * 4, hipMemcpyDeviceToHost, s));
         HIPCK(hipStreamSynchronize(s));
     }
-    h->pg.release();
     return BFT_GPU_OK;
 }
 
@@ -360,13 +340,13 @@ extern "C" int bft_gpu_pangenome_stats_dev(bft_gpu* h, void* d_spectrum, void* d
     const uint32_t G = pg_genomes(h);
     if (!d_spectrum && !d_genome_total && !d_genome_private) return BFT_GPU_OK;
     if ((uint64_t)cap < (uint64_t)G + 1) return bft_fail(BFT_GPU_E_NOSPACE, "pan-genome statistics: room for nb_genomes + 1 entries is needed");
-    BftPgScratch p{};
-    if (h->n_kmers) CK(pg_scratch(h, h->n_kmers, h->n_sets, s, &p));
     {
+        HandleScratch::Lease lease(h->pg);  // (held only where there are rows)
+        BftPgScratch p{};
+        if (h->n_kmers) CK(pg_scratch(h, lease, h->n_kmers, h->n_sets, s, &p));
         StageScope stage_scope(h, s);
         CK(pg_stats(h, G, (unsigned long long*)d_spectrum, (unsigned long long*)d_genome_total, (unsigned long long*)d_genome_private, p, s));
     }
-    if (h->n_kmers) h->pg.release();
     return bft_note_foreign_stream(h, s);
 }
 
@@ -381,14 +361,14 @@ extern "C" int bft_gpu_pangenome_stats(bft_gpu* h, uint64_t* spectrum, uint64_t*
     DevBuf out;  // [spectrum G + 1 | genome_total G | genome_private G]
     CK(out.alloc(((size_t)3 * G + 1) * 8));
     unsigned long long* const d = out.as<unsigned long long>();
+    HandleScratch::Lease lease(h->pg);  // (held only where there are rows)
     BftPgScratch p{};
-    if (h->n_kmers) CK(pg_scratch(h, h->n_kmers, h->n_sets, s, &p));
+    if (h->n_kmers) CK(pg_scratch(h, lease, h->n_kmers, h->n_sets, s, &p));
     StageScope stage_scope(h);
     CK(pg_stats(h, G, d, d + G + 1, d + 2 * (size_t)G + 1, p, s));
     if (spectrum) HIPCK(hipMemcpyAsync(spectrum, d, ((size_t)G + 1) * 8, hipMemcpyDeviceToHost, s));
     if (genome_total && G) HIPCK(hipMemcpyAsync(genome_total, d + G + 1, (size_t)G * 8, hipMemcpyDeviceToHost, s));
     if (genome_private && G) HIPCK(hipMemcpyAsync(genome_private, d + 2 * (size_t)G + 1, (size_t)G * 8, hipMemcpyDeviceToHost, s));
     HIPCK(hipStreamSynchronize(s));
-    if (h->n_kmers) h->pg.release();
     return BFT_GPU_OK;
 }

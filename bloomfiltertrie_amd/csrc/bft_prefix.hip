@@ -266,8 +266,8 @@ static size_t pm_carve(uint64_t m, uint8_t* base, BftPmScratch* p) {
     return c.off;
 }
 // The handle's scratch (h->pm: HandleScratch, bft_handle.h) for a batch of n prefixes on stream s; a new block has room for half as many again.
-static int pm_scratch(bft_gpu* h, uint64_t n, hipStream_t s, bool capturing, BftPmScratch* p) {
-    CK(h->pm.acquire(s, capturing));
+static int pm_scratch(bft_gpu* h, HandleScratch::Lease& lease, uint64_t n, hipStream_t s, bool capturing, BftPmScratch* p) {
+    CK(lease.acquire(s, capturing));
     const size_t tb = bft_scan::scratch_bytes(std::max<uint64_t>(n, BFT_PM_CHUNKS) + 1);
     if (h->pm_n < n) h->pm_n = n + n / 2;
     CK(h->pm.grow(h->pm_buf, pm_carve(h->pm_n, nullptr, p), 0));
@@ -308,11 +308,13 @@ extern "C" int bft_gpu_query_prefixes_dev(bft_gpu* h, const void* d_prefixes, co
         if (d_needed) CK(bft_zero_async(d_needed, 8, s));
         return bft_note_foreign_stream(h, s);
     }
-    BftPmScratch p;
-    CK(pm_scratch(h, n, s, capturing, &p));
-    CK(pm_count(h, (const uint8_t*)d_prefixes, (const uint8_t*)d_lengths, n, (uint64_t*)d_offsets, (uint64_t*)d_needed, s, p));
-    CK(pm_emit(h, n, p, cap, (uint8_t*)d_kmers_out, (uint32_t*)d_rows_out, (uint32_t*)d_colorsets_out, s));
-    h->pm.release();
+    {
+        HandleScratch::Lease lease(h->pm);
+        BftPmScratch p;
+        CK(pm_scratch(h, lease, n, s, capturing, &p));
+        CK(pm_count(h, (const uint8_t*)d_prefixes, (const uint8_t*)d_lengths, n, (uint64_t*)d_offsets, (uint64_t*)d_needed, s, p));
+        CK(pm_emit(h, n, p, cap, (uint8_t*)d_kmers_out, (uint32_t*)d_rows_out, (uint32_t*)d_colorsets_out, s));
+    }
     return bft_note_foreign_stream(h, s);
 }
 
@@ -337,18 +339,16 @@ extern "C" int bft_gpu_query_prefixes(bft_gpu* h, const uint8_t* prefixes, const
     CK(dneed.alloc(8));
     HIPCK(hipMemcpyAsync(dp.p, prefixes, n * h->B, hipMemcpyHostToDevice, s));
     HIPCK(hipMemcpyAsync(dl.p, lengths, n, hipMemcpyHostToDevice, s));
+    HandleScratch::Lease lease(h->pm);
     BftPmScratch p;
-    CK(pm_scratch(h, n, s, false, &p));
+    CK(pm_scratch(h, lease, n, s, false, &p));
     CK(pm_count(h, dp.as<uint8_t>(), dl.as<uint8_t>(), n, doff.as<uint64_t>(), dneed.as<uint64_t>(), s, p));
     uint64_t total = 0;
     HIPCK(hipMemcpyAsync(&total, dneed.p, 8, hipMemcpyDeviceToHost, s));
     HIPCK(hipStreamSynchronize(s));
     if (needed) *needed = total;
     const bool want = kmers_out || rows_out || colorsets_out;
-    if (want && total > cap) {
-        h->pm.release();
-        return bft_fail(BFT_GPU_E_NOSPACE, "prefix match buffers too small");
-    }
+    if (want && total > cap) return bft_fail(BFT_GPU_E_NOSPACE, "prefix match buffers too small");
     if (want && total) {
         DevBuf dk, dr, dc;
         if (kmers_out) CK(dk.alloc(total * h->B));
@@ -361,6 +361,5 @@ extern "C" int bft_gpu_query_prefixes(bft_gpu* h, const uint8_t* prefixes, const
     }
     HIPCK(hipMemcpyAsync(offsets, doff.p, (n + 1) * 8, hipMemcpyDeviceToHost, s));
     HIPCK(hipStreamSynchronize(s));
-    h->pm.release();
     return BFT_GPU_OK;
 }

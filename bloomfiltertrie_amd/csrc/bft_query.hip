@@ -508,14 +508,14 @@ static int query_rows(bft_gpu* h, const uint8_t* kmers, uint64_t m, DevBuf& dk, 
 // from the dictionary, and the wavefronts stream the ids out.  No row, no sorted table ("compact_table" stays), no host round trip.
 static int colors_core(bft_gpu* h, const uint8_t* d_kmers, uint64_t n, uint64_t* d_bits64, uint64_t* d_offsets, uint32_t* d_ids, uint64_t ids_cap, uint64_t* d_needed,
                        hipStream_t s, bool fill) {
-    CK(h->qc.acquire(s, bft_stream_capturing(s)));
+    HandleScratch::Lease lease(h->qc);  // (the scratch's use ends with this function)
+    CK(lease.acquire(s, bft_stream_capturing(s)));
     if (fill && h->im.kh_lines != nullptr && !h->opt_walk_hash && bft_kh_has_kernels(h->W, h->im.kh.S) && h->im.nb_genomes < 65536u) {  // (k_colors_kh keeps list lengths in 16 bits)
         // through the k-mer hash: lookup, offsets and ids in ONE launch (k_colors_kh; the host entry point counts first and fills per chunk: the three steps below)
         // (a block of its own: the kernel writes its counter and states raw, which a block of bft_scan's -- qc_tmp -- must never see)
         const size_t sb = bft_kh_colors_scratch_bytes(n);
         CK(h->qc.grow(h->qc_kh, sb, sb / 2));
         CK(bft_timed_launch(h, s, [&] { return bft_kh_colors(h->im, d_kmers, n, h->B, d_bits64, d_offsets, d_ids, d_ids ? ids_cap : 0, d_needed, h->qc_kh.p, s); }));
-        h->qc.release();
         return 0;
     }
     const size_t tb = bft_scan::scratch_bytes(n + 1);  // (the scan's tile states)
@@ -537,7 +537,6 @@ static int colors_core(bft_gpu* h, const uint8_t* d_kmers, uint64_t n, uint64_t*
             return 0;
         }));
     }
-    h->qc.release();
     return 0;
 }
 
@@ -762,7 +761,8 @@ static int query_sequences_core(bft_gpu* h, const char* d_seqs, const uint64_t* 
                                 int canonical, uint8_t* d_rows, hipStream_t s) {
     const uint32_t G = h->im.nb_genomes, rowbytes = (G + 7) / 8;
     if (rowbytes == 0 || n_seqs == 0) return 0;
-    CK(h->sq.acquire(s, bft_stream_capturing(s)));
+    HandleScratch::Lease lease(h->sq);  // (the scratch's use ends with this function)
+    CK(lease.acquire(s, bft_stream_capturing(s)));
     auto need = [&](DevBuf& b, size_t bytes) { return h->sq.grow(b, bytes, bytes / 8); };
     // sequences per chunk: 32-bit sequence numbers
     const uint64_t chunk = 1ull << 30;
@@ -807,7 +807,6 @@ static int query_sequences_core(bft_gpu* h, const char* d_seqs, const uint64_t* 
             return 0;
         }));
     }
-    h->sq.release();
     return 0;
 }
 

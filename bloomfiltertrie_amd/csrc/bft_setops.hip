@@ -362,8 +362,9 @@ static int so_core(bft_gpu* h, const uint8_t* d_kmers, const uint32_t* d_cs, uin
         return so_zero_u32(d_found, ng, s);
     }
     CK(bft_ensure_cs_bitmaps(h));
+    HandleScratch::Lease lease(h->so);  // (the scratch's use ends with this function)
     BftSoScratch p;
-    CK(h->so.acquire(s, false));  // (the entry points refuse a capturing stream)
+    CK(lease.acquire(s, false));  // (the entry points refuse a capturing stream)
     const bool look = d_kmers != nullptr;
     CK(h->so.grow(h->so_buf, so_carve(look ? n : 0, ng, nw, op == BFT_GPU_SETOP_SYMDIFF, nullptr, &p), 0));
     so_carve(look ? n : 0, ng, nw, op == BFT_GPU_SETOP_SYMDIFF, h->so_buf.as<uint8_t>(), &p);
@@ -394,7 +395,6 @@ static int so_core(bft_gpu* h, const uint8_t* d_kmers, const uint32_t* d_cs, uin
         if (d_counts) CK(bft_timed_launch(h, s, [&] { return bft_so_count(d, p.R, ng, d_counts, s); }));
         bft_stage("set operations: rows and counts", (double)ng * nw * 4 * ((d_rows ? 1 : 0) + (d_counts ? 1 : 0)) + (double)ng * ((d_rows ? rb : 0) + (d_counts ? 4 : 0)), s);
     }
-    h->so.release();
     return 0;
 }
 

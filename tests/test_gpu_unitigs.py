@@ -2,7 +2,8 @@
 BFT.bidirected_degrees): exact against the model of tests/test_unitigs_host.py, which is written from the definition alone and proves its
 invariants on the same cases on the CPU.  Key widths W = 1..4 and both T-form tail layouts; hand-made situations at odd and even k (lone k-mer,
 homopolymer, palindromes, hairpin, two successor words on two strands, a palindromic successor, a circle and the same circle from its other strand,
-a chain of 3000 k-mers and more whose stored strand keeps flipping); one index just past the capped grid; thresholds 0, 1, 2, N, N + 1; index states
+a chain of 3000 k-mers and more whose stored strand keeps flipping); one index just past the capped grid; the whole table as one chain and as
+one cycle of 1 .. 1025 k-mers (the jumps' last round); thresholds 0, 1, 2, N, N + 1; index states
 that all give the same unitigs; an index that is not canonical; caps, NOSPACE and guard bytes; the device form on a user stream interleaved with
 simple paths, colour and prefix queries on one handle."""
 import ctypes as C
@@ -86,6 +87,19 @@ def test_grid_edge():
     t = _ingest(genomes, H.GRID_K)
     _check_all(t, model, (0,))
     assert 2 * t.info()["kmers"] > 524288
+    t.close()
+
+
+@pytest.mark.parametrize("k", H.WHOLE_KS)
+@pytest.mark.parametrize("kind", ("chain", "cycle"))
+@pytest.mark.parametrize("n", H.WHOLE_NS)
+def test_whole_table_is_one_path(n, kind, k):
+    """as tests/test_gpu_graph_edges.py's case of the same name, through the mirrored instantiations of the shared kernels"""
+    genomes, model = H.whole_case(n, kind, k)
+    t = _ingest(genomes, k)
+    _check_all(t, model, (0, 1, 2))
+    off, seqs = t.unitigs(0)
+    assert off.tolist() == [0, n + k - 1] and len(seqs) == n + k - 1  # one path
     t.close()
 
 

@@ -1,8 +1,8 @@
 """CPU-side tests of the canonical (bidirected) unitigs (no GPU).  The truth model of include/bft_gpu.h's definition -- dicts, sets and strings,
 from nothing but {k-mer string: genome set} and the row order -- with the five invariants of the definition on every index the GPU tests use; the
 checker the GPU tests compare with, shown to report doctored results (a path in its mirror orientation, a cycle started one vertex late, a palindrome
-joined to a neighbour, a hairpin joined); the new names in the header and SIGNATURES, the symbols exported; the k_ug_* kernels found, without
-scratch memory or LDS; NULL arguments refused before anything touches a device.  tests/test_gpu_unitigs.py runs the cases of this file on the GPU."""
+joined to a neighbour, a hairpin joined); the new names in the header and SIGNATURES, the symbols exported; the k_ug_* kernels and the mirrored
+instantiations of the path engine's found, without scratch memory or LDS; NULL arguments refused before anything touches a device.  tests/test_gpu_unitigs.py runs the cases of this file on the GPU."""
 import ctypes as C
 import functools
 import os
@@ -19,12 +19,16 @@ import test_prefix_cases_host as P  # noqa: E402  (t_order: the row order of the
 from bloomfiltertrie_amd import _lib, synth as S  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNELS = {"k_ug_canon", "k_ug_degrees", "k_ug_links", "k_ug_ends", "k_ug_offsets", "k_ug_spell"}
+# the family's own kernels, and the mirrored instantiations of the path engine's (csrc/bft_paths.hip: template <bool MIRRORED>) the unitigs run
+KERNELS = {"k_ug_canon", "k_ug_degrees", "k_ug_links", "k_sp_ends<true>", "k_sp_offsets<true>", "k_sp_spell<true>"}
 NAMES = ("bft_gpu_unitigs", "bft_gpu_unitigs_dev", "bft_gpu_bidirected_degrees", "bft_gpu_bidirected_degrees_dev")
 KS = (9, 18, 27, 31, 36, 63, 64, 72, 126)  # W = 1..4, both tail layouts of the T-form (k % 9 == 0 and not)
 HAND_KS = (9, 27, 36, 64)
 N_GENOMES = 4
 GRID_K, GRID_ROWS = 31, 262144  # 2n vertices just past the capped grid's 524 288 threads
+# the whole table is one path: the sizes of tests/test_graph_cases_host.py's whole tables (a chain of 2^j k-mers needs the jumps' last round)
+WHOLE_NS = (1, 2, 3, 63, 64, 65, 1023, 1024, 1025)
+WHOLE_KS = (27, 72)
 
 _COMP = str.maketrans("ACGT", "TGCA")
 
@@ -272,6 +276,20 @@ def grid_case():
     return genomes, m
 
 
+@functools.lru_cache(maxsize=None)
+def whole_case(n, kind, k):
+    """(genomes, model): the index is exactly one chain or one cycle of n canonical k-mers, one genome.  (A random line or circle: the first seed
+    whose k-mers are n rows in one path -- a circle of two letters may be its own reverse complement.)"""
+    for attempt in range(50):
+        rng = np.random.default_rng(21000 + 5000 * k + 2 * n + (kind == "cycle") + 100000 * attempt)
+        q = _rand(rng, n) if kind == "cycle" else _rand(rng, n + k - 1)
+        genomes = [[(q * (k // n + 2))[:n + k - 1] if kind == "cycle" else q]]  # (the circle read once around and k - 1 letters on)
+        m = Model(owners_of(genomes, k), k)
+        if len(m.rows) == n and [len(p) for p in m.paths(0)] == [n]:
+            return genomes, m
+    raise AssertionError((n, kind, k))
+
+
 def noncanonical_case(k):
     """(k-mers of both strands for insert_kmers, model of that index): every k-mer of a short genome and of its reverse complement"""
     g = text(S.random_genome(400, 4242 + k))
@@ -340,6 +358,17 @@ def test_grid_case_invariants():
     assert 2 * len(m.rows) > 524288
 
 
+@pytest.mark.parametrize("k", WHOLE_KS)
+@pytest.mark.parametrize("kind", ("chain", "cycle"))
+@pytest.mark.parametrize("n", WHOLE_NS)
+def test_whole_table_cases(n, kind, k):
+    _, m = whole_case(n, kind, k)
+    kept = m.invariants(0)
+    _, _, chains, cycles = m.all_paths(0)
+    assert len(m.rows) == n and len(kept) == 1 and len(m.spell(kept[0])) == n + k - 1
+    assert (len(chains), len(cycles)) == ((0, 2) if kind == "cycle" and n > 1 else (2, 0))  # the path and its mirror (a cycle of one row: a self-loop, no edge)
+
+
 def test_noncanonical_model_counts():
     kmers, m = noncanonical_case(27)
     assert m.noncanonical == sum(1 for s in kmers if s > rc(s)) > 0
@@ -400,22 +429,25 @@ def test_names_are_declared_exported_and_in_signatures():
 
 
 def test_unitig_kernels_use_no_scratch_and_no_lds():
-    """Every k_ug_* kernel (every key width): no scratch memory, no vector register spilled to it, no LDS."""
+    """Every kernel of the unitigs -- the k_ug_* and the MIRRORED instantiations of k_sp_ends, k_sp_offsets and k_sp_spell -- at every key width:
+    no scratch memory, no vector register spilled to it, no LDS."""
     subprocess.check_call(["make", "-C", _lib.CSRC, "all"], stdout=subprocess.DEVNULL)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), "k_ug_"], capture_output=True, text=True).stdout
     seen = {}
-    for line in out.splitlines()[1:]:
-        if not line.strip():
-            continue
-        vgpr, sgpr, vspill, sspill, scratch, lds, maxwg, name = line.split(None, 7)
-        m = re.search(r"(k_ug_[a-z]+)", name)
-        if not m:
-            continue
-        seen[m.group(1)] = seen.get(m.group(1), 0) + 1
-        assert int(vspill) == 0 and int(scratch) == 0 and int(lds) == 0, line
-        assert int(vgpr) <= 128, line  # (two workgroups of 256 threads per SIMD at least)
+    for pat in ("k_ug_", "k_sp_"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), pat], capture_output=True, text=True).stdout
+        for line in out.splitlines()[1:]:
+            if not line.strip():
+                continue
+            vgpr, sgpr, vspill, sspill, scratch, lds, maxwg, name = line.split(None, 7)
+            m = re.search(r"(k_ug_[a-z]+)", name) or re.search(r"(k_sp_[a-z]+)<(?:\d+, )?true>", name)
+            if not m:
+                continue
+            kernel = m.group(1) + ("<true>" if m.group(1).startswith("k_sp_") else "")
+            seen[kernel] = seen.get(kernel, 0) + 1
+            assert int(vspill) == 0 and int(scratch) == 0 and int(lds) == 0, line
+            assert int(vgpr) <= 128, line  # (two workgroups of 256 threads per SIMD at least)
     assert set(seen) == KERNELS, seen
-    assert all(seen[name] == 4 for name in ("k_ug_canon", "k_ug_degrees", "k_ug_spell")), seen  # one per key width
+    assert all(seen[name] == 4 for name in ("k_ug_canon", "k_ug_degrees", "k_sp_spell<true>")), seen  # one per key width
 
 
 def test_null_arguments_are_refused_before_any_device_work():
