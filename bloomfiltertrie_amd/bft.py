@@ -462,6 +462,52 @@ class BFT:
         _lib.check(self._lib.bft_gpu_bidirected_degrees_dev(self._h, C.c_void_p(d_degrees_ptr or 0), cap, C.c_void_p(d_noncanonical_ptr),
                                                             C.c_void_p(stream or 0)))
 
+    def unitig_graph(self, min_shared=0):
+        """The compacted coloured graph of a canonical index on the GPU (bft_gpu_unitig_graph defines it): the unitigs plus one single-k-mer segment
+        per branching k-mer, the links between oriented segments 2 * i + o, and the vertices 2 * row + o of every segment.  Returns (seg_off: uint64
+        [n_segments + 1], in characters; seqs: uint8 ASCII; link_off: uint64 [2 * n_segments + 1], by oriented segment; links: uint32 target oriented
+        segments; members: uint32, segment i from seg_off[i] - i * (k - 1) on).  An index that is not canonical raises (BFT_GPU_E_STATE)."""
+        cnt = (C.c_uint64 * 6)()
+        _lib.check(self._lib.bft_gpu_unitig_graph(self._h, int(min_shared), None, None, None, None, None, 0, 0, 0, 0, cnt))
+        ns, nc, nl = int(cnt[0]), int(cnt[1]), int(cnt[4])
+        nm = nc - ns * (self.k - 1)
+        seg_off = np.zeros(ns + 1, dtype=np.uint64)
+        link_off = np.zeros(2 * ns + 1, dtype=np.uint64)
+        seqs = np.zeros(max(1, nc), dtype=np.uint8)
+        links = np.zeros(max(1, nl), dtype=np.uint32)
+        members = np.zeros(max(1, nm), dtype=np.uint32)
+        _lib.check(self._lib.bft_gpu_unitig_graph(self._h, int(min_shared), seg_off.ctypes.data, seqs.ctypes.data, link_off.ctypes.data, links.ctypes.data,
+                                                  members.ctypes.data, ns, nc, nl, nm, cnt))
+        return seg_off, seqs[:nc], link_off, links[:nl], members[:nm]
+
+    def unitig_graph_dev(self, d_seg_off_ptr, d_seqs_ptr, d_link_off_ptr, d_links_ptr, d_members_ptr, seg_cap, chars_cap, links_cap, members_cap,
+                         d_counts_ptr, min_shared=0, stream=None):
+        """Device-resident compacted graph (bft_gpu_unitig_graph_dev): {n_segments, n_chars, longest, non-canonical rows, n_links, singles} (6 uint64)
+        at d_counts_ptr always, every output that is not 0 below its cap; no synchronisation."""
+        _lib.check(self._lib.bft_gpu_unitig_graph_dev(self._h, int(min_shared), C.c_void_p(d_seg_off_ptr or 0), C.c_void_p(d_seqs_ptr or 0),
+                                                      C.c_void_p(d_link_off_ptr or 0), C.c_void_p(d_links_ptr or 0), C.c_void_p(d_members_ptr or 0), seg_cap,
+                                                      chars_cap, links_cap, members_cap, C.c_void_p(d_counts_ptr), C.c_void_p(stream or 0)))
+
+    def unitig_colors(self, members, seg_off, op):
+        """One colour row per segment of unitig_graph (bft_gpu_unitig_colors): op ("and" / "or" / "symdiff", as combine_colorsets) over the colour sets
+        of the segment's members.  Returns (rows: uint8 [n_segments, ceil(genomes / 8)], bit g of a row = genome g; counts: uint32 genomes per row)."""
+        code = self._setop(op)
+        members = np.ascontiguousarray(members, dtype=np.uint32)
+        seg_off = np.ascontiguousarray(seg_off, dtype=np.uint64)
+        ns = max(0, len(seg_off) - 1)
+        self.build()  # (pending genomes count in the row width)
+        rb = (int(self.info()["genomes"]) + 7) // 8
+        rows = np.zeros((ns, rb), dtype=np.uint8)
+        counts = np.zeros(ns, dtype=np.uint32)
+        _lib.check(self._lib.bft_gpu_unitig_colors(self._h, members.ctypes.data if len(members) else None, len(members), seg_off.ctypes.data if len(seg_off) else None,
+                                                   ns, code, rows.ctypes.data if rows.size else None, counts.ctypes.data if ns else None))
+        return rows, counts
+
+    def unitig_colors_dev(self, d_members_ptr, n_members, d_seg_off_ptr, n_segments, op, d_rows_ptr, d_counts_ptr, stream=None):
+        """Device-resident segment colours (bft_gpu_unitig_colors_dev): rows and / or counts into the buffers that are not 0; no synchronisation."""
+        _lib.check(self._lib.bft_gpu_unitig_colors_dev(self._h, C.c_void_p(d_members_ptr or 0), n_members, C.c_void_p(d_seg_off_ptr or 0), n_segments, self._setop(op),
+                                                       C.c_void_p(d_rows_ptr or 0), C.c_void_p(d_counts_ptr or 0), C.c_void_p(stream or 0)))
+
     def components(self, genome_ids=()):
         """get_nb_connected_component (reference snippets.h, src/snippets.c:605-960) on the GPU: the connected components of the index, or of the
         sub-graph of k-mers that carry every genome id of genome_ids (strictly increasing; bft_gpu_components defines them).  Returns

@@ -16,6 +16,7 @@
 #include "../../include/bft/merge.h"
 #include "../../include/bft/snippets.h"
 #include "../../include/bft/unitigs.h"
+#include "bft_gfa.h"
 
 #define DIE(...) do { fprintf(stderr, __VA_ARGS__); exit(EXIT_FAILURE); } while (0)
 #define NOT_NULL(p, where) do { if ((p) == NULL) DIE("%s: NULL pointer\n", where); } while (0)
@@ -864,6 +865,18 @@ void extract_unitigs_to_disk(BFT* graph, int min_shared, char* filename_output) 
     NOT_NULL(filename_output, "extract_unitigs_to_disk()");
     paths_to_disk(graph, bft_gpu_unitigs, min_shared > 0 ? (uint32_t)min_shared : 0u, filename_output, "extract_unitigs_to_disk(): failed to create output file.\n",
                   "Longest unitig has %d nuc.\n", "extract_unitigs_to_disk()");
+}
+
+/* <bft/unitigs.h>: the compacted coloured graph as GFA 1 (bft_gfa.h), from bft_gpu_unitig_graph and bft_gpu_unitig_colors */
+void extract_unitig_graph_to_disk(BFT* graph, int min_shared, bool colors, char* filename_output) {
+    NOT_NULL(graph, "extract_unitig_graph_to_disk()");
+    NOT_NULL(filename_output, "extract_unitig_graph_to_disk()");
+    FILE* file = fopen(filename_output, "w");
+    if (file == NULL) DIE("extract_unitig_graph_to_disk(): failed to create output file.\n");
+    const int rc = bft_gfa_write(graph->gpu, graph->k, min_shared > 0 ? (uint32_t)min_shared : 0u, colors ? 1 : 0, file);
+    if (rc < 0) ck(rc, "extract_unitig_graph_to_disk()");
+    if (rc == 1) DIE("extract_unitig_graph_to_disk(): out of memory\n");
+    if (fclose(file) != 0 || rc) DIE("extract_unitig_graph_to_disk(): failed to write the output file.\n");
 }
 
 /* ---------------------------------------------------------------- marking (include/bft.h:143-146, src/bft.c:686-765) */

@@ -10,6 +10,7 @@
  *                         [-extract_kmers {kmers|kmers_comp} output_file]
  *                         [-genome_matrix {shared|jaccard|mash} output_file]
  *                         [-unitigs min_shared output_file]
+ *                         [-gfa min_shared colors output_file]
  *
  * It is the per-k-mer loops of src/file_io.c:89-213 (build), :651-895 (presence CSV) and :897-1020 (branching)
  * rewired to one batched GPU call per file; file reading, ASCII parsing (parseKmerCount, src/fasta.c:3-53) and CSV
@@ -22,6 +23,8 @@
  * GPU (bft_gpu_insert_sequence_file); -min_abundance N keeps the k-mers a file holds at least N times.
  * Another: -unitigs writes the canonical (bidirected) unitigs of a canonical index (bft_gpu_unitigs; min_shared 0: every k-mer) as FASTA records
  * `>unitig_<i> length=<L>`, in the call's order.
+ * Another: -gfa writes the compacted coloured graph of a canonical index (bft_gpu_unitig_graph: the unitigs, the branching k-mers as segments of their
+ * own, the links between them) as GFA 1 (bft_gfa.h); colors 1 adds the union row, the intersection row and the number of genomes of every segment.
  * Another: -genome_matrix writes the genome-by-genome shared k-mer matrix (bft_gpu_genome_matrix) as tab-separated text: a header line of the genome
  * names behind an empty first cell, then one line per genome, its name and its row -- the counts (shared, %llu) or the distances computed from
  * them (jaccard, mash: %.6f).
@@ -35,6 +38,7 @@
 #include <string.h>
 
 #include "../../include/bft_gpu.h"
+#include "bft_gfa.h"
 
 #define DIE(...) do { fprintf(stderr, __VA_ARGS__); exit(EXIT_FAILURE); } while (0) /* ERROR(), include/useful_macros.h:33-43 */
 static void ck(int rc) { if (rc) DIE("%s\n", bft_gpu_last_error()); }
@@ -373,6 +377,24 @@ static void unitigs(bft_gpu* h, const char* min_shared, const char* path) {
     free(seqs);
 }
 
+/* -gfa: the compacted graph as GFA 1 (bft_gfa.h) */
+static void gfa(bft_gpu* h, const char* min_shared, const char* colors, const char* path, int k) {
+    char* end = NULL;
+    const long t = strtol(min_shared, &end, 10);
+    if (end == min_shared || *end || t < 0) DIE("Could not parse min_shared for command -gfa.\n");
+    if (strcmp(colors, "0") != 0 && strcmp(colors, "1") != 0) DIE("colors must be 0 or 1 for command -gfa.\n");
+    FILE* f = fopen(path, "w");
+    if (!f) DIE("Cannot create %s\n", path);
+    const int rc = bft_gfa_write(h, k, (uint32_t)t, colors[0] == '1', f);
+    if (rc < 0 || rc == 1) { /* (nothing was written: no empty file stays behind) */
+        fclose(f);
+        remove(path);
+    }
+    if (rc < 0) ck(rc);
+    if (rc == 1) DIE("-gfa: out of memory\n");
+    if (fclose(f) != 0 || rc) DIE("Cannot write %s\n", path);
+}
+
 int main(int argc, char** argv) {
     if (argc >= 2 && (strcmp(argv[1], "--version") == 0 || strcmp(argv[1], "-v") == 0)) { /* src/main.c:51-55 */
         fprintf(stderr, "0.8 (%s)\n", bft_gpu_version());
@@ -387,7 +409,8 @@ int main(int argc, char** argv) {
             "[-query_sequences threshold {canonical|non_canonical} list_sequence_files]\n"
             "[-extract_kmers {kmers|kmers_comp} output_file]\n"
             "[-genome_matrix {shared|jaccard|mash} output_file]\n"
-            "[-unitigs min_shared output_file]\n\n");
+            "[-unitigs min_shared output_file]\n"
+            "[-gfa min_shared colors output_file]\n\n");
     bft_gpu* h = NULL;
     int k = 0, i = 0;
     char buffer[2048];
@@ -449,6 +472,12 @@ int main(int argc, char** argv) {
         }
         if (strcmp(argv[i], "-genome_matrix") == 0) { genome_matrix(h, argv[i + 1], argv[i + 2], k, nb_genomes, names); continue; }
         if (strcmp(argv[i], "-unitigs") == 0) { unitigs(h, argv[i + 1], argv[i + 2]); continue; }
+        if (strcmp(argv[i], "-gfa") == 0) { /* four arguments */
+            if (i + 3 >= argc) DIE("-gfa min_shared colors output_file\n");
+            gfa(h, argv[i + 1], argv[i + 2], argv[i + 3], k);
+            i++;
+            continue;
+        }
         const int binary = strcmp(argv[i + 1], "kmers_comp") == 0;
         if (!binary && strcmp(argv[i + 1], "kmers") != 0) DIE("Unrecognized type of input files for %s.\n", argv[i]);
         if (strcmp(argv[i], "-extract_kmers") == 0) { extract_kmers(h, argv[i + 2], k, binary); continue; }

@@ -3,7 +3,7 @@
 // in: .bft files, the blob, the read-outs, the width of the dictionary's ids; over the tables of bft_stored.h), bft_derive.hip (what the
 // handle derives from a committed image, bft_derive.h: root tables, k-mer hash, node prefix hash, launch shape, compact table), bft_query.hip (the k-mer and
 // sequence queries, their tuner, the claim slots), bft_run.hip (the build's run stage, the sort and scan test hooks) and the analysis families
-// bft_prefix.hip, bft_paths.hip (the path engine and the simple paths), bft_unitigs.hip (its mirrored family), bft_components.hip, bft_pangenome.hip, bft_genome_matrix.hip, bft_subgraph.hip, bft_marking.hip, bft_setops.hip, bft_union.hip, bft_ingest.hip.
+// bft_prefix.hip, bft_paths.hip (the path engine and the simple paths), bft_unitigs.hip (its mirrored family), bft_cgraph.hip (the compacted graph over it), bft_components.hip, bft_pangenome.hip, bft_genome_matrix.hip, bft_subgraph.hip, bft_marking.hip, bft_setops.hip, bft_union.hip, bft_ingest.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

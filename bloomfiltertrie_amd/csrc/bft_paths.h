@@ -65,7 +65,7 @@ struct BftSpHeadLen {
 // What tells the two families apart on the host.
 struct BftPathFamily {
     bool mirrored;             // vertices: false = the n rows, true = the 2n oriented rows
-    uint32_t counts_bytes;     // of d_counts = {n_paths, n_chars, longest[, the family's own]}: 24 or 32
+    uint32_t counts_bytes;     // of d_counts = {n_paths, n_chars, longest[, the family's own]}: 24, 32 or 48
     const char* name;          // first word of every stage name and of the limit's message
     const char* ends_stage;    // the stage of the ends (named by what the family's ends decide)
     const char* capture_msg;   // a capturing stream is refused with this
@@ -82,6 +82,17 @@ int bft_sp_prepare(bft_gpu* h, const char* what);
 // vertices (0: none -- the bucket starts alone), the scans' temporary for nv <= m of them, a degree byte for each of deg_rows rows (0: none).
 // The block is sized exactly for m
 int bft_sp_scratch(bft_gpu* h, HandleScratch::Lease& lease, uint64_t m, uint64_t nv, uint64_t deg_rows, hipStream_t s, BftSpScratch* p);
+// The steps of a call of family f on stream s, for a caller that puts work of its own between them (bft_cgraph.hip).  d_counts: f.counts_bytes.
+//   bft_paths_scratch  the family's scratch through `lease`
+//   bft_paths_trace    d_counts zeroed; the family's front, the jumps, the ends: {head, distance} per vertex (bft_sp_hd(p, *fin)), the length of each
+//                      (kept) path at its head's indeg[], the longest into d_counts[2].  st[*fin] is free afterwards
+//   bft_paths_number   both scans: pred[] = the number of the path a (kept) head starts, choff[] = where it begins; d_counts[0 .. 1]
+//   bft_paths_emit     offsets (paths_cap + 1 entries at most) and characters (below chars_cap); either may be null
+int bft_paths_scratch(bft_gpu* h, const BftPathFamily& f, HandleScratch::Lease& lease, hipStream_t s, BftSpScratch* p);
+int bft_paths_trace(bft_gpu* h, const BftPathFamily& f, uint32_t min_shared, hipStream_t s, unsigned long long* d_counts, const BftSpScratch& p, int* fin);
+int bft_paths_number(bft_gpu* h, const BftPathFamily& f, hipStream_t s, unsigned long long* d_counts, const BftSpScratch& p, int fin);
+int bft_paths_emit(bft_gpu* h, const BftPathFamily& f, const BftSpScratch& p, int fin, uint64_t* d_offsets, uint64_t paths_cap, char* d_seqs, uint64_t chars_cap,
+                   const unsigned long long* d_counts, hipStream_t s);
 // bft_gpu_simple_paths_dev / bft_gpu_unitigs_dev and bft_gpu_simple_paths / bft_gpu_unitigs for the family f (include/bft_gpu.h)
 int bft_paths_dev(bft_gpu* h, const BftPathFamily& f, uint32_t min_shared, void* d_offsets, void* d_seqs, uint64_t paths_cap, uint64_t chars_cap, void* d_counts,
                   void* hip_stream);

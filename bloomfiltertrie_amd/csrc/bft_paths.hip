@@ -26,7 +26,7 @@
 //   k_sp_offsets  offsets[path] from the (kept) heads
 //   k_sp_spell    a head writes its k nucleotides, every other node its last one at offset + k - 1 + distance.  MIRRORED: the vertices of kept
 //                 paths alone, an odd vertex from the reverse complement of its row (its last nucleotide: the complement of s[0])
-// and on the host the scratch (bft_sp_scratch), the chain of launches with its stages (sp_count, sp_emit) and both forms of the entry point
+// and on the host the scratch (bft_sp_scratch), the chain of launches with its stages (bft_paths_trace, bft_paths_number, bft_paths_emit: also run by bft_cgraph.hip) and both forms of the entry point
 // (bft_paths_dev, bft_paths_host), driven by a family's BftPathFamily.
 // No kernel needs LDS or scratch memory.
 #include "bft_dev.h"
@@ -256,25 +256,23 @@ int bft_sp_prepare(bft_gpu* h, const char* what) {
     return 0;
 }
 
-namespace {
-
-uint64_t sp_vertices(const bft_gpu* h, const BftPathFamily& f) { return f.mirrored ? 2 * h->n_kmers : h->n_kmers; }
+static uint64_t sp_vertices(const bft_gpu* h, const BftPathFamily& f) { return f.mirrored ? 2 * h->n_kmers : h->n_kmers; }
 // The scratch of a call of family f.  (The arrays' places in the block are part of what a call costs -- the jumps read them at random --, so each
 // family keeps its rule: the rows carve for the most rows the handle has seen, h->sp_m; the mirrored model for its 2n vertices, and a degree byte per row.)
-int sp_family_scratch(bft_gpu* h, const BftPathFamily& f, HandleScratch::Lease& lease, hipStream_t s, BftSpScratch* p) {
+int bft_paths_scratch(bft_gpu* h, const BftPathFamily& f, HandleScratch::Lease& lease, hipStream_t s, BftSpScratch* p) {
     const uint64_t n = h->n_kmers;
     if (f.mirrored) return bft_sp_scratch(h, lease, 2 * n, 2 * n, n, s, p);
     h->sp_m = std::max(n, h->sp_m);
     return bft_sp_scratch(h, lease, h->sp_m, n, 0, s, p);
 }
 // a stage named "<family>: <what>" (the name is put together only where "build_stages" is on)
-void sp_stage(const bft_gpu* h, const BftPathFamily& f, const char* what, double bytes, hipStream_t s) {
+static void sp_stage(const bft_gpu* h, const BftPathFamily& f, const char* what, double bytes, hipStream_t s) {
     if (h->opt_build_stages) bft_stage((std::string(f.name) + ": " + what).c_str(), bytes, s);
 }
 
-// The family's front, jumps, ends and both scans on stream s: d_counts = {n_paths, n_chars, longest[, ...]} (f.counts_bytes, device); *fin: the
-// jumps' last buffer.  With "build_stages" on, every step is a stage (bft_gpu_build_stages), its bytes those its algorithm reads and writes.
-int sp_count(bft_gpu* h, const BftPathFamily& f, uint32_t t, hipStream_t s, unsigned long long* d_counts, const BftSpScratch& p, int* fin) {
+// The family's front, jumps and ends on stream s: d_counts = {., ., longest[, ...]} (f.counts_bytes, device, zeroed here); *fin: the jumps' last
+// buffer.  With "build_stages" on, every step is a stage (bft_gpu_build_stages), its bytes those its algorithm reads and writes.
+int bft_paths_trace(bft_gpu* h, const BftPathFamily& f, uint32_t t, hipStream_t s, unsigned long long* d_counts, const BftSpScratch& p, int* fin) {
     const uint64_t n = h->n_kmers, nv = sp_vertices(h, f);
     const double nd = (double)n, vd = (double)nv;
     CK(bft_zero_async(d_counts, f.counts_bytes, s));
@@ -289,15 +287,26 @@ int sp_count(bft_gpu* h, const BftPathFamily& f, uint32_t t, hipStream_t s, unsi
     sp_stage(h, f, "pointer jumping", vd * 48 * rounds, s);
     CK(bft_timed_launch(h, s, [&] { return sp_ends(f.mirrored, nv, h->k, p, cur, d_counts + 2, s); }));
     bft_stage(f.ends_stage, f.mirrored ? vd * (16 + 1 + 4 + 8) + nd * 4 : nd * (16 + 1 + 4 + 8 + 4), s);
-    const uint2* hd = bft_sp_hd(p, cur);
+    return 0;
+}
+// Both scans over what the ends left: the (kept) heads numbered in ascending vertex (pred[]), their paths placed (choff[]); d_counts[0 .. 1] =
+// {n_paths, n_chars}
+int bft_paths_number(bft_gpu* h, const BftPathFamily& f, hipStream_t s, unsigned long long* d_counts, const BftSpScratch& p, int fin) {
+    const uint64_t n = h->n_kmers, nv = sp_vertices(h, f);
+    const double nd = (double)n, vd = (double)nv;
+    const uint2* hd = bft_sp_hd(p, fin);
     if (f.mirrored) CK(bft_timed_launch(h, s, [&] { return bft_scan::exclusive_sum<uint32_t>(BftSpHeadOf<true>{hd, nv, p.indeg}, p.pred, nv, s, h->sp_tmp, d_counts, false); }));
     else CK(bft_timed_launch(h, s, [&] { return bft_scan::exclusive_sum<uint32_t>(BftSpHead{hd, nv}, p.pred, nv, s, h->sp_tmp, d_counts, false); }));
     CK(bft_timed_launch(h, s, [&] { return bft_scan::exclusive_sum<uint64_t>(BftSpHeadLen{hd, p.indeg, nv}, p.choff, nv, s, h->sp_tmp, d_counts + 1, false); }));
     sp_stage(h, f, "two scans (paths, characters)", f.mirrored ? vd * (8 + 4 + 4 + 8 + 4 + 8) : nd * (8 + 4 + 8 + 4 + 8), s);
     return 0;
 }
-// offsets (paths_cap + 1 entries at most) and characters (chars_cap at most) of the paths sp_count counted
-int sp_emit(bft_gpu* h, const BftPathFamily& f, const BftSpScratch& p, int fin, uint64_t* d_offsets, uint64_t paths_cap, char* d_seqs, uint64_t chars_cap,
+static int sp_count(bft_gpu* h, const BftPathFamily& f, uint32_t t, hipStream_t s, unsigned long long* d_counts, const BftSpScratch& p, int* fin) {
+    CK(bft_paths_trace(h, f, t, s, d_counts, p, fin));
+    return bft_paths_number(h, f, s, d_counts, p, *fin);
+}
+// offsets (paths_cap + 1 entries at most) and characters (chars_cap at most) of the paths the scans numbered and placed
+int bft_paths_emit(bft_gpu* h, const BftPathFamily& f, const BftSpScratch& p, int fin, uint64_t* d_offsets, uint64_t paths_cap, char* d_seqs, uint64_t chars_cap,
             const unsigned long long* d_counts, hipStream_t s) {
     const uint64_t n = h->n_kmers, nv = sp_vertices(h, f);
     if (d_offsets) CK(bft_timed_launch(h, s, [&] { return sp_offsets(f.mirrored, nv, p, fin, d_offsets, paths_cap, d_counts, s); }));
@@ -306,8 +315,6 @@ int sp_emit(bft_gpu* h, const BftPathFamily& f, const BftSpScratch& p, int fin, 
     sp_stage(h, f, "spelling", f.mirrored ? (double)n * 2 * (8.0 * h->W + 8 + 4 + 8 + 1) : (double)n * (8.0 * h->W + 8 + 8 + 1), s);
     return 0;
 }
-
-}  // namespace
 
 int bft_paths_dev(bft_gpu* h, const BftPathFamily& f, uint32_t min_shared, void* d_offsets, void* d_seqs, uint64_t paths_cap, uint64_t chars_cap, void* d_counts,
                   void* hip_stream) {
@@ -324,11 +331,11 @@ int bft_paths_dev(bft_gpu* h, const BftPathFamily& f, uint32_t min_shared, void*
     {
         HandleScratch::Lease lease(h->sp);
         BftSpScratch p;
-        CK(sp_family_scratch(h, f, lease, s, &p));
+        CK(bft_paths_scratch(h, f, lease, s, &p));
         StageScope stage_scope(h, s);
         int fin = 0;
         CK(sp_count(h, f, min_shared, s, (unsigned long long*)d_counts, p, &fin));
-        CK(sp_emit(h, f, p, fin, (uint64_t*)d_offsets, paths_cap, (char*)d_seqs, chars_cap, (const unsigned long long*)d_counts, s));
+        CK(bft_paths_emit(h, f, p, fin, (uint64_t*)d_offsets, paths_cap, (char*)d_seqs, chars_cap, (const unsigned long long*)d_counts, s));
     }
     return bft_note_foreign_stream(h, s);
 }
@@ -349,7 +356,7 @@ int bft_paths_host(bft_gpu* h, const BftPathFamily& f, uint32_t min_shared, uint
     CK(dcnt.alloc(f.counts_bytes));
     HandleScratch::Lease lease(h->sp);
     BftSpScratch p;
-    CK(sp_family_scratch(h, f, lease, s, &p));
+    CK(bft_paths_scratch(h, f, lease, s, &p));
     StageScope stage_scope(h);
     int fin = 0;
     CK(sp_count(h, f, min_shared, s, dcnt.as<unsigned long long>(), p, &fin));
@@ -364,7 +371,7 @@ int bft_paths_host(bft_gpu* h, const BftPathFamily& f, uint32_t min_shared, uint
         DevBuf doff, dseq;
         if (offsets) CK(doff.alloc((cnt[0] + 1) * 8));
         if (seqs && cnt[1]) CK(dseq.alloc(cnt[1]));
-        CK(sp_emit(h, f, p, fin, offsets ? doff.as<uint64_t>() : nullptr, cnt[0], seqs ? dseq.as<char>() : nullptr, cnt[1], dcnt.as<unsigned long long>(), s));
+        CK(bft_paths_emit(h, f, p, fin, offsets ? doff.as<uint64_t>() : nullptr, cnt[0], seqs ? dseq.as<char>() : nullptr, cnt[1], dcnt.as<unsigned long long>(), s));
         if (offsets) HIPCK(hipMemcpyAsync(offsets, doff.p, (cnt[0] + 1) * 8, hipMemcpyDeviceToHost, s));
         if (seqs && cnt[1]) HIPCK(hipMemcpyAsync(seqs, dseq.p, cnt[1], hipMemcpyDeviceToHost, s));
         HIPCK(hipStreamSynchronize(s));

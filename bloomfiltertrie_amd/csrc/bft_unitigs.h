@@ -23,3 +23,7 @@ int bft_ug_degrees(int W, const uint64_t* d_tk, uint64_t n, int k, const BftSpSc
                    hipStream_t s);
 // nodes, edges and the first state of the jumps (st[0]) of the 2n vertices
 int bft_ug_links(uint64_t n, uint32_t t, const uint32_t* d_tcol, const uint32_t* d_cs_off, const void* d_cs_ids, uint32_t cs_w, const BftSpScratch& p, hipStream_t s);
+// The unitigs' front (the BftPathFamily::front of the mirrored family) with its stages named "<family>: ...": canonicity (into d_counts[3]), buckets,
+// degrees of both orientations, links.  bft_ug_check: the family's check (BFT_GPU_E_STATE where counts[3] != 0)
+int bft_ug_front(bft_gpu* h, const char* family, uint32_t min_shared, hipStream_t s, unsigned long long* d_counts, const BftSpScratch& p);
+int bft_ug_check(const unsigned long long* counts);

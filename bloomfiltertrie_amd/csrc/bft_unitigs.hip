@@ -161,24 +161,29 @@ int bft_ug_links(uint64_t n, uint32_t t, const uint32_t* d_tcol, const uint32_t*
 // ------------------------------------------------------------------------------------------------
 // the C-ABI entry points: the unitigs through the path engine, the degrees on their own
 // ------------------------------------------------------------------------------------------------
+// a stage named "<family>: <what>" (the name is put together only where "build_stages" is on)
+static void ug_stage(const bft_gpu* h, const char* family, const char* what, double bytes, hipStream_t s) {
+    if (h->opt_build_stages) bft_stage((std::string(family) + ": " + what).c_str(), bytes, s);
+}
 // canonicity (into d_counts[3]), buckets, degrees of both orientations, links
-static int ug_front(bft_gpu* h, uint32_t t, hipStream_t s, unsigned long long* d_counts, const BftSpScratch& p) {
+int bft_ug_front(bft_gpu* h, const char* family, uint32_t t, hipStream_t s, unsigned long long* d_counts, const BftSpScratch& p) {
     const uint64_t n = h->n_kmers;
     const int W = h->W, k = h->k;
     const uint64_t* tk = h->d_tk.as<uint64_t>();
     const double nd = (double)n, rowb = 8.0 * W;
     CK(bft_timed_launch(h, s, [&] { return bft_ug_canonicity(W, tk, n, k, d_counts + 3, s); }));
-    bft_stage("unitigs: canonicity", nd * rowb, s);
+    ug_stage(h, family, "canonicity", nd * rowb, s);
     CK(bft_timed_launch(h, s, [&] { return bft_sp_buckets(W, tk, n, k, p, s); }));
-    bft_stage("unitigs: buckets of the table", (double)((1ull << p.sb) + 1) * 4, s);
+    ug_stage(h, family, "buckets of the table", (double)((1ull << p.sb) + 1) * 4, s);
     CK(bft_timed_launch(h, s, [&] { return bft_ug_degrees(W, tk, n, k, p, p.deg, n, true, p.succ, s); }));
-    bft_stage("unitigs: bidirected degrees and successors", nd * (rowb + 1 + 8), s);
+    ug_stage(h, family, "bidirected degrees and successors", nd * (rowb + 1 + 8), s);
     CK(bft_timed_launch(h, s, [&] { return bft_ug_links(n, t, h->d_tcol.as<uint32_t>(), h->d_cs_off.as<uint32_t>(), h->d_cs_ids.p, h->cs_w, p, s); }));
-    bft_stage("unitigs: nodes and edges", 2 * nd * (12 + 2 + (t ? 8 : 0) + 1 + 16), s);
+    ug_stage(h, family, "nodes and edges", 2 * nd * (12 + 2 + (t ? 8 : 0) + 1 + 16), s);
     return 0;
 }
+static int ug_front(bft_gpu* h, uint32_t t, hipStream_t s, unsigned long long* d_counts, const BftSpScratch& p) { return bft_ug_front(h, "unitigs", t, s, d_counts, p); }
 // the host-buffer form fills nothing where the index is not canonical
-static int ug_check(const unsigned long long* cnt) {
+int bft_ug_check(const unsigned long long* cnt) {
     if (cnt[3]) return bft_fail(BFT_GPU_E_STATE, "unitigs: the index is not canonical (" + std::to_string(cnt[3]) + " k-mers above their reverse complement)");
     return 0;
 }
@@ -191,7 +196,7 @@ static const BftPathFamily UG_FAMILY = {
     "unitigs recorded into a graph: not supported (the table may have to come back, scratch may grow)",
     "unitig buffers too small",
     ug_front,
-    ug_check,
+    bft_ug_check,
 };
 
 extern "C" int bft_gpu_unitigs_dev(bft_gpu* h, uint32_t min_shared, void* d_offsets, void* d_seqs, uint64_t paths_cap, uint64_t chars_cap, void* d_counts,

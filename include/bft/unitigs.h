@@ -20,6 +20,17 @@ extern "C" {
  * on stderr and exit(EXIT_FAILURE), as everywhere in <bft/bft.h>. */
 void extract_unitigs_to_disk(BFT* graph, int min_shared, char* filename_output);
 
+/* The compacted coloured graph of a canonical index (bft_gpu_unitig_graph defines it: the unitigs above, one segment more for every branching
+ * k-mer, and the links between oriented segments) written to filename_output as GFA 1:
+ *   H  VN:Z:1.0  kl:i:<k>
+ *   S  <i>  <sequence>  LN:i:<length>              one per segment, in the call's order; with colors also
+ *      cu:H:<row>  ci:H:<row>  gc:i:<n>            the genomes that hold a k-mer of the segment (union), those that hold all of them (intersection) --
+ *                                                  CEIL(nb_genomes / 8) bytes, genome g at bit g % 8 of byte g / 8, two hexadecimal digits per byte --
+ *                                                  and the number of genomes in the union
+ *   L  <i>  <+|->  <j>  <+|->  <k-1>M              one per link, in the order of the link lists: both mirror forms are written
+ * (fields separated by tabs).  min_shared as for extract_unitigs_to_disk.  Errors print a message on stderr and exit(EXIT_FAILURE). */
+void extract_unitig_graph_to_disk(BFT* graph, int min_shared, bool colors, char* filename_output);
+
 #ifdef __cplusplus
 }
 #endif

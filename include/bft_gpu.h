@@ -462,6 +462,50 @@ int bft_gpu_bidirected_degrees(bft_gpu* h, uint8_t* degrees, uint64_t cap, uint6
  * d_degrees (may be NULL) the bytes of the rows below cap.  Not inside a graph capture (BFT_GPU_E_ARG). */
 int bft_gpu_bidirected_degrees_dev(bft_gpu* h, void* d_degrees, uint64_t cap, void* d_noncanonical, void* hip_stream);
 
+/* The compacted coloured graph of a CANONICAL index: the unitigs completed to a cover of the index, the links between them, the k-mers of each (and,
+ * through bft_gpu_unitig_colors, a colour row of each).  An extension: the reference has no counterpart.  Vertices 2 * row + o, words, flip,
+ * successors, out, nodes, edges, kept paths and t = min_shared are exactly those of bft_gpu_unitigs.
+ *   eligible row      |C(s)| >= t (every row at t = 0);
+ *   segments          the kept paths of bft_gpu_unitigs(t), plus one segment of the single vertex (s, 0) for every eligible row that is NOT a node
+ *                     (the branching k-mers), numbered in ascending id of their first vertex -- the two kinds interleave.  Every eligible row lies in
+ *                     exactly one segment; the segments that are not such singles are, in order, byte for byte the output of bft_gpu_unitigs(t);
+ *   oriented segment  2 * i + o.  (i, 0) reads segment i = p[0] .. p[-1] as spelled: its first vertex is p[0], its last p[-1].  (i, 1) is its reverse
+ *                     complement: first vertex flip(p[-1]), last vertex flip(p[0]);
+ *   links             of an oriented segment A with last vertex e: for every successor vertex w of e (over all up to four represented words; a
+ *                     palindromic word is the vertex (y, 0), as in the degrees) whose row is eligible and, for t > 0, |C(e) & C(w)| >= t: A -> B, B the
+ *                     oriented segment whose first vertex is w (w always is one).  The targets of one A come in ascending id; the overlap is always
+ *                     k - 1 nucleotides.  A cycle has the self links S+ -> S+ and S- -> S-, a hairpin gives S+ -> S-, a homopolymer a self loop.  The
+ *                     link set is mirror-symmetric (A -> B iff B ^ 1 -> A ^ 1) once the two orientations of a palindromic single-k-mer segment are
+ *                     identified: links INTO a palindrome always name its + orientation (2 * i), the only asymmetry; the link lists of its two
+ *                     orientations are equal;
+ *   members           the vertex ids of a segment in path order: segment i occupies members[seg_off[i] - i (k - 1) .. seg_off[i + 1] - (i + 1) (k - 1)).
+ * Outputs: seg_off (n_segments + 1 character offsets into seqs), seqs (ASCII ACGT), link_off (2 * n_segments + 1 entries, indexed by oriented segment),
+ * links (links[link_off[A] .. link_off[A + 1]): the targets of A, oriented segments), members.  seg_off and link_off share seg_cap (segments), seqs
+ * has chars_cap bytes, links links_cap and members members_cap entries.  Every output may be NULL; with all NULL the call only counts.
+ * counts (6 x uint64) = {n_segments, n_chars, longest segment in characters, rows with s > rc(s), n_links, single-k-mer segments that are no unitig};
+ * n_members = n_chars - n_segments (k - 1).  A cap too small for an output that is not NULL: BFT_GPU_E_NOSPACE, counts filled, nothing else written.
+ * An index that is not canonical: BFT_GPU_E_STATE, counts filled, nothing else written.  The empty index: seg_off[0] = link_off[0] = 0.  Pending
+ * insertions, "compact_table", kernel time, "build_stages" (stage names start "unitig graph:") and the limit of 2^31 - 1 k-mers: as bft_gpu_unitigs,
+ * whose scratch the call uses (nothing is added to its 107 bytes per k-mer): the calls are serialised on a handle. */
+int bft_gpu_unitig_graph(bft_gpu* h, uint32_t min_shared, uint64_t* seg_off, char* seqs, uint64_t* link_off, uint32_t* links, uint32_t* members,
+                         uint64_t seg_cap, uint64_t chars_cap, uint64_t links_cap, uint64_t members_cap, uint64_t counts[6]);
+/* The same into device buffers on hip_stream (NULL = the handle's stream), without host synchronisation: d_counts (6 x uint64) is always written;
+ * d_seg_off receives its entries j <= seg_cap, d_link_off its entries j <= 2 * seg_cap, d_seqs, d_links and d_members what lies below their caps;
+ * nothing is written beyond any cap.  When d_counts[3] != 0 the index is not canonical and the other outputs are unspecified.  Not inside a graph
+ * capture (BFT_GPU_E_ARG). */
+int bft_gpu_unitig_graph_dev(bft_gpu* h, uint32_t min_shared, void* d_seg_off, void* d_seqs, void* d_link_off, void* d_links, void* d_members,
+                             uint64_t seg_cap, uint64_t chars_cap, uint64_t links_cap, uint64_t members_cap, void* d_counts, void* hip_stream);
+/* One colour row per segment: op (BFT_GPU_SETOP_AND / _OR / _SYMDIFF, below) over the colour sets of its members -- OR: the genomes that hold a k-mer
+ * of the segment, AND: those that hold all of it.  members and seg_off are what bft_gpu_unitig_graph returned (segment i: the members from
+ * seg_off[i] - i (k - 1) on).  rows (n_segments rows of CEIL(nb_genomes / 8) bytes) and counts (genomes per row) are laid out as by
+ * bft_gpu_combine_colorsets, which reduces them; either may be NULL.  Host form: a member >= 2 * n_kmers, offsets that grow by less than k - 1 and a
+ * last segment behind n_members are BFT_GPU_E_ARG, and nothing is written.  Device form: such a member is the absent k-mer, such a segment is empty;
+ * nothing is read outside the inputs.  Needs the sorted table ("compact_table": it comes back).  Not inside a graph capture (BFT_GPU_E_ARG). */
+int bft_gpu_unitig_colors(bft_gpu* h, const uint32_t* members, uint64_t n_members, const uint64_t* seg_off, uint64_t n_segments, int op, uint8_t* rows,
+                          uint32_t* counts);
+int bft_gpu_unitig_colors_dev(bft_gpu* h, const void* d_members, uint64_t n_members, const void* d_seg_off, uint64_t n_segments, int op, void* d_rows,
+                              void* d_counts, void* hip_stream);
+
 /* Connected components:get_nb_connected_component(bft, &nb, BFS | DFS) and (..., BFS_subgraph | DFS_subgraph, nb_id_genomes, ids...) (reference
  * snippets.h, src/snippets.c:605-960) without the walk, over the whole graph (nb_ids = 0) or the sub-graph of genome_ids.
  *   vertices  the stored k-mers; in a sub-graph, only the members: k-mers whose colour set holds EVERY id of genome_ids;
