@@ -129,7 +129,7 @@ SIGNATURES = {
     "bft_gpu_group_query_branching_dev": (C.c_int, [_P, _P, _P, _P, _P, _P]),
 }
 
-# test hooks: exported by the library, not part of include/bft_gpu.h (csrc/bft_assemble.hip; tests/test_gpu_intern_edges.py)
+# test hooks: exported by the library, not part of include/bft_gpu.h (csrc/bft_intern.hip; tests/test_gpu_intern_edges.py)
 TEST_HOOKS = {
     # (d_seg_off, d_ids, nk, np, mode, narrow_w, distinct_hint, d_tcol, d_cs_off, cs_off_cap, d_cs_ids, cs_ids_cap, d_narrow, counts[5], hip_stream)
     "bft_gpu_test_intern": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, C.c_uint64, _P, _P, C.c_uint64, _P, C.c_uint64, _P, C.POINTER(C.c_uint64), _P]),

@@ -1,6 +1,6 @@
 // bft_cs_sig.h -- the signature of a colour set (the sorted genome-id list of a k-mer): a sum of mixed ids -- order-free, so that the
 // elements can be added in any order by any lane -- mixed with the length.  The ORDER of the distinct signatures numbers the colour sets of
-// an image (bft_assemble.hip: k_cs_sig over the id lists, then a hash of the signatures): any path that makes signatures must make these.
+// an image (bft_intern.hip: k_cs_sig over the id lists, then a hash of the signatures): any path that makes signatures must make these.
 // The exact pass, taken when two different sets share a signature, sorts on all 64 bits as well and numbers the sets of one signature by a
 // second key, then by the first k-mer that holds them: the same order wherever the signatures differ (tests/test_gpu_intern_edges.py holds
 // both paths to a restatement of this file).

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/bft_gpu.h"
+#include "bft_assemble.h"
 #include "bft_handle.h"
 #include "bft_index.h"
 #include "bft_sort.h"

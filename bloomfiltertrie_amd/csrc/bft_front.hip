@@ -24,6 +24,7 @@
 // One read and one write of the array for all the remaining bits, where a device-wide LSD sort spends a pass per 8 bits
 // (a library radix sort: 7 passes over 2x10^8 composites, 7.6 ms; its segmented sort of the same buckets: 4.5 ms; these kernels: 2.0 ms).
 #include "bft_dev.h"
+#include "bft_front.h"
 #include "bft_scan.h"
 #include "bft_sort.h"
 #include <mutex>

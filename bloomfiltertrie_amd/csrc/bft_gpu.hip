@@ -6,7 +6,7 @@
 //   bft_kernels_query.h  k_pack_to_tform (packed 2-bit k-mers -> T-form words: the per-level rev[]/rotation work of
 //                        src/presenceNode.c:1327-1371 done once per k-mer; over the declarations of bft_walk.h)
 // The bulk build turns the log into a sorted, de-duplicated run in bft_run.hip (the library's own sort and scan: bft_sort.h, bft_scan.h);
-// colour-set interning and container assembly are the kernels of bft_assemble.hip -- see DESIGN.md "Insertion".
+// colour-set interning is bft_intern.hip, container assembly bft_assemble.hip, the flat form of the big CCs bft_flat.hip -- see DESIGN.md "Insertion".
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,10 +17,14 @@
 #include <vector>
 
 #include "../../include/bft_gpu.h"
+#include "bft_assemble.h"
 #include "bft_color_plan.h"
+#include "bft_front.h"
 #include "bft_handle.h"
 #include "bft_hash.h"
 #include "bft_index.h"
+#include "bft_intern.h"
+#include "bft_merge.h"
 #include "bft_run_plan.h"
 #include "bft_sort.h"
 #include "bft_walk.h"

@@ -8,10 +8,14 @@
 #include <hip/hip_runtime.h>
 
 #include "bft_derive.h"  // bft_rederive, bft_ensure_table / bft_drop_table, the k-mer hash fill of a build (KhFill)
+#include "bft_assemble.h"  // BftDeviceIndex (bft_stored.h)
 #include "bft_dev.h"
+#include "bft_front.h"   // BftPairRun
 #include "bft_image.h"
 #include "bft_ingest.h"
+#include "bft_intern.h"  // BftInternTail
 #include "bft_kh.h"
+#include "bft_merge.h"  // BftRunOut
 
 // Scratch of ONE query family of a handle: blocks (DevBufs beside it in struct bft_gpu) that belong to the handle, not to a stream -- one stream uses
 // them at a time, they grow and never shrink.  A call takes them through a Lease (acquire(), fallible), sizes each block with grow(), and its use

@@ -16,6 +16,8 @@
 
 #include "bft_dev.h"
 #include "bft_image.h"
+#include "bft_intern.h"
+#include "bft_merge.h"
 #include "bft_scan.h"
 #include "bft_sort.h"
 #include "bft_union.h"

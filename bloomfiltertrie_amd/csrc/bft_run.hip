@@ -9,6 +9,7 @@
 
 #include <algorithm>
 
+#include "bft_front.h"
 #include "bft_handle.h"
 #include "bft_paths.h"  // BftSpHead (bft_gpu_test_scan_ex)
 #include "bft_run_plan.h"

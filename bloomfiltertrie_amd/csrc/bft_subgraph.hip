@@ -16,6 +16,7 @@
 #include "bft_dev.h"
 #include "bft_handle.h"
 #include "bft_kernels_load.h"
+#include "bft_merge.h"
 #include "bft_scan.h"
 #include "bft_subgraph.h"
 #include "bft_walk.h"

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "bft_dev.h"
+#include "bft_merge.h"  // BftRun
 
 // Keys of the merged diagonal one workgroup places (k_un_count / k_un_emit).  A tile stages at most BFT_UNION_TILE + 1 rows in LDS (the + 1: the second
 // half of a pair of equal keys that would straddle the tile's end is taken in): 32.8 KB at W = 4, so four workgroups of 256 threads per CU.

@@ -1,7 +1,7 @@
 // bft_union.hip -- merging two indexes into a new one (merging_BFT, reference include/merge.h:14; its body in src/merge.c is commented out upstream):
 // every k-mer of a and of b, genome g of b as genome id_base + g, a k-mer of both with the union of its two colour sets.
 //
-// An index is a "run" (bft_dev.h): its sorted distinct k-mers, a colour-set id per k-mer and the dictionary.  bft_merge_runs already merges two runs;
+// An index is a "run" (bft_merge.h): its sorted distinct k-mers, a colour-set id per k-mer and the dictionary.  bft_merge_runs already merges two runs;
 // its colour-set half is used as it is.  What differs from an insertion build is the placement of the k-mers.  A build's run is small beside its
 // index, so every run row searches the index.  Two indexes are of similar size: 26 dependent gathers for each of 2x10^7 rows, on a chip where a gather
 // pays per line requested.  Here both tables are streamed instead, co-ranked tile by tile:
@@ -16,6 +16,7 @@
 #include "bft_union.h"
 
 #include "bft_handle.h"
+#include "bft_merge.h"
 #include "bft_scan.h"
 #include "bft_walk.h"
 

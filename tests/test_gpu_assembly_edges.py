@@ -10,7 +10,10 @@ across them -- and, exactly:
   * query_rows answers set membership and the rank in the truth's order for every member (a sample of the big cases), the SNP neighbours of forty
     members at every position and k-mers that leave a member behind each level -- through the containers ("kmer_hash", "root_direct", "node_hash"
     0), through the containers with every CC flat, and with the options at their defaults.
+The assembly is a list of steps (Depth, step_* in csrc/bft_assemble.hip) and a build stage ends only where a step ends: the last test holds the stage
+sequence of eight cases and the bytes of every stage to a recorded table (tests/golden/assembly_stage_tables.json).
 Apart from `grid` (2048 * 256 + 300 rows: a second grid pass) and the cases whose regime is a size, a case is a few hundred to a few thousand rows."""
+import json
 import os
 import sys
 
@@ -118,3 +121,32 @@ def test_both_assignment_kernels_build_the_same_node(T):
     moved = {"path": a["path"], "uc": a["uc"] + shift, "ccs": [{**c, "pref": c["pref"] + np.array([0, 0, shift, 0])} for c in a["ccs"]]}
     assert H.node_diff(moved, b) is None, H.node_diff(moved, b)
     assert len(a["ccs"]) >= 2
+
+
+# the smallest cases that walk every branch of the depth loop: no k-mers; one depth that is also the last; two depths; a remainder behind the last
+# level; many CCs beside a small node; three, seven (two-word keys) and fourteen depths (four words)
+STAGE_CASES = ("ends_k9_n0", "root_256", "child_cc_3584", "rem26", "ncc_side", "depth_k27", "depth_k63", "depth_k126")
+STAGE_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "assembly_stage_tables.json")
+
+
+def stage_table(name):
+    """[[stage name, algorithmic bytes]] of one build of the case: every k-mer in one batch, "build_stages" on"""
+    case = H.CASES[name]
+    t = BFT(case.k)
+    t.set_option("build_stages", 1)
+    t.insert_kmers(np.ascontiguousarray(case.packed), 0)
+    t.build()
+    out = [[nm, by] for nm, _, by in t.build_stages()]
+    t.close()
+    return out
+
+
+@pytest.mark.parametrize("name", STAGE_CASES)
+def test_build_stage_table_is_the_parents(name):
+    """The build's stages, in order, with the bytes each one's formula gives, are the ones recorded before the assembly was cut into steps
+    (tests/golden/assembly_stage_tables.json): a step that crosses a stage boundary or a byte formula that drifts shows here.  The bytes are
+    doubles computed from integers: compared with ==."""
+    with open(STAGE_GOLDEN) as f:
+        want = json.load(f)[name]
+    got = stage_table(name)
+    assert len(want) > 0 and got == want, [(g, w) for g, w in zip(got, want) if g != w] or (len(got), len(want))

@@ -1,4 +1,4 @@
-"""The colour-set interning (csrc/bft_assemble.hip: bft_intern_colors_gpu, the k_cs_* kernels) at every list, wavefront and table edge.
+"""The colour-set interning (csrc/bft_intern.hip: bft_intern_colors_gpu, the k_cs_* kernels) at every list, wavefront and table edge.
 
 The cases, their truth and the proof that each reaches its regime are tests/test_intern_cases_host.py's (no GPU).  Here every case goes through
 the hook bft_gpu_test_intern in its three modes -- 0: the hash path on the caller's stream; 1: the tail deferred to a side stream, its verdict

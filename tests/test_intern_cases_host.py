@@ -1,4 +1,4 @@
-"""CPU-side tests (no GPU) of the colour-set interning (csrc/bft_assemble.hip: bft_intern_colors_gpu and its k_cs_* kernels): the cases that
+"""CPU-side tests (no GPU) of the colour-set interning (csrc/bft_intern.hip: bft_intern_colors_gpu and its k_cs_* kernels): the cases that
 tests/test_gpu_intern_edges.py runs through the hook bft_gpu_test_intern, the truth they are held to, and a proof that each case reaches the
 regime it is named for.  When a constant of the interning changes, this file fails until the cases cover every edge again.
 
@@ -37,7 +37,7 @@ MIN_SLOTS = 1 << 16  # smallest hash table; accepted while the distinct signatur
 
 
 def test_constants_are_the_sources():
-    asm = open(os.path.join(_lib.CSRC, "bft_assemble.hip")).read()
+    asm = open(os.path.join(_lib.CSRC, "bft_intern.hip")).read()
     dev = open(os.path.join(_lib.CSRC, "bft_dev.h")).read()
     assert re.search(r"^#define ABLK (\d+)$", asm, flags=re.M).group(1) == str(ABLK)
     assert re.search(r"^#define CS_CACHE (\d+)u$", asm, flags=re.M).group(1) == str(CS_CACHE)

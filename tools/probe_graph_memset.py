@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """hipMemsetAsync recorded into a HIP graph: correct on the first replay, garbage on the second (ROCm 7.0.2 on MI355X) -- why every path of the
-library that a caller may capture zeroes with a kernel of its own (bft_zero_async, csrc/bft_dev.h).  Prints the byte sums after capture and after two
+library that a caller may capture zeroes with a kernel of its own (bft_zero_async, csrc/bft_pin.hip).  Prints the byte sums after capture and after two
 replays of a graph that holds one memset of a buffer filled with ones in between."""
 import ctypes as C, torch
 hip = C.CDLL("libamdhip64.so")
