@@ -508,6 +508,75 @@ class BFT:
         _lib.check(self._lib.bft_gpu_unitig_colors_dev(self._h, C.c_void_p(d_members_ptr or 0), n_members, C.c_void_p(d_seg_off_ptr or 0), n_segments, self._setop(op),
                                                        C.c_void_p(d_rows_ptr or 0), C.c_void_p(d_counts_ptr or 0), C.c_void_p(stream or 0)))
 
+    def unitig_bubbles(self, graph, max_branch_chars=0):
+        """Simple bubbles (variants) of a compacted graph on the GPU (bft_gpu_unitig_bubbles defines them): graph is the tuple unitig_graph returned.
+        Returns (bubbles: uint32 [n, 6], rows {source A, sink Z, B_1 .. B_4} of oriented segments in ascending A, unused branches 0xFFFFFFFF;
+        counts: uint64 [4] = {bubbles, branches, bubbles whose branches all have 2k - 1 characters, the longest branch in characters})."""
+        seg_off, seqs, link_off, links = (np.ascontiguousarray(a, dtype=d) for a, d in zip(graph[:4], (np.uint64, np.uint8, np.uint64, np.uint32)))
+        ns = max(0, len(seg_off) - 1)
+        ptr = lambda a: a.ctypes.data if len(a) else None  # noqa: E731
+        args = (ptr(seg_off), ptr(seqs), ptr(link_off), ptr(links), ns, len(links), int(max_branch_chars))
+        counts = np.zeros(4, dtype=np.uint64)
+        cnt = counts.ctypes.data_as(C.POINTER(C.c_uint64))
+        _lib.check(self._lib.bft_gpu_unitig_bubbles(self._h, *args, None, 0, cnt))
+        out = np.zeros((int(counts[0]), 6), dtype=np.uint32)
+        if len(out):
+            _lib.check(self._lib.bft_gpu_unitig_bubbles(self._h, *args, out.ctypes.data, len(out), cnt))
+        return out, counts
+
+    def unitig_bubbles_dev(self, d_seg_off_ptr, d_seqs_ptr, d_link_off_ptr, d_links_ptr, n_segments, n_links, d_bubbles_ptr, cap, d_counts_ptr,
+                           max_branch_chars=0, stream=None):
+        """Device-resident bubbles (bft_gpu_unitig_bubbles_dev) over device copies of unitig_graph's arrays: {bubbles, branches, substitution
+        shapes, longest branch} (4 uint64) at d_counts_ptr always, the records below cap at d_bubbles_ptr when it is not 0; no synchronisation."""
+        _lib.check(self._lib.bft_gpu_unitig_bubbles_dev(self._h, C.c_void_p(d_seg_off_ptr or 0), C.c_void_p(d_seqs_ptr or 0), C.c_void_p(d_link_off_ptr or 0),
+                                                        C.c_void_p(d_links_ptr or 0), n_segments, n_links, int(max_branch_chars), C.c_void_p(d_bubbles_ptr or 0),
+                                                        cap, C.c_void_p(d_counts_ptr), C.c_void_p(stream or 0)))
+
+    def unitig_segment_of(self, graph):
+        """The k-mer -> segment table of a compacted graph (bft_gpu_unitig_segment_of): graph is the tuple unitig_graph returned.  Returns (seg_of:
+        uint32 per row in the extract order, 2 * segment + orientation of the stored strand; pos: uint32, the row's index inside its segment), both
+        0xFFFFFFFF for a row in no segment."""
+        seg_off = np.ascontiguousarray(graph[0], dtype=np.uint64)
+        members = np.ascontiguousarray(graph[4], dtype=np.uint32)
+        ns = max(0, len(seg_off) - 1)
+        self.build()  # (the row count is final)
+        n = int(self.info()["kmers"])
+        seg_of, pos = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+        _lib.check(self._lib.bft_gpu_unitig_segment_of(self._h, members.ctypes.data if len(members) else None, len(members), seg_off.ctypes.data if len(seg_off) else None,
+                                                       ns, seg_of.ctypes.data if n else None, pos.ctypes.data if n else None, n))
+        return seg_of, pos
+
+    def unitig_segment_of_dev(self, d_members_ptr, n_members, d_seg_off_ptr, n_segments, d_seg_of_ptr, d_pos_ptr, cap, stream=None):
+        """Device-resident k-mer -> segment table (bft_gpu_unitig_segment_of_dev): the entries of the rows below cap into the buffers that are not 0;
+        no synchronisation."""
+        _lib.check(self._lib.bft_gpu_unitig_segment_of_dev(self._h, C.c_void_p(d_members_ptr or 0), n_members, C.c_void_p(d_seg_off_ptr or 0), n_segments,
+                                                           C.c_void_p(d_seg_of_ptr or 0), C.c_void_p(d_pos_ptr or 0), cap, C.c_void_p(stream or 0)))
+
+    def bubbles(self, min_shared=0, max_branch_chars=0, colors=False):
+        """The variants of a canonical index in one call: unitig_graph(min_shared) -> unitig_bubbles, and with colors unitig_colors("and").  Returns one
+        dict per bubble, in the order of unitig_bubbles: "source", "sink" and "branches" (oriented segments 2 * i + o of the graph at min_shared),
+        "alleles" (the string of every branch as the bubble reads it: reverse-complemented for o = 1) and, with colors, "genomes": per branch the sorted
+        ids of the genomes that hold every k-mer of the allele."""
+        graph = self.unitig_graph(min_shared)
+        seg_off, seqs = graph[0], graph[1]
+        recs, _ = self.unitig_bubbles(graph, max_branch_chars)
+        rows = self.unitig_colors(graph[4], seg_off, "and")[0] if colors and len(recs) else None
+        text = seqs.tobytes().decode()
+        comp = str.maketrans("ACGT", "TGCA")
+
+        def spelled(b):
+            s = text[int(seg_off[b >> 1]):int(seg_off[(b >> 1) + 1])]
+            return s if b & 1 == 0 else s.translate(comp)[::-1]
+
+        out = []
+        for rec in recs.tolist():
+            branches = [b for b in rec[2:] if b != 0xFFFFFFFF]
+            item = {"source": rec[0], "sink": rec[1], "branches": branches, "alleles": [spelled(b) for b in branches]}
+            if colors:
+                item["genomes"] = [np.flatnonzero(np.unpackbits(rows[b >> 1], bitorder="little")).tolist() for b in branches]
+            out.append(item)
+        return out
+
     def components(self, genome_ids=()):
         """get_nb_connected_component (reference snippets.h, src/snippets.c:605-960) on the GPU: the connected components of the index, or of the
         sub-graph of k-mers that carry every genome id of genome_ids (strictly increasing; bft_gpu_components defines them).  Returns

@@ -16,6 +16,7 @@
 #include "../../include/bft/merge.h"
 #include "../../include/bft/snippets.h"
 #include "../../include/bft/unitigs.h"
+#include "bft_bubbles_io.h"
 #include "bft_gfa.h"
 
 #define DIE(...) do { fprintf(stderr, __VA_ARGS__); exit(EXIT_FAILURE); } while (0)
@@ -877,6 +878,18 @@ void extract_unitig_graph_to_disk(BFT* graph, int min_shared, bool colors, char*
     if (rc < 0) ck(rc, "extract_unitig_graph_to_disk()");
     if (rc == 1) DIE("extract_unitig_graph_to_disk(): out of memory\n");
     if (fclose(file) != 0 || rc) DIE("extract_unitig_graph_to_disk(): failed to write the output file.\n");
+}
+
+/* <bft/unitigs.h>: the simple bubbles (variants) of that graph as text (bft_bubbles_io.h), from bft_gpu_unitig_bubbles and bft_gpu_unitig_colors */
+void extract_bubbles_to_disk(BFT* graph, int min_shared, int max_branch_length, char* filename_output) {
+    NOT_NULL(graph, "extract_bubbles_to_disk()");
+    NOT_NULL(filename_output, "extract_bubbles_to_disk()");
+    FILE* file = fopen(filename_output, "w");
+    if (file == NULL) DIE("extract_bubbles_to_disk(): failed to create output file.\n");
+    const int rc = bft_bubbles_write(graph->gpu, graph->k, min_shared > 0 ? (uint32_t)min_shared : 0u, max_branch_length > 0 ? (uint64_t)max_branch_length : 0u, file);
+    if (rc < 0) ck(rc, "extract_bubbles_to_disk()");
+    if (rc == 1) DIE("extract_bubbles_to_disk(): out of memory\n");
+    if (fclose(file) != 0 || rc) DIE("extract_bubbles_to_disk(): failed to write the output file.\n");
 }
 
 /* ---------------------------------------------------------------- marking (include/bft.h:143-146, src/bft.c:686-765) */

@@ -11,6 +11,7 @@
  *                         [-genome_matrix {shared|jaccard|mash} output_file]
  *                         [-unitigs min_shared output_file]
  *                         [-gfa min_shared colors output_file]
+ *                         [-bubbles min_shared max_branch_chars output_file]
  *
  * It is the per-k-mer loops of src/file_io.c:89-213 (build), :651-895 (presence CSV) and :897-1020 (branching)
  * rewired to one batched GPU call per file; file reading, ASCII parsing (parseKmerCount, src/fasta.c:3-53) and CSV
@@ -25,6 +26,8 @@
  * `>unitig_<i> length=<L>`, in the call's order.
  * Another: -gfa writes the compacted coloured graph of a canonical index (bft_gpu_unitig_graph: the unitigs, the branching k-mers as segments of their
  * own, the links between them) as GFA 1 (bft_gfa.h); colors 1 adds the union row, the intersection row and the number of genomes of every segment.
+ * Another: -bubbles writes the simple bubbles (variants) of that graph (bft_gpu_unitig_bubbles; max_branch_chars 0: no limit) as text, one block per
+ * bubble with the genomes of every allele (bft_bubbles_io.h); the segment ids are those of -gfa at the same min_shared.
  * Another: -genome_matrix writes the genome-by-genome shared k-mer matrix (bft_gpu_genome_matrix) as tab-separated text: a header line of the genome
  * names behind an empty first cell, then one line per genome, its name and its row -- the counts (shared, %llu) or the distances computed from
  * them (jaccard, mash: %.6f).
@@ -38,6 +41,7 @@
 #include <string.h>
 
 #include "../../include/bft_gpu.h"
+#include "bft_bubbles_io.h"
 #include "bft_gfa.h"
 
 #define DIE(...) do { fprintf(stderr, __VA_ARGS__); exit(EXIT_FAILURE); } while (0) /* ERROR(), include/useful_macros.h:33-43 */
@@ -395,6 +399,25 @@ static void gfa(bft_gpu* h, const char* min_shared, const char* colors, const ch
     if (fclose(f) != 0 || rc) DIE("Cannot write %s\n", path);
 }
 
+/* -bubbles: the variants of the compacted graph as text (bft_bubbles_io.h) */
+static void bubbles(bft_gpu* h, const char* min_shared, const char* max_chars, const char* path, int k) {
+    char* end = NULL;
+    const long t = strtol(min_shared, &end, 10);
+    if (end == min_shared || *end || t < 0) DIE("Could not parse min_shared for command -bubbles.\n");
+    const long long mc = strtoll(max_chars, &end, 10);
+    if (end == max_chars || *end || mc < 0) DIE("Could not parse max_branch_chars for command -bubbles.\n");
+    FILE* f = fopen(path, "w");
+    if (!f) DIE("Cannot create %s\n", path);
+    const int rc = bft_bubbles_write(h, k, (uint32_t)t, (uint64_t)mc, f);
+    if (rc < 0 || rc == 1) { /* (nothing was written: no empty file stays behind) */
+        fclose(f);
+        remove(path);
+    }
+    if (rc < 0) ck(rc);
+    if (rc == 1) DIE("-bubbles: out of memory\n");
+    if (fclose(f) != 0 || rc) DIE("Cannot write %s\n", path);
+}
+
 int main(int argc, char** argv) {
     if (argc >= 2 && (strcmp(argv[1], "--version") == 0 || strcmp(argv[1], "-v") == 0)) { /* src/main.c:51-55 */
         fprintf(stderr, "0.8 (%s)\n", bft_gpu_version());
@@ -410,7 +433,8 @@ int main(int argc, char** argv) {
             "[-extract_kmers {kmers|kmers_comp} output_file]\n"
             "[-genome_matrix {shared|jaccard|mash} output_file]\n"
             "[-unitigs min_shared output_file]\n"
-            "[-gfa min_shared colors output_file]\n\n");
+            "[-gfa min_shared colors output_file]\n"
+            "[-bubbles min_shared max_branch_chars output_file]\n\n");
     bft_gpu* h = NULL;
     int k = 0, i = 0;
     char buffer[2048];
@@ -475,6 +499,12 @@ int main(int argc, char** argv) {
         if (strcmp(argv[i], "-gfa") == 0) { /* four arguments */
             if (i + 3 >= argc) DIE("-gfa min_shared colors output_file\n");
             gfa(h, argv[i + 1], argv[i + 2], argv[i + 3], k);
+            i++;
+            continue;
+        }
+        if (strcmp(argv[i], "-bubbles") == 0) { /* four arguments */
+            if (i + 3 >= argc) DIE("-bubbles min_shared max_branch_chars output_file\n");
+            bubbles(h, argv[i + 1], argv[i + 2], argv[i + 3], k);
             i++;
             continue;
         }

@@ -31,6 +31,16 @@ void extract_unitigs_to_disk(BFT* graph, int min_shared, char* filename_output);
  * (fields separated by tabs).  min_shared as for extract_unitigs_to_disk.  Errors print a message on stderr and exit(EXIT_FAILURE). */
 void extract_unitig_graph_to_disk(BFT* graph, int min_shared, bool colors, char* filename_output);
 
+/* The simple bubbles (variants) of that graph (bft_gpu_unitig_bubbles defines them: two to four parallel segments between the same two flanks, each
+ * reported once) written to filename_output as text, one block per bubble in the call's order, fields separated by tabs:
+ *   B  <index>  <source id><+|->  <sink id><+|->  <m>                                        the bubble: its number, source, sink, branches
+ *   A  <segment id><+|->  <sequence in that orientation>  <number of genomes>  <genome ids>  one per branch, in the source's link order
+ * The genomes of a branch are the intersection row of its segment: the genomes that hold every k-mer of the allele, ascending, separated by commas.
+ * Segment ids are those of extract_unitig_graph_to_disk at the same min_shared (- is the reverse complement of the S line), so the file joins to the
+ * GFA.  max_branch_length > 0: only bubbles whose branches all have at most that many nucleotides (0 or less: no limit).  min_shared and errors as
+ * above. */
+void extract_bubbles_to_disk(BFT* graph, int min_shared, int max_branch_length, char* filename_output);
+
 #ifdef __cplusplus
 }
 #endif

@@ -506,6 +506,50 @@ int bft_gpu_unitig_colors(bft_gpu* h, const uint32_t* members, uint64_t n_member
 int bft_gpu_unitig_colors_dev(bft_gpu* h, const void* d_members, uint64_t n_members, const void* d_seg_off, uint64_t n_segments, int op, void* d_rows,
                               void* d_counts, void* hip_stream);
 
+/* Simple bubbles (variants) on the compacted coloured graph: two to four parallel segments between the same two flanks.  The call reads the arrays
+ * bft_gpu_unitig_graph returned -- seg_off (n_segments + 1), seqs (seg_off[n_segments] characters), link_off (2 * n_segments + 1), links (n_links) --
+ * not an index; the handle supplies k, the stream and the scratch.  An extension: the reference has no counterpart.
+ *   S = n_segments; the oriented segments are 0 .. 2S - 1; seg(X) = X >> 1; out(X) is the list links[link_off[X] .. link_off[X + 1]).
+ *   palindromic segment   a segment of exactly k characters whose string equals its own reverse complement (even k only; read from seqs).
+ *   bubble with source A  the oriented segment A is the source of a bubble with sink Z and branches B_1 .. B_m when ALL of these hold:
+ *                         - out(A) = [B_1 .. B_m] with 2 <= m <= 4: ALL of A's links, in their stored (ascending) order;
+ *                         - for every j: out(B_j) = [Z], the same Z for all j, and out(B_j ^ 1) = [A ^ 1] (one way in, one way out);
+ *                         - out(Z ^ 1) has exactly m entries and every entry t has t ^ 1 in {B_j} (the sink has no other way in; evaluated
+ *                           literally, not through the mirror symmetry of the table);
+ *                         - seg(A), seg(Z), seg(B_1) .. seg(B_m) are pairwise different (no self loop, no cycle through the source, not both
+ *                           orientations of one segment as two branches);
+ *                         - neither seg(A) nor seg(Z) is palindromic.  (A palindromic branch can never pass the rules above on the links of
+ *                           bft_gpu_unitig_graph: links INTO a palindrome always name its + orientation P, so out(A) holds P and out(Z ^ 1) holds P
+ *                           too, whose flip P ^ 1 is no branch);
+ *                         - max_branch_chars > 0: every branch has at most that many characters (0: no limit).
+ *   reported              every bubble exists twice, as A -> B_j -> Z and as its mirror Z ^ 1 -> B_j ^ 1 -> A ^ 1: the one with A < (Z ^ 1) is
+ *                         reported.  Bubbles come in ascending A; an oriented segment is the source of at most one bubble.
+ * Outputs: bubbles (may be NULL: the call only counts), records of 6 x uint32 {A, Z, B_1, B_2, B_3, B_4}, the branches in A's link order, unused slots
+ * 0xFFFFFFFF; it holds cap records.  counts (4 x uint64) = {n_bubbles, branches of all bubbles, bubbles whose branches ALL have exactly 2k - 1
+ * characters (k k-mers: the shape of an isolated substitution), the longest branch of a reported bubble in characters}.  cap < n_bubbles:
+ * BFT_GPU_E_NOSPACE, counts filled, nothing else written.  The host form validates: link_off that decreases, link_off[2S] != n_links, a target >= 2S
+ * and a seg_off step below k are BFT_GPU_E_ARG, with nothing written.  At most 2^31 - 1 segments (BFT_GPU_E_LIMIT).  Kernel time and "build_stages"
+ * (stage names start "bubbles:") as everywhere.  The scratch (5 bytes per oriented segment) is the call's own: it interleaves freely with
+ * bft_gpu_unitig_graph, the queries and the other families on one handle. */
+int bft_gpu_unitig_bubbles(bft_gpu* h, const uint64_t* seg_off, const char* seqs, const uint64_t* link_off, const uint32_t* links, uint64_t n_segments,
+                           uint64_t n_links, uint64_t max_branch_chars, uint32_t* bubbles, uint64_t cap, uint64_t counts[4]);
+/* The same on device buffers on hip_stream (NULL = the handle's stream), without host synchronisation and without a count read back: d_counts
+ * (4 x uint64) is always written, d_bubbles (may be NULL) receives the records below cap.  Nothing is validated up front, but no lane reads outside the
+ * given arrays: a list of more than 4 entries, an offset past n_links, a target >= 2S or segment offsets outside seqs make "no bubble" for that lane.
+ * Not inside a graph capture (BFT_GPU_E_ARG). */
+int bft_gpu_unitig_bubbles_dev(bft_gpu* h, const void* d_seg_off, const void* d_seqs, const void* d_link_off, const void* d_links, uint64_t n_segments,
+                               uint64_t n_links, uint64_t max_branch_chars, void* d_bubbles, uint64_t cap, void* d_counts, void* hip_stream);
+/* The k-mer -> segment table of a compacted graph, from its members and seg_off: seg_of[row] = 2 * i + o when vertex 2 * row + o is a member of
+ * segment i (the stored strand of the row reads along oriented segment (i, o)), pos[row] = its index inside segment i in path order; both
+ * 0xFFFFFFFF for a row in no segment (not eligible at the graph's min_shared).  Rows are those of bft_gpu_extract.  Either output may be NULL; both
+ * hold cap entries, n_kmers are needed (BFT_GPU_E_NOSPACE, nothing written).  Host form: bad members and offsets are BFT_GPU_E_ARG as for
+ * bft_gpu_unitig_colors.  Device form: a member that is no vertex, or whose segment the offsets do not give, is skipped; rows below cap only.  Pending
+ * insertions are built first.  Not inside a graph capture (BFT_GPU_E_ARG). */
+int bft_gpu_unitig_segment_of(bft_gpu* h, const uint32_t* members, uint64_t n_members, const uint64_t* seg_off, uint64_t n_segments, uint32_t* seg_of,
+                              uint32_t* pos, uint64_t cap);
+int bft_gpu_unitig_segment_of_dev(bft_gpu* h, const void* d_members, uint64_t n_members, const void* d_seg_off, uint64_t n_segments, void* d_seg_of, void* d_pos,
+                                  uint64_t cap, void* hip_stream);
+
 /* Connected components:get_nb_connected_component(bft, &nb, BFS | DFS) and (..., BFS_subgraph | DFS_subgraph, nb_id_genomes, ids...) (reference
  * snippets.h, src/snippets.c:605-960) without the walk, over the whole graph (nb_ids = 0) or the sub-graph of genome_ids.
  *   vertices  the stored k-mers; in a sub-graph, only the members: k-mers whose colour set holds EVERY id of genome_ids;
