@@ -82,6 +82,10 @@ SIGNATURES = {
     "bft_gpu_unitig_bubbles_dev": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, C.c_uint64, _P, C.c_uint64, _P, _P]),
     "bft_gpu_unitig_segment_of": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, _P, _P, C.c_uint64]),
     "bft_gpu_unitig_segment_of_dev": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, _P, _P, C.c_uint64, _P]),
+    "bft_gpu_thread_sequences": (C.c_int, [_P, C.c_char_p, _P, C.c_uint64, _P, _P, C.c_uint64, _P, C.c_uint64, _P, _P, C.c_uint64, _P, _P, C.c_uint64, _P, C.c_uint64,
+                                           C.POINTER(C.c_uint64)]),
+    "bft_gpu_thread_sequences_dev": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint64, _P, _P, C.c_uint64, _P, C.c_uint64, _P, _P, C.c_uint64, _P, _P, C.c_uint64, _P,
+                                               C.c_uint64, _P, _P]),
     "bft_gpu_components": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64, _P, C.c_uint64, _P]),
     "bft_gpu_components_dev": (C.c_int, [_P, _P, C.c_uint32, _P, _P, C.c_uint64, _P, _P]),
     "bft_gpu_kmers_by_count": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),

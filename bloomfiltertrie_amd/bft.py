@@ -577,6 +577,57 @@ class BFT:
             out.append(item)
         return out
 
+    def thread_sequences(self, sequences, graph, seg_of=None):
+        """Where a list of ASCII sequences runs in a compacted graph (bft_gpu_thread_sequences defines the walks): graph is the tuple unitig_graph
+        returned, seg_of the pair unitig_segment_of(graph) returned (computed here when None).  Returns (walks: uint64 [n, 4], rows {sequence, first
+        position p0, positions n_w, index q0 of the first position in the first step}; walk_off: uint64 [n + 1] offsets into steps; steps: uint32
+        oriented segments 2 * i + o; counts: uint64 [8] = {walks, steps, positions, invalid, absent from the index, in no segment, breaks between
+        located neighbours, non-canonical rows}).  An index that is not canonical raises (BFT_GPU_E_STATE)."""
+        enc = [x.encode() if isinstance(x, str) else bytes(x) for x in sequences]
+        off = np.zeros(len(enc) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(e) for e in enc])
+        blob = b"".join(enc) + b"\0"
+        if seg_of is None:
+            seg_of = self.unitig_segment_of(graph)
+        sg, ps = (np.ascontiguousarray(a, dtype=np.uint32) for a in seg_of)
+        seg_off, link_off, links = (np.ascontiguousarray(graph[i], dtype=d) for i, d in ((0, np.uint64), (2, np.uint64), (3, np.uint32)))
+        ns = max(0, len(seg_off) - 1)
+        ptr = lambda a: a.ctypes.data if len(a) else None  # noqa: E731
+        args = (blob, off.ctypes.data, len(enc), ptr(sg), ptr(ps), len(sg), ptr(seg_off), ns, ptr(link_off), ptr(links), len(links))
+        counts = np.zeros(8, dtype=np.uint64)
+        cnt = counts.ctypes.data_as(C.POINTER(C.c_uint64))
+        _lib.check(self._lib.bft_gpu_thread_sequences(self._h, *args, None, None, 0, None, 0, cnt))
+        nw, nst = int(counts[0]), int(counts[1])
+        walks = np.zeros((nw, 4), dtype=np.uint64)
+        walk_off = np.zeros(nw + 1, dtype=np.uint64)
+        steps = np.zeros(nst, dtype=np.uint32)
+        if nw:
+            _lib.check(self._lib.bft_gpu_thread_sequences(self._h, *args, walks.ctypes.data, walk_off.ctypes.data, nw, steps.ctypes.data, nst, cnt))
+        return walks, walk_off, steps, counts
+
+    def thread_sequences_dev(self, d_seqs_ptr, d_seq_off_ptr, n_seqs, total_chars, d_seg_of_ptr, d_pos_ptr, n_rows, d_seg_off_ptr, n_segments, d_link_off_ptr,
+                             d_links_ptr, n_links, d_walks_ptr, d_walk_off_ptr, walks_cap, d_steps_ptr, steps_cap, d_counts_ptr, stream=None):
+        """Device-resident threading (bft_gpu_thread_sequences_dev) over device copies of the sequences, unitig_graph's arrays and unitig_segment_of's
+        table: the 8 uint64 counts at d_counts_ptr always, walks (4 uint64 each) and walk_off entries (walks_cap + 1 at the most) below walks_cap, steps
+        below steps_cap, each into the buffer that is not 0; no synchronisation."""
+        v = lambda x: C.c_void_p(x or 0)  # noqa: E731
+        _lib.check(self._lib.bft_gpu_thread_sequences_dev(self._h, v(d_seqs_ptr), v(d_seq_off_ptr), n_seqs, total_chars, v(d_seg_of_ptr), v(d_pos_ptr), n_rows,
+                                                          v(d_seg_off_ptr), n_segments, v(d_link_off_ptr), v(d_links_ptr), n_links, v(d_walks_ptr), v(d_walk_off_ptr),
+                                                          walks_cap, v(d_steps_ptr), steps_cap, v(d_counts_ptr), v(stream)))
+
+    def thread(self, sequences, min_shared=0):
+        """The walks of a list of sequences over the compacted graph of a canonical index in one call: unitig_graph(min_shared) -> unitig_segment_of ->
+        thread_sequences.  Returns one dict per walk, in the call's order: "sequence" (its index in the list), "start" and "end" (the characters
+        [start, end) of the sequence the walk covers), "path" (oriented segments 2 * i + o of the graph at min_shared), "path_start" and "path_end"
+        (the same characters on the path: its segments spelled with k - 1 overlap)."""
+        graph = self.unitig_graph(min_shared)
+        walks, walk_off, steps, _ = self.thread_sequences(sequences, graph)
+        out = []
+        for (s, p0, nw, q0), a, b in zip(walks.tolist(), walk_off[:-1].tolist(), walk_off[1:].tolist()):
+            span = nw + self.k - 1
+            out.append({"sequence": s, "start": p0, "end": p0 + span, "path": steps[a:b].tolist(), "path_start": q0, "path_end": q0 + span})
+        return out
+
     def components(self, genome_ids=()):
         """get_nb_connected_component (reference snippets.h, src/snippets.c:605-960) on the GPU: the connected components of the index, or of the
         sub-graph of k-mers that carry every genome id of genome_ids (strictly increasing; bft_gpu_components defines them).  Returns

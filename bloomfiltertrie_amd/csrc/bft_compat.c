@@ -17,6 +17,7 @@
 #include "../../include/bft/snippets.h"
 #include "../../include/bft/unitigs.h"
 #include "bft_bubbles_io.h"
+#include "bft_gaf.h"
 #include "bft_gfa.h"
 
 #define DIE(...) do { fprintf(stderr, __VA_ARGS__); exit(EXIT_FAILURE); } while (0)
@@ -890,6 +891,25 @@ void extract_bubbles_to_disk(BFT* graph, int min_shared, int max_branch_length, 
     if (rc < 0) ck(rc, "extract_bubbles_to_disk()");
     if (rc == 1) DIE("extract_bubbles_to_disk(): out of memory\n");
     if (fclose(file) != 0 || rc) DIE("extract_bubbles_to_disk(): failed to write the output file.\n");
+}
+
+/* <bft/unitigs.h>: the sequences of a FASTA / FASTQ file threaded through that graph, one GAF line per walk (bft_gaf.h), from bft_gpu_thread_sequences */
+void thread_sequences_to_disk(BFT* graph, int min_shared, char* filename_sequences, char* filename_output) {
+    NOT_NULL(graph, "thread_sequences_to_disk()");
+    NOT_NULL(filename_sequences, "thread_sequences_to_disk()");
+    NOT_NULL(filename_output, "thread_sequences_to_disk()");
+    FILE* file = fopen(filename_output, "w");
+    if (file == NULL) DIE("thread_sequences_to_disk(): failed to create output file.\n");
+    const int rc = bft_gaf_write(graph->gpu, graph->k, min_shared > 0 ? (uint32_t)min_shared : 0u, filename_sequences, file);
+    if (rc < 0 || rc >= 3) { /* (nothing was written: no empty file stays behind) */
+        fclose(file);
+        remove(filename_output);
+    }
+    if (rc < 0) ck(rc, "thread_sequences_to_disk()");
+    if (rc == 1) DIE("thread_sequences_to_disk(): out of memory\n");
+    if (rc == 3) DIE("thread_sequences_to_disk(): failed to read the sequence file.\n");
+    if (rc == 4) DIE("thread_sequences_to_disk(): the sequence file is neither FASTA nor FASTQ.\n");
+    if (fclose(file) != 0 || rc) DIE("thread_sequences_to_disk(): failed to write the output file.\n");
 }
 
 /* ---------------------------------------------------------------- marking (include/bft.h:143-146, src/bft.c:686-765) */

@@ -12,6 +12,7 @@
  *                         [-unitigs min_shared output_file]
  *                         [-gfa min_shared colors output_file]
  *                         [-bubbles min_shared max_branch_chars output_file]
+ *                         [-thread min_shared sequence_file output_file]
  *
  * It is the per-k-mer loops of src/file_io.c:89-213 (build), :651-895 (presence CSV) and :897-1020 (branching)
  * rewired to one batched GPU call per file; file reading, ASCII parsing (parseKmerCount, src/fasta.c:3-53) and CSV
@@ -28,6 +29,8 @@
  * own, the links between them) as GFA 1 (bft_gfa.h); colors 1 adds the union row, the intersection row and the number of genomes of every segment.
  * Another: -bubbles writes the simple bubbles (variants) of that graph (bft_gpu_unitig_bubbles; max_branch_chars 0: no limit) as text, one block per
  * bubble with the genomes of every allele (bft_bubbles_io.h); the segment ids are those of -gfa at the same min_shared.
+ * Another: -thread lays the sequences of one FASTA / FASTQ file onto that graph (bft_gpu_thread_sequences: the maximal walks the sequences spell exactly)
+ * and writes one GAF line per walk (bft_gaf.h); the segment ids are those of -gfa at the same min_shared.
  * Another: -genome_matrix writes the genome-by-genome shared k-mer matrix (bft_gpu_genome_matrix) as tab-separated text: a header line of the genome
  * names behind an empty first cell, then one line per genome, its name and its row -- the counts (shared, %llu) or the distances computed from
  * them (jaccard, mash: %.6f).
@@ -42,6 +45,7 @@
 
 #include "../../include/bft_gpu.h"
 #include "bft_bubbles_io.h"
+#include "bft_gaf.h"
 #include "bft_gfa.h"
 
 #define DIE(...) do { fprintf(stderr, __VA_ARGS__); exit(EXIT_FAILURE); } while (0) /* ERROR(), include/useful_macros.h:33-43 */
@@ -418,6 +422,25 @@ static void bubbles(bft_gpu* h, const char* min_shared, const char* max_chars, c
     if (fclose(f) != 0 || rc) DIE("Cannot write %s\n", path);
 }
 
+/* -thread: the walks of a file's sequences over the compacted graph as GAF (bft_gaf.h) */
+static void thread_sequences(bft_gpu* h, const char* min_shared, const char* seq_path, const char* path, int k) {
+    char* end = NULL;
+    const long t = strtol(min_shared, &end, 10);
+    if (end == min_shared || *end || t < 0) DIE("Could not parse min_shared for command -thread.\n");
+    FILE* f = fopen(path, "w");
+    if (!f) DIE("Cannot create %s\n", path);
+    const int rc = bft_gaf_write(h, k, (uint32_t)t, seq_path, f);
+    if (rc < 0 || rc == 1 || rc >= 3) { /* (nothing was written: no empty file stays behind) */
+        fclose(f);
+        remove(path);
+    }
+    if (rc < 0) ck(rc);
+    if (rc == 1) DIE("-thread: out of memory\n");
+    if (rc == 3) DIE("-thread: cannot read %s\n", seq_path);
+    if (rc == 4) DIE("-thread: %s is neither FASTA nor FASTQ\n", seq_path);
+    if (fclose(f) != 0 || rc) DIE("Cannot write %s\n", path);
+}
+
 int main(int argc, char** argv) {
     if (argc >= 2 && (strcmp(argv[1], "--version") == 0 || strcmp(argv[1], "-v") == 0)) { /* src/main.c:51-55 */
         fprintf(stderr, "0.8 (%s)\n", bft_gpu_version());
@@ -434,7 +457,8 @@ int main(int argc, char** argv) {
             "[-genome_matrix {shared|jaccard|mash} output_file]\n"
             "[-unitigs min_shared output_file]\n"
             "[-gfa min_shared colors output_file]\n"
-            "[-bubbles min_shared max_branch_chars output_file]\n\n");
+            "[-bubbles min_shared max_branch_chars output_file]\n"
+            "[-thread min_shared sequence_file output_file]\n\n");
     bft_gpu* h = NULL;
     int k = 0, i = 0;
     char buffer[2048];
@@ -505,6 +529,12 @@ int main(int argc, char** argv) {
         if (strcmp(argv[i], "-bubbles") == 0) { /* four arguments */
             if (i + 3 >= argc) DIE("-bubbles min_shared max_branch_chars output_file\n");
             bubbles(h, argv[i + 1], argv[i + 2], argv[i + 3], k);
+            i++;
+            continue;
+        }
+        if (strcmp(argv[i], "-thread") == 0) { /* four arguments */
+            if (i + 3 >= argc) DIE("-thread min_shared sequence_file output_file\n");
+            thread_sequences(h, argv[i + 1], argv[i + 2], argv[i + 3], k);
             i++;
             continue;
         }

@@ -3,7 +3,7 @@
 // in: .bft files, the blob, the read-outs, the width of the dictionary's ids; over the tables of bft_stored.h), bft_derive.hip (what the
 // handle derives from a committed image, bft_derive.h: root tables, k-mer hash, node prefix hash, launch shape, compact table), bft_query.hip (the k-mer and
 // sequence queries, their tuner, the claim slots), bft_run.hip (the build's run stage, the sort and scan test hooks) and the analysis families
-// bft_prefix.hip, bft_paths.hip (the path engine and the simple paths), bft_unitigs.hip (its mirrored family), bft_cgraph.hip (the compacted graph over it), bft_bubbles.hip (bubbles and the k-mer -> segment table over its arrays), bft_components.hip, bft_pangenome.hip, bft_genome_matrix.hip, bft_subgraph.hip, bft_marking.hip, bft_setops.hip, bft_union.hip, bft_ingest.hip.
+// bft_prefix.hip, bft_paths.hip (the path engine and the simple paths), bft_unitigs.hip (its mirrored family), bft_cgraph.hip (the compacted graph over it), bft_bubbles.hip (bubbles and the k-mer -> segment table over its arrays), bft_thread.hip (sequences threaded through it), bft_components.hip, bft_pangenome.hip, bft_genome_matrix.hip, bft_subgraph.hip, bft_marking.hip, bft_setops.hip, bft_union.hip, bft_ingest.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -274,6 +274,8 @@ struct bft_gpu {
     DevBuf so_buf;                   // set operations over groups (BftSoScratch, bft_setops.h): colour set per k-mer, presence bits, accumulators, split list
     HandleScratch bb{"bubbles"};
     DevBuf bb_buf, bb_tmp;           // bubbles on the compacted graph (BftBbScratch, bft_bubbles.h): flag and slot per oriented segment; the scan's temporary
+    HandleScratch th{"sequence threading"};
+    DevBuf th_buf, th_tmp;           // sequence threading over the compacted graph (BftThScratch, bft_thread.h): codes, plan, bucket starts, per-position arrays; the scans' temporary
     HandleScratch ig{"sequence ingest"};
     DevBuf ig_seq, ig_soff;          // insertion from sequences (bft_ingest.hip): the host form's chunk of the blob and its offsets
     DevBuf ig_codes, ig_bad, ig_npos, ig_poff, ig_seqtile, ig_tmp;  // codes, plan and the scans' temporary (as sq_*)

@@ -62,3 +62,32 @@ __device__ __forceinline__ bool seq_window(const uint64_t* __restrict__ codes, c
     return ok;
 }
 
+// seq_window's sibling for callers that need to know which strand the canonical word is: x = the smaller of the window w and rc(w), *strand = 0 when
+// that is w itself -- a palindromic w included, where seq_window reports "use the reverse complement" --, 1 when it is rc(w).
+template <int W>
+__device__ __forceinline__ bool seq_window_strand(const uint64_t* __restrict__ codes, const uint32_t* __restrict__ bad, uint64_t c0, int k, uint64_t* x, uint32_t* strand) {
+    uint64_t xf[W], xr[W], rv[W + 1];
+    const bool ok = seq_window<W>(codes, bad, c0, k, 0, xf);
+#pragma unroll
+    for (int q = 0; q < W; q++) rv[q] = rev2_64(~xf[W - 1 - q]);
+    rv[W] = 0;
+    const uint32_t dn = (uint32_t)(64 * W - 2 * k);  // < 64
+    const int top = 2 * k - 64 * (W - 1);
+#pragma unroll
+    for (int q = 0; q < W; q++) xr[q] = dn ? (rv[q] >> dn) | (rv[q + 1] << (64u - dn)) : rv[q];
+    if (top < 64) xr[W - 1] &= (1ull << top) - 1ull;
+    bool use_rc = false;
+#pragma unroll
+    for (int q = W - 1; q >= 0; q--) {  // the lowest differing field decides: word 0 last
+        const uint64_t df = xf[q] ^ xr[q];
+        if (df) {
+            const int fs = __builtin_ctzll(df) & ~1;
+            use_rc = ((xf[q] >> fs) & 3ull) > ((xr[q] >> fs) & 3ull);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < W; q++) x[q] = use_rc ? xr[q] : xf[q];
+    *strand = use_rc ? 1u : 0u;
+    return ok;
+}
+

@@ -28,11 +28,20 @@ int read_all(const char* path, std::string& out) {
 }
 }  // namespace
 
-extern "C" int bft_seqfile_read(const char* path, char** blob, uint64_t** offsets, uint64_t* nb_seqs) {
-    if (!path || !blob || !offsets || !nb_seqs) return BFT_SEQFILE_E_IO;
-    *blob = nullptr;
-    *offsets = nullptr;
-    *nb_seqs = 0;
+namespace {
+// the name of the record whose header line is [at, end): what follows '>' / '@' up to the first blank; an empty one becomes the record's ordinal
+void add_name(const char* d, size_t at, size_t end, std::string* names, std::vector<uint64_t>* name_off) {
+    if (!names) return;
+    size_t e = at + 1;
+    while (e < end && d[e] != ' ' && d[e] != '\t') e++;
+    if (e > at + 1) names->append(d + at + 1, e - at - 1);
+    else names->append(std::to_string(name_off->size() - 1));
+    names->push_back('\0');
+    name_off->push_back(names->size());
+}
+
+// the reader behind both entry points; names / name_off: null, or the records' names, each ended by a NUL, and nb_seqs + 1 offsets into them
+int read_records(const char* path, char** blob, uint64_t** offsets, uint64_t* nb_seqs, std::string* names, std::vector<uint64_t>* name_off) {
     std::string data;
     const int rc = read_all(path, data);
     if (rc != BFT_SEQFILE_OK) return rc;
@@ -52,6 +61,7 @@ extern "C" int bft_seqfile_read(const char* path, char** blob, uint64_t** offset
                 if (d[at] == '>') {  // (at < n: d[at] is the line's first character, or its line feed)
                     if (open) off.push_back(seqs.size());
                     open = true;
+                    add_name(d, at, end, names, name_off);
                 } else {
                     seqs.append(d + at, end - at);
                 }
@@ -65,6 +75,7 @@ extern "C" int bft_seqfile_read(const char* path, char** blob, uint64_t** offset
                 if (end == at) { at = next; continue; }  // blank lines between records
                 if (d[at] != '@') return BFT_SEQFILE_E_FORMAT;
                 if (next >= n) return BFT_SEQFILE_E_FORMAT;  // no sequence line
+                add_name(d, at, end, names, name_off);
                 at = next;
                 end = line_end(d, n, at, &next);
                 const size_t s0 = at, s1 = end;
@@ -94,6 +105,45 @@ extern "C" int bft_seqfile_read(const char* path, char** blob, uint64_t** offset
     *blob = b;
     *offsets = o;
     *nb_seqs = off.size() - 1;
+    return BFT_SEQFILE_OK;
+}
+
+}  // namespace
+
+extern "C" int bft_seqfile_read(const char* path, char** blob, uint64_t** offsets, uint64_t* nb_seqs) {
+    if (!path || !blob || !offsets || !nb_seqs) return BFT_SEQFILE_E_IO;
+    *blob = nullptr;
+    *offsets = nullptr;
+    *nb_seqs = 0;
+    return read_records(path, blob, offsets, nb_seqs, nullptr, nullptr);
+}
+
+extern "C" int bft_seqfile_read_named(const char* path, char** blob, uint64_t** offsets, char** names, uint64_t** name_offsets, uint64_t* nb_seqs) {
+    if (!path || !blob || !offsets || !names || !name_offsets || !nb_seqs) return BFT_SEQFILE_E_IO;
+    *blob = nullptr;
+    *offsets = nullptr;
+    *names = nullptr;
+    *name_offsets = nullptr;
+    *nb_seqs = 0;
+    std::string nm;
+    std::vector<uint64_t> no(1, 0);
+    const int rc = read_records(path, blob, offsets, nb_seqs, &nm, &no);
+    if (rc != BFT_SEQFILE_OK) return rc;
+    char* b = (char*)malloc(nm.size() ? nm.size() : 1);
+    uint64_t* o = (uint64_t*)malloc(no.size() * sizeof(uint64_t));
+    if (!b || !o || no.size() != *nb_seqs + 1) {
+        free(b);
+        free(o);
+        bft_seqfile_free(*blob, *offsets);
+        *blob = nullptr;
+        *offsets = nullptr;
+        *nb_seqs = 0;
+        return BFT_SEQFILE_E_IO;
+    }
+    if (!nm.empty()) memcpy(b, nm.data(), nm.size());
+    memcpy(o, no.data(), no.size() * sizeof(uint64_t));
+    *names = b;
+    *name_offsets = o;
     return BFT_SEQFILE_OK;
 }
 

@@ -14,6 +14,10 @@ extern "C" {
  * records are kept as sequences of length 0, an empty (or all-blank) file gives zero sequences.  No gzip.  *blob and *offsets are malloc'ed
  * (free() them, or bft_seqfile_free); on an error nothing is allocated.  The characters are not interpreted: what is not ACGTU is the kernels' business. */
 int bft_seqfile_read(const char* path, char** blob, uint64_t** offsets, uint64_t* nb_seqs);
+/* The same with the records' names: the header line behind '>' / '@' up to the first blank or tab; an empty name becomes the record's ordinal in the
+ * file, counted from 0 (the sequence index of the calls that take the blob).  *names holds them one after the other, each ended by a NUL,
+ * *name_offsets nb_seqs + 1 offsets into it (name i starts at name_offsets[i]); both are malloc'ed (free() them). */
+int bft_seqfile_read_named(const char* path, char** blob, uint64_t** offsets, char** names, uint64_t** name_offsets, uint64_t* nb_seqs);
 void bft_seqfile_free(char* blob, uint64_t* offsets);
 #ifdef __cplusplus
 }

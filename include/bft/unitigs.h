@@ -41,6 +41,16 @@ void extract_unitig_graph_to_disk(BFT* graph, int min_shared, bool colors, char*
  * above. */
 void extract_bubbles_to_disk(BFT* graph, int min_shared, int max_branch_length, char* filename_output);
 
+/* Where do sequences run in that graph?  Every record of the plain-text FASTA / FASTQ file filename_sequences is threaded through the compacted graph
+ * at min_shared (bft_gpu_thread_sequences defines the walks: the maximal stretches of a sequence whose k-mers are all in segments and follow each
+ * other inside a segment or across a link) and written to filename_output as GAF, one line per walk in the call's order, fields separated by tabs:
+ *   <name>  <sequence length>  <start>  <end>  +  <path>  <path length>  <path start>  <path end>  <matches>  <block length>  255  cg:Z:<matches>=
+ * The name is the record's header up to the first blank (an empty one: the record's number, from 0); the path is >i or <i per step, i a segment id of
+ * extract_unitig_graph_to_disk at the same min_shared (<i reads the reverse complement of the S line), so the file joins to the GFA; a walk is an
+ * exact match: matches = block length = end - start = path end - path start.  min_shared and errors as above; a sequence file that cannot be read is
+ * an error too. */
+void thread_sequences_to_disk(BFT* graph, int min_shared, char* filename_sequences, char* filename_output);
+
 #ifdef __cplusplus
 }
 #endif

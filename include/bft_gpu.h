@@ -550,6 +550,52 @@ int bft_gpu_unitig_segment_of(bft_gpu* h, const uint32_t* members, uint64_t n_me
 int bft_gpu_unitig_segment_of_dev(bft_gpu* h, const void* d_members, uint64_t n_members, const void* d_seg_off, uint64_t n_segments, void* d_seg_of, void* d_pos,
                                   uint64_t cap, void* hip_stream);
 
+/* Sequence threading: where does a sequence run in the compacted graph?  For a batch of sequences and a compacted graph of the handle's CANONICAL
+ * index, the maximal walks over oriented segments that the sequences spell exactly.  An extension: the reference has no counterpart.
+ * Inputs: k, the stored table and its rows, as bft_gpu_extract; the graph arrays of bft_gpu_unitig_graph(t): seg_off, link_off, links, S = n_segments,
+ * out(X) as in the bubbles' text; seg_of and pos from bft_gpu_unitig_segment_of on that graph (n_rows entries each);
+ * m_i = seg_off[i + 1] - seg_off[i] - (k - 1), the members of segment i.  The sequences are seqs / seq_off as for bft_gpu_query_sequences.
+ *   position (s, p)  of sequence s, 0 <= p <= len_s - k: its window is the word w of k characters from p.  It is VALID when no character is outside
+ *                    ACGTU in either case (U reads as T): the rule of bft_gpu_insert_sequences.  c is the smaller of w and rc(w), A < C < G < T.
+ *                    Strand sigma = 0 when w == c, a palindromic w included; else sigma = 1.
+ *   located          a valid position whose c is stored at row r with seg_of[r] != 0xFFFFFFFF.  It reads along oriented segment
+ *                    X = seg_of[r] ^ sigma, i = X >> 1.  Its index is q = pos[r] when X is even, q = m_i - 1 - pos[r] when X is odd.  A position
+ *                    that is invalid, absent from the index, or in no segment is NOT located; each of the three is counted separately.
+ *   transition       between located neighbours (s, p) = (X, q) and (s, p + 1) = (Y, r): INSIDE when Y == X and r == q + 1; ACROSS when
+ *                    q == m_X - 1, r == 0 and Y is in out(X); otherwise a BREAK.
+ *   walk             a maximal run of consecutive located positions of one sequence whose transitions are all inside or across.  Its STEPS are
+ *                    the oriented segments visited: the first position opens a step, every across transition opens the next one.  So a sequence
+ *                    that runs twice round a cyclic unitig gives S+ S+ S+, a hairpin gives S+ S-, a homopolymer run gives one step per window.
+ *                    Walks come in ascending (s, p); no walk spans two sequences.
+ * Outputs (every one may be NULL; with all NULL the call counts): walks, 4 x uint64 per walk {s, p0, n_w, q0} = the sequence index, the first
+ * position, the number of positions, the index of the first position in the first step; walk_off, n_walks + 1 uint64 offsets into steps; steps, uint32
+ * oriented segments.  The walk covers characters [p0, p0 + n_w + k - 1) of the sequence; on its path (the steps spelled with k - 1 overlap) it covers
+ * [q0, q0 + n_w + k - 1).  walks and walk_off share walks_cap (walks; walk_off holds walks_cap + 1 entries), steps has steps_cap entries.
+ * counts (8 x uint64) = {n_walks, n_steps, positions, invalid positions, valid positions absent from the index, present but in no segment, breaks
+ * between two located neighbours, rows with s > rc(s)}.
+ * A cap too small for an output that is not NULL: BFT_GPU_E_NOSPACE, counts filled, nothing else written.  counts[7] != 0: the index is not canonical,
+ * BFT_GPU_E_STATE, counts filled, nothing else written.  n_rows different from the index's k-mer count: BFT_GPU_E_ARG.  A call with 2^32 characters or
+ * more, or 2^32 sequences or more: BFT_GPU_E_LIMIT; at most 2^31 - 1 segments and k-mers (BFT_GPU_E_LIMIT).  Pending insertions are built first;
+ * "compact_table": the sorted table comes back.  Kernel time and "build_stages" as everywhere else; stage names start "threading:".
+ * The host form validates the graph arrays as bft_gpu_unitig_bubbles and bft_gpu_unitig_segment_of do: link offsets that decrease, link_off[2S] !=
+ * n_links, a target >= 2S, segment offsets that grow by less than k, and sequence offsets that decrease are BFT_GPU_E_ARG, with nothing written.  In
+ * both forms a seg_of entry >= 2S, or a pos >= m_i, makes the position "in no segment", and a link list longer than 4 entries or past n_links is the
+ * empty list.  The scratch (17 bytes per character of the batch, plus 4 bytes per bucket of the table) is the call's own: it interleaves freely with
+ * bft_gpu_unitig_graph, the bubbles, the queries and the other families on one handle. */
+int bft_gpu_thread_sequences(bft_gpu* h, const char* seqs, const uint64_t* seq_off, uint64_t nb_seqs, const uint32_t* seg_of, const uint32_t* pos,
+                             uint64_t n_rows, const uint64_t* seg_off, uint64_t n_segments, const uint64_t* link_off, const uint32_t* links, uint64_t n_links,
+                             uint64_t* walks, uint64_t* walk_off, uint64_t walks_cap, uint32_t* steps, uint64_t steps_cap, uint64_t counts[8]);
+/* The same on device buffers on hip_stream (NULL = the handle's stream), d_seqs holding total_chars characters, without host synchronisation and
+ * without a count read back: d_counts (8 x uint64) is always written; d_walks receives the walks below walks_cap, d_walk_off its entries j <=
+ * min(n_walks, walks_cap), d_steps the steps below steps_cap; nothing is written beyond a cap.  When d_counts[7] != 0 the index is not canonical and
+ * the other outputs are unspecified.  Nothing is validated up front, but no lane reads outside the given graph arrays and tables; the sequence
+ * offsets are trusted as by bft_gpu_query_sequences_dev (they do not decrease and end at total_chars at the most).  Not inside a graph capture
+ * (BFT_GPU_E_ARG). */
+int bft_gpu_thread_sequences_dev(bft_gpu* h, const void* d_seqs, const void* d_seq_off, uint64_t nb_seqs, uint64_t total_chars, const void* d_seg_of,
+                                 const void* d_pos, uint64_t n_rows, const void* d_seg_off, uint64_t n_segments, const void* d_link_off, const void* d_links,
+                                 uint64_t n_links, void* d_walks, void* d_walk_off, uint64_t walks_cap, void* d_steps, uint64_t steps_cap, void* d_counts,
+                                 void* hip_stream);
+
 /* Connected components:get_nb_connected_component(bft, &nb, BFS | DFS) and (..., BFS_subgraph | DFS_subgraph, nb_id_genomes, ids...) (reference
  * snippets.h, src/snippets.c:605-960) without the walk, over the whole graph (nb_ids = 0) or the sub-graph of genome_ids.
  *   vertices  the stored k-mers; in a sub-graph, only the members: k-mers whose colour set holds EVERY id of genome_ids;
